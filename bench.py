@@ -8,7 +8,14 @@ the rank's utterances (already resident in HBM), all-reduce (sum) of the weight 
 RCCL, divide by the active ranks, SGD update.  Weak scaling: every rank processes --utts
 utterances per step.  Prints ONE JSON line on rank 0.
 
-  python bench.py --gpus 1 --steps 5 --warmup 2
+A plain run sets up, warms up, times the steps and prints the headline figure.  --full adds, after the
+timed region: the per-kernel roofline (instrumented steps), the Viterbi decode rate, the CPU baseline with
+the engine-vs-oracle correctness gate, and the config-3 / config-5 entries.  --dump-outputs DIR writes what
+the last timed step left for its caller (fp64, as DIR/<name>.npy): `lambda`, the weights after its SGD update,
+and `lambda_acc`, their running sum over the steps (the SGD step consumes the gradient and zeroes it).  The
+inputs are seeded, so two builds can be compared output for output.
+
+  python bench.py --gpus 1 --steps 5 --warmup 2 [--dump-outputs DIR] [--full]
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
          --master-port P bench.py --gpus N --steps K --warmup W
 """
@@ -275,7 +282,14 @@ def main():
                          "leaves the dense contractions (fp64 throughout; 3e-8 on the gradient, contract 1e-4); fast32: f32 MFMA contractions (opt-in)")
     ap.add_argument("--scratch-gib", type=int, default=96, help="device scratch budget per chunk of utterances")
     ap.add_argument("--no-other-configs", action="store_true", help="skip the config-3 / config-5 steps after the timed region")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed region also measure the roofline, the decode rate, the CPU baseline with the oracle "
+                         "gate (--no-cpu-baseline skips it) and the config-3 / config-5 entries (--no-other-configs skips them)")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write the last timed step's results (lambda after the SGD update, lambda_acc) as DIR/<name>.npy")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     # the JSON line must be the only thing on stdout: until it is printed, file descriptor 1 points
     # at stderr, so that library banners (RCCL prints one under NCCL_DEBUG=VERSION) do not mix in
@@ -363,6 +377,29 @@ def main():
     out = None
     gate_err = None
     if rank == 0:
+        out = {
+            "metric": "utterances/sec SCRF forward-backward (TIMIT-shape)",
+            "value": round(U * world * args.steps / dt, 2),
+            "unit": "utterances/s",
+            "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+            "ms_per_step": round(1e3 * dt / args.steps, 3),
+            "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
+            "dtype": "f64", "data": "synthetic",
+            "config": {"workload": "BASELINE config 2: segmental CRF forward-backward, 48 labels, max-seg-len 25, "
+                                   "39-dim x 300-frame utterances, stdstate map (lambda_len 18528)",
+                       "utts_per_rank_per_step": U, "global_minibatch": U * world, "precision": args.precision,
+                       "parallelism": "dp%d" % world,
+                       "rccl_ranks": dist.get_world_size() if dist is not None else 0,
+                       "collective": ("engine RCCL communicator (scrf_allreduce_grad)" if native else "torch.distributed all_reduce (nccl = RCCL)") if dist is not None else None,
+                       "step_sync": "scrf_fb_batch returns once the recursion's status is known (one event wait per step)"},
+        }
+        if args.dump_outputs:
+            # what a caller of the step holds after the last timed one: the updated weights and their running sum
+            # (k_sgd_step applies the gradient and zeroes it, trainers/CRF_SGTrainer.cpp:317-321)
+            os.makedirs(args.dump_outputs, exist_ok=True)
+            np.save(os.path.join(args.dump_outputs, "lambda.npy"), np.asarray(eng.get_lambda(), dtype=np.float64))
+            np.save(os.path.join(args.dump_outputs, "lambda_acc.npy"), np.asarray(eng.get_lambda_acc(), dtype=np.float64))
+    if rank == 0 and args.full:
         # ---- correctness gate, part 1: the timed steps left a finite model behind
         if not np.isfinite(eng.get_lambda()).all():
             gate_err = "lambda is not finite after the timed steps"
@@ -479,23 +516,7 @@ def main():
                              # (4 N_seg L F per utterance, 0.466 GFLOP) on the fp64 matrix pipe = 169 k utterances/s per GPU
                              "survey_8d_dense_gflop_per_utt": round(4.0 * nseg * L * F / 1e9, 4),
                              "frac_of_survey_8d_mfma_bound": round(4.0 * nseg * L * F * U / (mfma_peak * 1e12) * 1e3 / step_ms, 4)}}
-        out = {
-            "metric": "utterances/sec SCRF forward-backward (TIMIT-shape)",
-            "value": round(U * world * args.steps / dt, 2),
-            "unit": "utterances/s",
-            "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-            "ms_per_step": round(1e3 * dt / args.steps, 3),
-            "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
-            "dtype": "f64", "data": "synthetic",
-            "config": {"workload": "BASELINE config 2: segmental CRF forward-backward, 48 labels, max-seg-len 25, "
-                                   "39-dim x 300-frame utterances, stdstate map (lambda_len 18528)",
-                       "utts_per_rank_per_step": U, "global_minibatch": U * world, "precision": args.precision,
-                       "parallelism": "dp%d" % world,
-                       "rccl_ranks": dist.get_world_size() if dist is not None else 0,
-                       "collective": ("engine RCCL communicator (scrf_allreduce_grad)" if native else "torch.distributed all_reduce (nccl = RCCL)") if dist is not None else None,
-                       "step_sync": "scrf_fb_batch returns once the recursion's status is known (one event wait per step)"},
-            "roofline": roofline,
-        }
+        out["roofline"] = roofline
         # decode half of the metric: best-path labels of the same resident batch, bit-identical
         # to the reference-order evaluation (fp64-MFMA arc weights + reference-order recomputation of the
         # entries a rounding-error bound cannot clear); one untimed call first
@@ -535,7 +556,7 @@ def main():
             out["parity_gate"] = "skipped (--no-cpu-baseline): finiteness of lambda only"
     batch.close()
     eng.close()
-    if rank == 0 and world == 1 and out is not None and not args.no_other_configs:
+    if rank == 0 and world == 1 and out is not None and args.full and not args.no_other_configs:
         # (at N = 1 only, like the CPU baseline: the other ranks would sit in the barrier below meanwhile)
         # the north-star training shape and the stress shape on the same clock (general path: materialised windows,
         # dense fp64-MFMA contractions); parity cases elsewhere, throughput entries here.  After the config-2 engine

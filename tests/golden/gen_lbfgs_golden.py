@@ -37,6 +37,9 @@ def parse_trace(text):
 
 def run_reference_trace():
     lib = os.path.join(ROOT, "oracle", "_ref")
+    exe = os.path.join(lib, "lbfgs_ref_trace")   # built by oracle/Makefile next to the library
+    if os.path.exists(exe):
+        return subprocess.run([exe], capture_output=True, text=True, check=True).stdout
     if not os.path.exists(os.path.join(lib, "liblbfgs_ref.so")):
         raise SystemExit("oracle/_ref/liblbfgs_ref.so is missing: run `make -C oracle` where /root/reference exists")
     with tempfile.TemporaryDirectory() as td:

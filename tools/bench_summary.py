@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Readable summary of a bench.py JSON line: tools/bench_summary.py gpurun_out/bench.json"""
+"""Readable summary of a `bench.py --full` JSON line: tools/bench_summary.py bench.json"""
 import json
 import sys
 

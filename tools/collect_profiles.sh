@@ -12,7 +12,7 @@ out=$root/gpurun_out/$tag
 rm -rf $out $root/gpurun_out/prof_${tag}_* $root/gpurun_out/pmc_${tag}*
 mkdir -p $out
 die() { echo "collect_profiles: $*" >&2; exit 1; }
-B="--precision $prec --no-cpu-baseline --no-other-configs"
+B="--full --precision $prec --no-cpu-baseline --no-other-configs"
 cd $root
 tools/prof_kernels.sh ${tag}_$prec $B --steps 5 --warmup 2 > $out/${tag}_${prec}_kernel_table.txt 2>&1 || die "kernel trace failed"
 [ -s gpurun_out/${tag}_${prec}_kernel_stats.csv ] || die "no kernel stats csv"
@@ -45,6 +45,6 @@ done
 echo "shape traces done"
 tools/run_microbench.sh > /dev/null 2>&1
 cp gpurun_out/microbench.txt $out/${tag}_microbench.txt
-python bench.py --steps 20 --warmup 5 > $out/${tag}_bench_$prec.json 2> $out/${tag}_bench_$prec.err
+python bench.py --full --steps 20 --warmup 5 > $out/${tag}_bench_$prec.json 2> $out/${tag}_bench_$prec.err
 echo "bench rc=$?"
 ls -la $out

@@ -5,7 +5,7 @@ tag=$1; shift
 root=${GRAFT_REPO_ROOT:-/root/repo}
 out=$root/gpurun_out/prof_$tag
 cd /tmp && export TMPDIR=/tmp
-rocprofv3 --kernel-trace --stats --output-format csv -d $out -o $tag -- python3 $root/bench.py "$@" > $out.log 2>&1
+rocprofv3 --kernel-trace --stats --output-format csv -d $out -o $tag -- python3 $root/bench.py --full "$@" > $out.log 2>&1
 f=$(find $out -name "*kernel_stats.csv" | head -1)
 cp $f $root/gpurun_out/${tag}_kernel_stats.csv
 python3 - "$f" <<'PY'
