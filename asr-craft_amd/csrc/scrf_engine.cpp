@@ -95,6 +95,8 @@ struct scrf_engine_s {
   // that is a no-op when an utterance of the batch failed (d_latch): a failed scrf_fb_batch leaves the
   // gradient as it was, and a NUMERIC failure of the linear-domain recursion can be redone in the log domain
   double* d_stage = nullptr;
+  // sparse maps (scrf_sparse.hip): lambda re-laid index-major per call, [0] state block, [1] transition block
+  double* d_lamT[2] = {nullptr, nullptr};
   double* d_sums_stage = nullptr;
   int* d_latch = nullptr;     // {status code, utterance} of the first failed utterance of the batch in flight
   int* h_latch = nullptr;     // pinned copy, valid once ev_status has completed
@@ -259,7 +261,19 @@ static int build_layout(const scrf_config& c, ScrfLayout* l, std::string* why) {
   if (c.model_type == SCRF_STDSEG && c.num_labs % c.lab_max_dur != 0) { *why = "stdseg: the number of all labels and the maximum duration of labels do not correspond (nLabs = nActualLabs * labMaxDur)"; return SCRF_ERR_INVALID; }
   if (c.model_type > SCRF_STDSEG_NO_DUR_NO_SEGTRANSFTR) { *why = "unknown model_type"; return SCRF_ERR_INVALID; }
   if (c.model_type == SCRF_STDFRAME && c.lab_max_dur != 1) { *why = "the maximum duration of labels must be 1 for \"stdframe\" CRF model."; return SCRF_ERR_INVALID; }  // CRFTrain/src/Main.cpp:574-578
-  if (c.map_type > SCRF_STDTRANS) { *why = "only dense stdstate/stdtrans feature maps are built"; return SCRF_ERR_INVALID; }
+  if (c.map_type > SCRF_STDSPARSETRANS) { *why = "unknown map_type"; return SCRF_ERR_INVALID; }
+  const bool sparse = c.map_type == SCRF_STDSPARSE || c.map_type == SCRF_STDSPARSETRANS;
+  if (sparse) {   // CRF_StdSparseFeatureMap: the frame model and the TIMIT-demo model, one state per label
+    if (c.model_type == SCRF_STDSEG_NO_DUR_NO_TRANSFTR) { *why = "crf_featuremap must be \"stdstate\" for \"stdseg_no_dur_no_transftr\" CRF model."; return SCRF_ERR_INVALID; }
+    if (c.model_type == SCRF_STDSEG) { *why = "sparse feature maps (stdsparse/stdsparsetrans) are not built for the \"stdseg\" CRF model; use \"stdframe\" or \"stdseg_no_dur_no_segtransftr\""; return SCRF_ERR_INVALID; }
+    if (c.model_type == SCRF_STDSEG_NO_DUR) { *why = "sparse feature maps (stdsparse/stdsparsetrans) are not built for the \"stdseg_no_dur\" CRF model; use \"stdframe\" or \"stdseg_no_dur_no_segtransftr\""; return SCRF_ERR_INVALID; }
+    if (c.num_states != 1) { *why = "sparse feature maps (stdsparse/stdsparsetrans) are built for crf_states = 1 only"; return SCRF_ERR_INVALID; }
+    if (c.num_feas % 2) { *why = "a sparse feature map reads (index, value) pairs: num_feas must be even (the reference reads past the window otherwise)"; return SCRF_ERR_INVALID; }
+    if ((c.use_state_ftrs && c.state_fidx_start != 0) || (c.use_trans_ftrs && c.trans_fidx_start != 0)) {
+      *why = "a sparse feature map needs feature index start 0: the reference adds the index to the label's block without subtracting the start, so another start reads outside the label's weights";
+      return SCRF_ERR_INVALID;
+    }
+  }
   if (c.model_type == SCRF_STDSEG_NO_DUR_NO_TRANSFTR && (c.map_type != SCRF_STDSTATE || c.use_trans_ftrs)) {   // CRFTrain/src/Main.cpp:465-468
     *why = "crf_featuremap must be \"stdstate\" for \"stdseg_no_dur_no_transftr\" CRF model.";
     return SCRF_ERR_INVALID;
@@ -271,8 +285,13 @@ static int build_layout(const scrf_config& c, ScrfLayout* l, std::string* why) {
   l->use_sb = c.use_state_bias != 0; l->use_tb = c.use_trans_bias != 0;
   l->sfs = c.state_fidx_start; l->sfe = c.state_fidx_end; l->tfs = c.trans_fidx_start; l->tfe = c.trans_fidx_end;
   l->sbv = c.state_bias_val; l->tbv = c.trans_bias_val;
-  if (l->use_sf && (l->sfe < l->sfs || l->sfe >= l->F)) { *why = "state feature range outside the window vector"; return SCRF_ERR_INVALID; }
-  if (l->use_tf && (l->tfe < l->tfs || l->tfe >= l->F)) { *why = "transition feature range outside the window vector"; return SCRF_ERR_INVALID; }
+  if (sparse) {
+    // the ranges bound the pair INDEX; the biases are added unscaled (CRF_StdSparseFeatureMap.cpp:74-79, :113-118)
+    l->sbv = l->tbv = 1.0;
+    if (l->use_sf && l->sfe >= 0x3fffffffu) { *why = "state feature index range too large"; return SCRF_ERR_INVALID; }
+    if (l->use_tf && l->tfe >= 0x3fffffffu) { *why = "transition feature index range too large"; return SCRF_ERR_INVALID; }
+  } else if (l->use_sf && (l->sfe < l->sfs || l->sfe >= l->F)) { *why = "state feature range outside the window vector"; return SCRF_ERR_INVALID; }
+  if (!sparse && l->use_tf && (l->tfe < l->tfs || l->tfe >= l->F)) { *why = "transition feature range outside the window vector"; return SCRF_ERR_INVALID; }
   l->nsfe = l->use_sf ? l->sfe - l->sfs + 1 : 0;
   l->ntfe = l->use_tf ? l->tfe - l->tfs + 1 : 0;
   l->nsf = l->nsfe + (l->use_sb ? 1 : 0);
@@ -363,6 +382,10 @@ extern "C" int scrf_create(const scrf_config* cfg, scrf_handle* out) {
   CRCHK(hipMalloc((void**)&h->d_m0, sizeof(double) * lay.L * lay.L));
   CRCHK(hipMalloc((void**)&h->d_w1, sizeof(double) * lay.L));
   if (lay.D <= 40) CRCHK(hipMalloc((void**)&h->d_dtab, sizeof(double) * fused_dur_table_doubles(lay)));
+  if (cfg->map_type >= SCRF_STDSPARSE) {
+    if (lay.nsfe + lay.use_sb) CRCHK(hipMalloc((void**)&h->d_lamT[0], sizeof(double) * ((size_t)lay.nsfe + lay.use_sb) * lay.L));
+    if (lay.ntfe + lay.use_tb) CRCHK(hipMalloc((void**)&h->d_lamT[1], sizeof(double) * ((size_t)lay.ntfe + lay.use_tb) * lay.L * lay.L));
+  }
   if (cfg->model_type == SCRF_STDSEG && !lay.use_tf) CRCHK(hipMalloc((void**)&h->d_sl_tab, sizeof(double) * (2 * (size_t)lay.L * lay.L + 8)));
   CRCHK(hipMalloc((void**)&h->d_e0, sizeof(double) * lay.L * lay.L));
   CRCHK(hipMalloc((void**)&h->d_et0, sizeof(double) * lay.L * lay.L));
@@ -413,6 +436,7 @@ extern "C" int scrf_destroy(scrf_handle h) {
   if (h->own_grad) hipFree(h->d_grad);
   hipFree(h->d_grad2); hipFree(h->d_sums2); hipFree(h->scratch2);
   hipFree(h->d_stage); hipFree(h->d_sums_stage); hipFree(h->d_latch);
+  hipFree(h->d_lamT[0]); hipFree(h->d_lamT[1]);
   if (h->h_latch) hipHostFree(h->h_latch);
   if (h->h_sums) hipHostFree(h->h_sums);
   if (h->ev_sums) hipEventDestroy(h->ev_sums);
@@ -842,8 +866,9 @@ extern "C" int scrf_batch_create(scrf_handle h, const scrf_utt* utts, uint32_t n
   // fused window synthesis: one segment-recipe stream without context whose window is exactly
   // the state feature range, no transition features
   const int f32_cfg = h->cfg.train_precision == SCRF_PREC_FAST32;
-  const bool hybrid_first = h->hybrid_first && lay.L > 64 && n_streams == 1 && !lay.use_tf;
-  const bool seg_stream0 = !hybrid_first && !by_windows && n_streams >= 1 && h->cfg.model_type != SCRF_STDSEG_NO_DUR && h->cfg.model_type != SCRF_STDSEG && lay.use_sf &&
+  const bool sparse_map = h->cfg.map_type >= SCRF_STDSPARSE;   // the general path only
+  const bool hybrid_first = !sparse_map && h->hybrid_first && lay.L > 64 && n_streams == 1 && !lay.use_tf;
+  const bool seg_stream0 = !sparse_map && !hybrid_first && !by_windows && n_streams >= 1 && h->cfg.model_type != SCRF_STDSEG_NO_DUR && h->cfg.model_type != SCRF_STDSEG && lay.use_sf &&
                            recipes[0].extract_seg_ftr && !recipes[0].left_ctx && !recipes[0].right_ctx && lay.sfs == 0 &&
                            lay.nsfe == 8 * recipes[0].in_width + lay.D && fused_supported(lay, recipes[0].in_width, f32_cfg);
   // "mixed" (round 4, BASELINE config 3's shape): the state features are exactly stream 0's segment-recipe window and the
@@ -853,7 +878,7 @@ extern "C" int scrf_batch_create(scrf_handle h, const scrf_utt* utts, uint32_t n
   // fit (L > 64).  The window vectors stay materialised, but the five sampled blocks -- 5 W of the 8 W + D columns, copies
   // of raw frames -- leave the two dense contractions: scores get their share from the per-frame projections P (k_add_p),
   // counts through the per-frame sums Z (k_lin_z, Z^T F), exactly as on the fused path.
-  b->hybrid_ok = !by_windows && n_streams == 1 && h->cfg.model_type != SCRF_STDSEG_NO_DUR && h->cfg.model_type != SCRF_STDSEG && lay.use_sf &&
+  b->hybrid_ok = !sparse_map && !by_windows && n_streams == 1 && h->cfg.model_type != SCRF_STDSEG_NO_DUR && h->cfg.model_type != SCRF_STDSEG && lay.use_sf &&
                  !lay.use_tf && recipes[0].extract_seg_ftr && !recipes[0].left_ctx && !recipes[0].right_ctx && lay.sfs == 0 && lay.D >= 2 &&
                  lay.nsfe == 8 * recipes[0].in_width + lay.D && (hybrid_first || !fused_supported(lay, recipes[0].in_width, f32_cfg));
   const bool mixed_ok = seg_stream0 && n_streams >= 2 && lay.use_tf && lay.tfs >= lay.nsfe && h->fuse_mixed;
@@ -1045,6 +1070,8 @@ struct ChunkBufs {
   bool la = false;           // SCRF_PREC_FASTLIN: linear window average (6 groups in P / Z, no avg group in the dense parts)
   double* slab_d = nullptr;  // duration + bias counts of the wave-specialised count kernel (behind slab_s)
   int expf_tiles = 1;        // tile list the fused count kernel walks
+  ScrfSparseIndex spx[2];    // sparse maps: inverted index + bias slab of the state [0] / transition [1] counts
+  bool lamT_ready = false;   // sparse maps: h->d_lamT already re-laid for this call (scrf_fb_batch: once, before the lanes fork)
 };
 
 struct Need { bool fb, post, beta, vit; bool fused = false; bool vitfast = false; bool la = false; bool hybrid = false; };
@@ -1060,6 +1087,9 @@ static uint32_t decode_fix_cap(uint64_t nseg, uint32_t L) {
 // training path only
 // STDSEG_NO_DUR: one transition matrix per window (scrf_segtrans.hip); its own workgroup recursion
 static bool segtrans(scrf_handle h) { return h->cfg.model_type == SCRF_STDSEG_NO_DUR; }
+
+// stdsparse / stdsparsetrans (scrf_sparse.hip): always the general path, scores and counts by the sparse kernels
+static bool sparse(scrf_handle h) { return h->cfg.map_type >= SCRF_STDSPARSE; }
 
 static bool wave_path(scrf_handle h, bool post) {
   if (h->force_fb || segtrans(h)) return false;
@@ -1125,6 +1155,8 @@ static size_t chunk_bytes(scrf_handle h, scrf_batch b, uint64_t nutt, uint64_t n
       if (segtrans(h)) {
         tot += pad256(nseg * LL * sizeof(double));                    // XI2
         tot += pad256((size_t)segtrans_chunks(nseg, LL, l.ntf) * LL * l.ntf * sizeof(double));
+      } else if (l.use_tf && sparse(h)) {
+        tot += pad256(nfr * LL * sizeof(double)) + pad256(nfr * 8);  // XI, xrow_next
       } else if (l.use_tf) {
         tot += pad256(nfr * LL * sizeof(double)) + pad256(nfr * 8);  // XI, xrow_next
         uint32_t nch_t = transframe_chunks(nfr, (uint32_t)LL, scrf_spec_trans(l).nfun(), h->cfg.train_precision == SCRF_PREC_FAST32);
@@ -1132,15 +1164,21 @@ static size_t chunk_bytes(scrf_handle h, scrf_batch b, uint64_t nutt, uint64_t n
       } else if (!wave_path(h, nd.post)) {
         tot += pad256(nutt * LL * sizeof(double));
       }
-      const uint64_t rpc_s = expf_rows_per_chunk(nseg);
-      uint64_t nch_s = nd.fused ? 512 : (nseg + rpc_s - 1) / rpc_s;
-      tot += pad256(nch_s * l.L * l.nsf * sizeof(double));
+      if (sparse(h)) {
+        tot += sparse_counts_bytes(nseg, l.F, l.nsfe, l.L);
+        if (l.use_tf) tot += sparse_counts_bytes(nfr, l.F, l.ntfe, (uint32_t)LL);
+      } else {
+        const uint64_t rpc_s = expf_rows_per_chunk(nseg);
+        uint64_t nch_s = nd.fused ? 512 : (nseg + rpc_s - 1) / rpc_s;
+        tot += pad256(nch_s * l.L * l.nsf * sizeof(double));
+      }
     }
   }
   if (nd.vit) tot += 2 * pad256(nfr * l.L * sizeof(uint16_t));
   return tot + 4096;
 }
 
+static uint64_t l_F2(scrf_handle h) { return h->lay.F / 2; }
 // largest u1 > u0 whose chunk fits the budget (always at least one utterance)
 static uint32_t plan_chunk(scrf_handle h, scrf_batch b, uint32_t u0, const Need& nd) {
   uint32_t u1 = u0 + 1;
@@ -1149,6 +1187,7 @@ static uint32_t plan_chunk(scrf_handle h, scrf_batch b, uint32_t u0, const Need&
     uint64_t nfr = b->frame_off[u1 + 1] - b->frame_off[u0], nseg = b->seg_off[u1 + 1] - b->seg_off[u0];
     if (chunk_bytes(h, b, u1 + 1 - u0, nfr, nseg, nd) > h->cfg.scratch_bytes) break;
     if (nfr > 0x7fffffffull) break;
+    if (sparse(h) && nseg * (l_F2(h)) > 0xffffffffull) break;   // the sparse index's entry positions are 32-bit
     u1++;
   }
   return u1;
@@ -1256,6 +1295,9 @@ static int carve(scrf_handle h, scrf_batch b, uint32_t u0, uint32_t u1, const Ne
         cb->nch_t = segtrans_chunks(nseg, LL, l.ntf);
         cb->rpc_t = (nseg + cb->nch_t - 1) / cb->nch_t;
         cb->slab_t = a.take<double>((size_t)cb->nch_t * LL * l.ntf);
+      } else if (l.use_tf && sparse(h)) {
+        cb->XI = a.take<double>(nfr * LL);
+        cb->xrow_next = a.take<uint64_t>(nfr);
       } else if (l.use_tf) {
         cb->XI = a.take<double>(nfr * LL);
         cb->xrow_next = a.take<uint64_t>(nfr);
@@ -1264,6 +1306,10 @@ static int carve(scrf_handle h, scrf_batch b, uint32_t u0, uint32_t u1, const Ne
         cb->slab_t = a.take<double>((size_t)cb->nch_t * LL * l.ntf);
       } else if (!cb->wave) {
         cb->xi_acc = a.take<double>(nutt * LL);
+      }
+      if (sparse(h)) {
+        sparse_counts_carve(a.take<char>(sparse_counts_bytes(nseg, l.F, l.nsfe, l.L)), nseg, l.F, l.nsfe, l.L, &cb->spx[0]);
+        if (l.use_tf) sparse_counts_carve(a.take<char>(sparse_counts_bytes(nfr, l.F, l.ntfe, (uint32_t)LL)), nfr, l.F, l.ntfe, (uint32_t)LL, &cb->spx[1]);
       }
       cb->rpc_s = expf_rows_per_chunk(nseg);
       cb->nch_s = (uint32_t)((nseg + cb->rpc_s - 1) / cb->rpc_s);
@@ -1274,7 +1320,7 @@ static int carve(scrf_handle h, scrf_batch b, uint32_t u0, uint32_t u1, const Ne
         cb->nch_s = fused_expf_blocks(l, b->recipe[0].in_width, h->cfg.train_precision == SCRF_PREC_FAST32,
                                       b->tile_off[plan.tile_list][u1] - b->tile_off[plan.tile_list][u0], nd.la);
       }
-      cb->slab_s = a.take<double>((size_t)(nd.fused ? 512 : cb->nch_s) * l.L * l.nsf);
+      if (!sparse(h)) cb->slab_s = a.take<double>((size_t)(nd.fused ? 512 : cb->nch_s) * l.L * l.nsf);
       // dense columns + durations + bias <= nsf: the duration slab fits behind the dense one
       if (nd.fused) cb->slab_d = cb->slab_s + (size_t)cb->nch_s * l.L * plan.ncol;
     }
@@ -1413,7 +1459,7 @@ static int run_scores(scrf_handle h, scrf_batch b, uint32_t u0, uint32_t u1, Chu
       // the frame rows (k_frame_rows: the node's first window) only -- its other window rows are not written (the TIMIT
       // demo's +-6-frame context stream: 5.8 GB of the 9.3 GB window image).  The window hook (scrf_windows) and EXACT
       // precision materialise every row.
-      const bool first_only = fast && l.use_tf && !segtrans(h) && l.D > 1 && (col > l.sfe || col + b->width[s] <= l.sfs);
+      const bool first_only = fast && !sparse(h) && l.use_tf && !segtrans(h) && l.D > 1 && (col > l.sfe || col + b->width[s] <= l.sfs);
       KT_RUN("k_windows", cb.st, launch_windows(cb.st, b->d_frames[s], b->d_sframe_off[s], bv, u0, u1, nfr, r.in_width, l.D, r.left_ctx,
                      r.right_ctx, r.extract_seg_ftr, cb.X, cb.hybrid ? hybrid_row_floats(l, r.in_width) : l.F, col,
                      (first_only ? 1 : 0) | (cb.hybrid ? 2 : 0)));
@@ -1437,13 +1483,33 @@ static int run_scores(scrf_handle h, scrf_batch b, uint32_t u0, uint32_t u1, Chu
     cb.es_ready = true;
     tk.stop(2);
     nl += 2;
+  } else if (sparse(h)) {
+    // stdsparse / stdsparsetrans: the reference's pair order in every tier (bit-identical scores), lambda index-major
+    PhaseTimer tk(h, PH_K_SCORE, cb.st);
+    if (!cb.lamT_ready) launch_sp_relay(cb.st, h->d_lambda, l, 0, h->d_lamT[0]);
+    KT_RUN("k_sp_scores(state)", cb.st, launch_sp_scores(cb.st, cb.X, l.F, nullptr, nseg, h->d_lamT[0], l, 0, cb.S));
+    tk.stop(2);
+    nl += 1;
+    if (l.use_tf) {
+      if (!cb.lamT_ready) launch_sp_relay(cb.st, h->d_lambda, l, 1, h->d_lamT[1]);
+      launch_frame_rows(cb.st, bv, u0, u1, l.D, nfr, cb.xrow_cur, 0);
+      KT_RUN("k_sp_scores(trans)", cb.st, launch_sp_scores(cb.st, cb.X, l.F, cb.xrow_cur, nfr, h->d_lamT[1], l, 1, cb.M));
+      nl += 3;
+    }
   } else if (!cb.fused) {
     PhaseTimer tk(h, PH_K_SCORE, cb.st);
     if (fast) KT_RUN("k_scores_mfma(state)", cb.st, launch_scores_mfma(cb.st, cb.X, l.F, nullptr, nseg, h->d_lambda, l, scrf_spec_state(l), l.L, cb.S, f32));
     else KT_RUN("k_scores_exact(state)", cb.st, launch_scores_exact(cb.st, cb.X, l.F, nullptr, nseg, h->d_lambda, l, 0, l.L, cb.S));
     tk.stop(1);
   }
-  if (segtrans(h)) {
+  if (sparse(h)) {
+    if (!l.use_tf && !h->m0_valid) {   // bias-only transitions: the dense path's M0 (the bias value is 1 here)
+      launch_scores_exact(cb.st, cb.X, l.F, nullptr, 1, h->d_lambda, l, 1, l.L * l.L, h->d_m0);
+      launch_exp_m(cb.st, h->d_m0, l.L, 1, h->d_e0, h->d_et0, h->d_msh0);
+      h->m0_valid = true;
+      nl += 2;
+    }
+  } else if (segtrans(h)) {
     // one transition matrix per window: the same contraction over every row of X; the rows of the
     // utterance-initial segments (no predecessor) are zeroed like the reference leaves them unused
     if (fast) KT_RUN("k_scores_mfma(trans)", cb.st, launch_scores_mfma(cb.st, cb.X, l.F, nullptr, nseg, h->d_lambda, l, scrf_spec_trans(l), l.L * l.L, cb.M, f32));
@@ -1918,6 +1984,11 @@ static int fb_run(scrf_handle h, scrf_batch b, int latch[2], bool* used_lin) {
     launch_exp_m(h->stream, h->d_m0, l.L, 1, h->d_e0, h->d_et0, h->d_msh0);
     h->m0_valid = true;
   }
+  if (sparse(h)) {
+    // lambda index-major once per call, on the engine stream before the lanes fork: every chunk's score kernel reads it
+    launch_sp_relay(h->stream, h->d_lambda, l, 0, h->d_lamT[0]);
+    if (l.use_tf) launch_sp_relay(h->stream, h->d_lambda, l, 1, h->d_lamT[1]);
+  }
   if (use2) {
     HIPCHK(h, hipMemsetAsync(h->d_grad2, 0, sizeof(double) * l.lambda_len, h->stream));
     HIPCHK(h, hipMemsetAsync(h->d_sums2, 0, sizeof(double) * 4, h->stream));
@@ -1931,6 +2002,7 @@ static int fb_run(scrf_handle h, scrf_batch b, int latch[2], bool* used_lin) {
     int rc = carve(h, b, u0, u1, nd, &cb, lane);
     if (rc != SCRF_OK) return rc;
     if (!lane) { cb.grad = h->d_stage; cb.sums = h->d_sums_stage; }
+    cb.lamT_ready = sparse(h);
     if (cb.lin) *used_lin = true;
     const uint64_t nutt = u1 - u0, nfr = b->frame_off[u1] - b->frame_off[u0], nseg = b->seg_off[u1] - b->seg_off[u0];
     rc = run_scores(h, b, u0, u1, cb, fast, f32);
@@ -1952,7 +2024,7 @@ static int fb_run(scrf_handle h, scrf_batch b, int latch[2], bool* used_lin) {
     // are committed and their all-reduce goes to the second stream, under the state contraction.  A NUMERIC failure of
     // the recursion is retried with the log-domain kernels by the caller: that has to be known BEFORE a collective is
     // issued (the peers issue theirs exactly once), so the host waits for the status here.
-    const bool ov = h->overlap_comm && h->comm_overlap_on && two_block_reduce(h) && !use2 && !h->timing;
+    const bool ov = h->overlap_comm && h->comm_overlap_on && two_block_reduce(h) && !use2 && !h->timing && !sparse(h);
     bool trans_done = false;   // the transition counts of this chunk are already in the staged gradient
     if (ov) {
       if (ci + 1 == n_chunks) {
@@ -2029,13 +2101,25 @@ static int fb_run(scrf_handle h, scrf_batch b, int latch[2], bool* used_lin) {
           KT_RUN("k_expf_mfma(samples)", cb.st, launch_expf_mfma(cb.st, cb.Z, 5 * l.L, b->d_frames[0] + b->frame_off[u0] * W0, W0, nullptr, nfr, l,
                            spec_samples(W0), cb.rpc_l, cb.nch_l, cb.slab_l));
         nl += 2;
+      } else if (sparse(h)) {
+        // inverted index of the chunk's windows, per-index sums of R, bias sums; then the transition counts of the
+        // next node's first window (the dense path's xrow_next) over Y - xi
+        PhaseTimer tk(h, PH_K_EXPF, cb.st);
+        KT_RUN("sparse state counts", cb.st, launch_sp_counts(cb.st, cb.X, l.F, nullptr, nseg, cb.R, l, 0, cb.spx[0], cb.grad));
+        tk.stop(1);
+        if (l.use_tf) {
+          launch_frame_rows(cb.st, bv, u0, u1, l.D, nfr, cb.xrow_next, 1);
+          KT_RUN("sparse transition counts", cb.st, launch_sp_counts(cb.st, cb.X, l.F, cb.xrow_next, nfr, cb.XI, l, 1, cb.spx[1], cb.grad));
+          nl += 2;
+        }
       } else {
         PhaseTimer tk(h, PH_K_EXPF, cb.st);
         if (fast) KT_RUN("k_expf_mfma(state)", cb.st, launch_expf_mfma(cb.st, cb.R, l.L, cb.X, l.F, nullptr, nseg, l, scrf_spec_state(l), cb.rpc_s, cb.nch_s, cb.slab_s, f32));
         else KT_RUN("k_expf_gemm(state)", cb.st, launch_expf_gemm(cb.st, cb.R, l.L, cb.X, l.F, nullptr, nseg, l, 0, cb.rpc_s, cb.nch_s, cb.slab_s));
         tk.stop(1);
       }
-      if (segtrans(h)) {
+      if (sparse(h)) {
+      } else if (segtrans(h)) {
         // transition counts of the segment's own window: XI2 rows are windows, no row map
         if (fast) KT_RUN("k_expf_mfma(trans)", cb.st, launch_expf_mfma(cb.st, cb.XI, l.L * l.L, cb.X, l.F, nullptr, nseg, l, scrf_spec_trans(l), cb.rpc_t, cb.nch_t, cb.slab_t, f32));
         else KT_RUN("k_expf_gemm(trans)", cb.st, launch_expf_gemm(cb.st, cb.XI, l.L * l.L, cb.X, l.F, nullptr, nseg, l, 1, cb.rpc_t, cb.nch_t, cb.slab_t));
@@ -2069,9 +2153,9 @@ static int fb_run(scrf_handle h, scrf_batch b, int latch[2], bool* used_lin) {
         launch_reduce_slabs(cb.st, cb.slab_s, cb.nch_s, l.L, l, spec_stats_x(l, W0), cb.grad);
         launch_reduce_slabs(cb.st, cb.slab_d, nblk_d, l.L, l, ScrfGemmSpec{0, 0, l.D, (uint32_t)l.use_sb, l.sbv, 8 * W0, 0}, cb.grad);
         launch_reduce_slabs(cb.st, cb.slab_l, cb.nch_l, 5 * l.L, l, spec_samples(W0), cb.grad);
-      } else launch_reduce_slabs(cb.st, cb.slab_s, cb.nch_s, l.L, l, scrf_spec_state(l), cb.grad);
+      } else if (!sparse(h)) launch_reduce_slabs(cb.st, cb.slab_s, cb.nch_s, l.L, l, scrf_spec_state(l), cb.grad);
       if (side) HIPCHK(h, hipStreamWaitEvent(cb.st, h->ev_join, 0));   // the side stream's weights are in
-      else if (trans_done) {}
+      else if (trans_done || (sparse(h) && l.use_tf)) {}
       else if (l.use_tf || segtrans(h)) launch_reduce_slabs(cb.st, cb.slab_t, cb.nch_t, l.L * l.L, l, scrf_spec_trans(l), cb.grad);
       else if (cb.wave) launch_atb(cb.st, l, cb.fA, cb.fB, nfr, cb.rpc_atb, cb.nch_atb, cb.slab_atb, h->d_m0, cb.grad,
                                    cb.lin ? cb.dl.gsd : nullptr);

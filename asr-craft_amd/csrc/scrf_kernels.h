@@ -226,4 +226,28 @@ void launch_ns_viterbi(hipStream_t st, const ScrfLayout& lay, ScrfBatchView bv, 
                        const double* TD, const double* TO, const double* TE, float* vc, uint16_t* bp, uint32_t* out_labels,
                        uint32_t* out_n, float* out_cost);
 
+// ---- sparse feature maps (scrf_sparse.hip): stdsparse / stdsparsetrans.  kind 0 = state (outputs = labels, rows = windows),
+// kind 1 = transitions (outputs = (p, c) pairs, rows = frames read through a row map)
+struct ScrfSparseIndex {
+  uint32_t* hist;     // [ntiles][nidx] per-tile counts, then their exclusive prefix over the tiles
+  uint32_t* tot;      // [nidx]
+  uint32_t* bstart;   // [nidx + 1] bucket starts
+  uint32_t* erow;     // [entries] row of each entry, buckets in (row, k) order
+  float* eval;        // [entries] value of each entry
+  uint32_t* sstart;   // [nidx + 1] first count segment of each bucket
+  double* slab;       // [2048][n_out] bias-count partial sums
+  double* part;       // [max_segs][n_out] per-segment partial counts
+  uint32_t ntiles, rpt;
+  uint32_t seg;       // entries per count segment
+  uint64_t max_segs;
+};
+void sparse_index_plan(uint64_t n_rows, uint32_t nidx, uint32_t* ntiles, uint32_t* rpt);
+size_t sparse_counts_bytes(uint64_t n_rows, uint32_t F, uint32_t nidx, uint32_t n_out);
+void sparse_counts_carve(void* base, uint64_t n_rows, uint32_t F, uint32_t nidx, uint32_t n_out, ScrfSparseIndex* ix);
+void launch_sp_relay(hipStream_t st, const double* lambda, const ScrfLayout& l, int kind, double* lamT);
+void launch_sp_scores(hipStream_t st, const float* X, uint32_t F, const uint64_t* xrow, uint64_t n_rows, const double* lamT,
+                      const ScrfLayout& l, int kind, double* out);
+void launch_sp_counts(hipStream_t st, const float* X, uint32_t F, const uint64_t* xrow, uint64_t n_rows, const double* R,
+                      const ScrfLayout& l, int kind, const ScrfSparseIndex& ix, double* grad);
+
 #endif  // SCRF_KERNELS_H_

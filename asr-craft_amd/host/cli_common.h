@@ -79,10 +79,16 @@ inline void refuse_unbuilt_flags(const Args& a, uint32_t D) {
 inline void set_fmap_config(const Args& a, CliModel* m) {
   CRF_FeatureMap_config& c = m->fmap;
   const std::string fm = a.str("crf_featuremap", "stdstate");
-  c.map_type = fm == "stdtrans" ? STDTRANS : STDSTATE;
-  if (fm != "stdstate" && fm != "stdtrans") { std::cerr << "crf_featuremap=" << fm << " is not built" << std::endl; exit(1); }
+  c.map_type = fm == "stdtrans" ? STDTRANS : fm == "stdsparse" ? STDSPARSE : fm == "stdsparsetrans" ? STDSPARSETRANS : STDSTATE;
+  if (fm != "stdstate" && fm != "stdtrans" && fm != "stdsparse" && fm != "stdsparsetrans") { std::cerr << "crf_featuremap=" << fm << " is not built" << std::endl; exit(1); }
   if (m->mtype == STDSEG_NO_DUR_NO_TRANSFTR && fm != "stdstate") {   // CRFTrain/src/Main.cpp:465-468, exit code of its catch block
     std::cerr << "Exception: main() in CRFTrain caught exception: crf_featuremap must be \"stdstate\" for \"stdseg_no_dur_no_transftr\" CRF model." << std::endl;
+    exit(-1);
+  }
+  const bool sparse = c.map_type == STDSPARSE || c.map_type == STDSPARSETRANS;
+  if (sparse && (m->mtype == STDSEG || m->mtype == STDSEG_NO_DUR || a.num("crf_states", 1) != 1)) {
+    std::cerr << "Exception: main() caught exception: crf_featuremap=" << fm << " is built for \"stdframe\" and "
+              << "\"stdseg_no_dur_no_segtransftr\" CRF models with crf_states=1" << std::endl;
     exit(-1);
   }
   c.numLabs = m->L;
@@ -92,7 +98,7 @@ inline void set_fmap_config(const Args& a, CliModel* m) {
   c.stateFidxStart = (QNUInt32)a.num("crf_stateftr_start", 0);
   long e = a.num("crf_stateftr_end", -1);
   c.stateFidxEnd = e >= 0 ? (QNUInt32)e : m->F - 1;
-  c.useTransFtrs = c.map_type == STDTRANS;
+  c.useTransFtrs = c.map_type == STDTRANS || c.map_type == STDSPARSETRANS;   // CRFTrain/src/Main.cpp:376-399
   c.transFidxStart = (QNUInt32)a.num("crf_transftr_start", 0);
   e = a.num("crf_transftr_end", -1);
   c.transFidxEnd = e >= 0 ? (QNUInt32)e : m->F - 1;

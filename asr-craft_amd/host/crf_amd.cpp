@@ -31,8 +31,9 @@ using std::string;
 CRF_FeatureMap::CRF_FeatureMap(CRF_FeatureMap_config* cnf) : config(cnf) { recalc(); }
 
 CRF_FeatureMap* CRF_FeatureMap::createFeatureMap(CRF_FeatureMap_config* cnf) {
+  if (cnf->map_type == STDSPARSE || cnf->map_type == STDSPARSETRANS) return new CRF_StdSparseFeatureMap(cnf);   // ftrmaps/CRF_FeatureMap.cpp:57-65
   if (cnf->map_type != STDSTATE && cnf->map_type != STDTRANS)
-    throw runtime_error("createFeatureMap: only the dense stdstate/stdtrans maps are built");
+    throw runtime_error("createFeatureMap: file-defined feature maps are not built");
   return new CRF_FeatureMap(cnf);
 }
 
@@ -104,7 +105,8 @@ scrf_config makeConfig(CRF_Model* crf, int device, uint32_t precision) {
   memset(&g, 0, sizeof(g));
   g.abi_version = SCRF_ABI_VERSION;
   g.model_type = (uint32_t)crf->getModelType();
-  g.map_type = c->map_type == STDTRANS ? SCRF_STDTRANS : SCRF_STDSTATE;
+  g.map_type = c->map_type == STDTRANS ? SCRF_STDTRANS : c->map_type == STDSPARSE ? SCRF_STDSPARSE
+              : c->map_type == STDSPARSETRANS ? SCRF_STDSPARSETRANS : SCRF_STDSTATE;
   g.num_labs = c->numLabs;
   g.num_feas = c->numFeas;
   g.num_states = c->numStates;

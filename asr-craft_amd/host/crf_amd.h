@@ -77,6 +77,12 @@ class CRF_FeatureMap {
   QNUInt32 numFtrFuncs = 0, numStateFuncs = 0, numTransFuncs = 0, numActualLabels = 0;
 };
 typedef CRF_FeatureMap CRF_StdFeatureMap;
+// stdsparse / stdsparsetrans (ftrmaps/CRF_StdSparseFeatureMap.cpp): the dense map's weight layout, windows read as
+// (index, value) pairs by the engine (scrf_abi.h, scrf_map_type); the index ranges are crf_stateftr_* / crf_transftr_*
+class CRF_StdSparseFeatureMap : public CRF_FeatureMap {
+ public:
+  explicit CRF_StdSparseFeatureMap(CRF_FeatureMap_config* cnf) : CRF_FeatureMap(cnf) {}
+};
 
 namespace crf_amd { class Engine; }
 

@@ -8,7 +8,7 @@ PKG_ROOT = os.path.dirname(os.path.dirname(HERE))  # asr-craft_amd/
 
 LAB_BAD = 0xFFFFFFFF
 STDFRAME, STDSEG, STDSEG_NO_DUR, STDSEG_NO_DUR_NO_TRANSFTR, STDSEG_NO_DUR_NO_SEGTRANSFTR = range(5)
-STDSTATE, STDTRANS = 0, 1
+STDSTATE, STDTRANS, STDSPARSE, STDSPARSETRANS = 0, 1, 2, 3
 PREC_EXACT, PREC_FAST, PREC_FAST32, PREC_FASTLIN = 0, 1, 2, 3
 ABI_VERSION = 1
 MAX_STREAMS = 3
@@ -79,13 +79,19 @@ def window_width(in_width, D, lctx=0, rctx=0, extract_seg=True):
 
 def make_config(model_type=STDSEG_NO_DUR_NO_SEGTRANSFTR, L=48, D=25, F=337, sfs=0, sfe=-1, use_trans_ftrs=False,
                 tfs=0, tfe=-1, use_state_ftrs=True, use_state_bias=True, use_trans_bias=True,
-                state_bias_val=1.0, trans_bias_val=1.0, device_id=0, precision=PREC_EXACT, scratch_bytes=0, num_states=1):
-    """Same meaning as CRFTrain's set_fmap_config (CRFTrain/src/Main.cpp:372-430)."""
+                state_bias_val=1.0, trans_bias_val=1.0, device_id=0, precision=PREC_EXACT, scratch_bytes=0, num_states=1,
+                map_type=None, sparse=False):
+    """Same meaning as CRFTrain's set_fmap_config (CRFTrain/src/Main.cpp:372-430).
+    map_type: STDSTATE / STDTRANS / STDSPARSE / STDSPARSETRANS; None = the dense map that use_trans_ftrs implies, or its
+    sparse twin with sparse=True.  A sparse map reads each window of F floats as (index, value) pairs; sfe / tfe bound
+    the index (default F - 1, as CRFTrain's crf_stateftr_end default) and the biases are unscaled."""
     if sfe is None or sfe < 0:
         sfe = F - 1
     if tfe is None or tfe < 0:
         tfe = F - 1
-    return Config(ABI_VERSION, model_type, STDTRANS if use_trans_ftrs else STDSTATE, L, F, num_states, D,
+    if map_type is None:
+        map_type = (STDSPARSETRANS if use_trans_ftrs else STDSPARSE) if sparse else (STDTRANS if use_trans_ftrs else STDSTATE)
+    return Config(ABI_VERSION, model_type, map_type, L, F, num_states, D,
                   int(use_state_ftrs), sfs, sfe, int(use_trans_ftrs), tfs, tfe, int(use_state_bias),
                   int(use_trans_bias), state_bias_val, trans_bias_val, device_id, precision, scratch_bytes)
 

@@ -61,8 +61,15 @@ enum scrf_model_type {
   SCRF_STDSEG_NO_DUR_NO_SEGTRANSFTR = 4  /* the TIMIT-demo model */
 };
 
-/* ftrmaptype, CRF.h:40 (dense maps only) */
-enum scrf_map_type { SCRF_STDSTATE = 0, SCRF_STDTRANS = 1 };
+/* ftrmaptype, CRF.h:40.  The sparse maps (ftrmaps/CRF_StdSparseFeatureMap.cpp) read a window of num_feas floats as
+ * (index, value) pairs (x[2k], x[2k+1]): a pair whose index lies in [fidx_start, fidx_end] adds value * lambda[block +
+ * index]; the state / transition bias is added unscaled (state_bias_val / trans_bias_val are not applied).  The
+ * fidx ranges bound the INDEX, not a window column; the weight layout is the dense map's.  Defined here where the
+ * reference is not: num_feas must be even, fidx_start must be 0 (the reference does not subtract it), and an index
+ * float that is negative, NaN or >= 2^32 is skipped as out of range.  Sparse maps are taken by SCRF_STDFRAME and
+ * SCRF_STDSEG_NO_DUR_NO_SEGTRANSFTR with num_states == 1; SCRF_STDSPARSETRANS is the front-ends'
+ * name for a sparse map with use_trans_ftrs set. */
+enum scrf_map_type { SCRF_STDSTATE = 0, SCRF_STDTRANS = 1, SCRF_STDSPARSE = 2, SCRF_STDSPARSETRANS = 3 };
 
 /* Arithmetic policy of the score / expected-count contractions.
  *  EXACT : fp64, ascending feature order, unfused multiply-then-add == the reference's
