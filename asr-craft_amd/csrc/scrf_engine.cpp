@@ -148,6 +148,8 @@ struct scrf_engine_s {
   double* d_sl_tab = nullptr;   // STDSEG, bias-only transitions: E, E^T (nLabs^2 each) and max M (scrf_stdseg_lin.hip)
   bool frame_mass = false;   // posterior-mass self-checks with the frame model's bounds (scrf_set_frame_mass_check)
   bool lin_dp = true;
+  bool post_split = true;    // SCRF_POSTOCC_SPLIT=0: k_post_occ walks every utterance in one piece (same results)
+  uint64_t n_post_split = 0, n_post_whole = 0;   // k_post_occ launches in frame segments / in one piece (scrf_posterior_stats)
   // the workgroup-per-utterance log-domain recursion (k_fb: column-wise max-shifted log-sum-exp, the
   // reference's LogMath) instead of the wavefront kernels, whose transition step works on exp(M - max M):
   // set for the automatic redo of a batch / hook call that raised SCRF_ERR_NUMERIC there
@@ -165,6 +167,9 @@ struct scrf_engine_s {
   uint32_t *dec_lab = nullptr, *dec_n = nullptr, *dec_hlab = nullptr, *dec_hn = nullptr;
   float *dec_cost = nullptr, *dec_hcost = nullptr;
   uint64_t dec_cap_f = 0, dec_cap_u = 0;
+  // result arrays of scrf_posteriors_batch (whole batch: chunking stays invisible), kept across calls like the decode buffers
+  char* post_buf = nullptr;
+  size_t post_cap = 0;
   std::string err;
   // per-kernel HIP-event times of the last timed call (scrf_kernel_timing)
   struct KTime { std::string name; double ms; uint32_t n; };
@@ -356,6 +361,7 @@ extern "C" int scrf_create(const scrf_config* cfg, scrf_handle* out) {
   if (const char* e = getenv("SCRF_FUSE_MIXED")) h->fuse_mixed = atoi(e) != 0;
   if (const char* e = getenv("SCRF_COMM_OVERLAP")) h->comm_overlap_on = atoi(e) != 0;
   if (const char* e = getenv("SCRF_LINDP")) h->lin_dp = atoi(e) != 0;
+  if (const char* e = getenv("SCRF_POSTOCC_SPLIT")) h->post_split = atoi(e) != 0;
   if (const char* e = getenv("SCRF_FAST_DECODE")) h->fast_decode = atoi(e) != 0;
   if (const char* e = getenv("SCRF_BATCH_POOL")) { h->pool_on = atoi(e) != 0; h->pool_up = atoi(e) != 2; }
   if (const char* e = getenv("SCRF_HYBRID")) { h->hybrid = atoi(e) != 0; h->hybrid_first = atoi(e) == 2; }
@@ -451,6 +457,7 @@ extern "C" int scrf_destroy(scrf_handle h) {
   if (h->ev_fork) hipEventDestroy(h->ev_fork);
   if (h->ev_join) hipEventDestroy(h->ev_join);
   hipFree(h->dec_lab); hipFree(h->dec_n); hipFree(h->dec_cost);
+  hipFree(h->post_buf);
   if (h->dec_hlab) hipHostFree(h->dec_hlab);
   if (h->dec_hn) hipHostFree(h->dec_hn);
   if (h->dec_hcost) hipHostFree(h->dec_hcost);
@@ -1049,6 +1056,7 @@ struct ChunkBufs {
   double* fB = nullptr;
   double* numer_f = nullptr; // [nfr]
   double* mass_s = nullptr;  // [nfr] state posterior mass per node (reference self-check, computeExpF :917-947)
+  double* mass_part = nullptr;  // [groups][nfr] its partial sums per 64 outputs (posterior output, L > 64)
   // scaled linear-domain recursion (training path of the wavefront DP)
   bool lin = false;
   bool es_ready = false;     // cb.S already holds exp(S - smax) (written by the fused score kernel)
@@ -1074,7 +1082,11 @@ struct ChunkBufs {
   bool lamT_ready = false;   // sparse maps: h->d_lamT already re-laid for this call (scrf_fb_batch: once, before the lanes fork)
 };
 
-struct Need { bool fb, post, beta, vit; bool fused = false; bool vitfast = false; bool la = false; bool hybrid = false; };
+// ponly (scrf_posteriors_batch): the recursion of the training path without anything that needs labels or feeds the
+// gradient -- the linear-domain vectors (or alpha_dur / beta) and the per-frame state mass, no count buffers
+struct Need { bool fb, post, beta, vit; bool fused = false; bool vitfast = false; bool la = false; bool hybrid = false; bool ponly = false; bool plog = false; };
+// plog: ponly through the log-domain recursion (SCRF_PREC_EXACT)
+static bool need_lin(const Need& nd) { return nd.post || (nd.ponly && !nd.plog); }
 
 // entries the decode screen may list per chunk before the chunk falls back to the EXACT path
 static uint32_t decode_fix_cap(uint64_t nseg, uint32_t L) {
@@ -1131,8 +1143,8 @@ static size_t chunk_bytes(scrf_handle h, scrf_batch b, uint64_t nutt, uint64_t n
   if (segtrans(h)) tot += pad256(nseg * LL * sizeof(double));               // M2: one matrix per window
   else if (l.use_tf) tot += pad256(nfr * LL * sizeof(double)) + pad256(nfr * 8);  // M, xrow_cur
   if (nd.fb) {
-    const bool wave = wave_path(h, nd.post);
-    if (wave && nd.post && h->lin_dp) {
+    const bool wave = wave_path(h, need_lin(nd));
+    if (wave && need_lin(nd) && h->lin_dp) {
       // scaled linear-domain recursion: no alpha-with-duration array
       tot += pad256(nseg * sizeof(double)) + pad256(nfr * sizeof(double));               // smax, s_true
       tot += 4 * pad256(nfr * l.L * sizeof(double)) + 4 * pad256(nfr * sizeof(double));  // a, p, b, sd + log-scales
@@ -1150,6 +1162,7 @@ static size_t chunk_bytes(scrf_handle h, scrf_batch b, uint64_t nutt, uint64_t n
         if (!l.use_tf) tot += pad256(((nfr + atb_rows_per_chunk(nfr) - 1) / atb_rows_per_chunk(nfr)) * LL * sizeof(double));
       }
     }
+    if (nd.ponly) tot += (1 + (size_t)(post_occ_groups(l) > 1 ? post_occ_groups(l) : 0)) * pad256(nfr * sizeof(double));   // mass_s + its per-group parts
     if (nd.post) {
       tot += pad256(nfr * sizeof(double));                            // mass_s
       if (segtrans(h)) {
@@ -1248,8 +1261,8 @@ static int carve(scrf_handle h, scrf_batch b, uint32_t u0, uint32_t u1, const Ne
     cb->m_per_frame = 0;
   }
   if (nd.fb) {
-    cb->wave = wave_path(h, nd.post);
-    cb->lin = cb->wave && nd.post && h->lin_dp;
+    cb->wave = wave_path(h, need_lin(nd));
+    cb->lin = cb->wave && need_lin(nd) && h->lin_dp;
     if (cb->lin) {
       cb->smax = a.take<double>(nseg);
       cb->s_true = a.take<double>(nfr);
@@ -1287,6 +1300,10 @@ static int carve(scrf_handle h, scrf_batch b, uint32_t u0, uint32_t u1, const Ne
           cb->slab_atb = a.take<double>((size_t)cb->nch_atb * LL);
         }
       }
+    }
+    if (nd.ponly) {
+      cb->mass_s = a.take<double>(nfr);
+      if (post_occ_groups(l) > 1) cb->mass_part = a.take<double>(nfr * post_occ_groups(l));
     }
     if (nd.post) {
       cb->mass_s = a.take<double>(nfr);
@@ -1536,7 +1553,7 @@ static int run_scores(scrf_handle h, scrf_batch b, uint32_t u0, uint32_t u1, Chu
 // forward + backward (+ posteriors when `post`): wavefront-per-utterance kernels for L <= 64,
 // the workgroup-per-utterance kernel otherwise.  Leaves R = Y - gamma in cb.AD (post) or
 // alpha-with-duration (no post), alpha in cb.alpha, beta in cb.beta (wave path or nd.beta).
-static int run_dp(scrf_handle h, scrf_batch b, uint32_t u0, uint32_t u1, ChunkBufs& cb, bool post, uint32_t* nl_out) {
+static int run_dp(scrf_handle h, scrf_batch b, uint32_t u0, uint32_t u1, ChunkBufs& cb, bool post, uint32_t* nl_out, bool ponly = false) {
   const ScrfLayout& l = h->lay;
   const uint64_t nutt = u1 - u0, nfr = b->frame_off[u1] - b->frame_off[u0];
   // (only the posterior-mass self-checks look at it in the recursion kernels)
@@ -1563,15 +1580,20 @@ static int run_dp(scrf_handle h, scrf_batch b, uint32_t u0, uint32_t u1, ChunkBu
     if (cb.lin) {
       const uint64_t nseg = b->seg_off[u1] - b->seg_off[u0];
       if (!cb.es_ready) {
-        KT_RUN("k_true_scores", cb.st, launch_true_scores(cb.st, l, bv, b->d_frame_u, u0, nfr, cb.S, cb.s_true));
+        if (!ponly) KT_RUN("k_true_scores", cb.st, launch_true_scores(cb.st, l, bv, b->d_frame_u, u0, nfr, cb.S, cb.s_true));
         KT_RUN("k_exp_rows", cb.st, launch_exp_rows(cb.st, cb.S, nseg, l.L, cb.smax));
-        nl += 2;
+        nl += ponly ? 1 : 2;
       }
       {
         PhaseTimer tk(h, PH_K_DP, cb.st);
         KT_RUN(l.L > 64 ? "k_dp_lin_mw" : "k_dp_lin", cb.st, launch_dp_lin(cb.st, l, bv, u0, (uint32_t)nutt, cb.S, cb.smax, cb.E, cb.ET, cb.msh, cb.m_per_frame, cb.dl,
                       b->d_zx, b->d_status));
         tk.stop(1);
+      }
+      if (ponly) {   // the caller's posterior-output kernels take it from here
+        if (nl_out) *nl_out = nl + 1;
+        HIPCHK(h, hipGetLastError());
+        return SCRF_OK;
       }
       if (cb.fused) {
         // posterior pass and the per-frame sums of R in one walk (R is not read back for Z)
@@ -2225,6 +2247,190 @@ extern "C" int scrf_fb_batch(scrf_handle h, scrf_batch b, double* numer, double*
   return SCRF_OK;
 }
 
+
+// ---------------------------------------------------------------------------------------------
+// posterior output: frame, boundary and segment posteriors of a label-less batch
+// ---------------------------------------------------------------------------------------------
+static const char* model_type_name(uint32_t mt) {
+  return mt == SCRF_STDFRAME ? "stdframe" : mt == SCRF_STDSEG ? "stdseg" : mt == SCRF_STDSEG_NO_DUR ? "stdseg_no_dur"
+         : mt == SCRF_STDSEG_NO_DUR_NO_TRANSFTR ? "stdseg_no_dur_no_transftr" : "stdseg_no_dur_no_segtransftr";
+}
+// the models the posterior pass serves: one transition matrix per frame (or one in all), one state per label
+static int post_model_ok(scrf_handle h, const char* fn) {
+  if (h->cfg.model_type == SCRF_STDSEG || h->cfg.model_type == SCRF_STDSEG_NO_DUR)
+    return fail(h, SCRF_ERR_INVALID, "%s: posterior output is not built for the \"%s\" CRF model; use \"stdframe\", "
+                "\"stdseg_no_dur_no_transftr\" or \"stdseg_no_dur_no_segtransftr\"", fn, model_type_name(h->cfg.model_type));
+  if (h->cfg.num_states > 1)
+    return fail(h, SCRF_ERR_INVALID, "%s: posterior output is built for crf_states = 1 only (this \"%s\" model has crf_states = %u)",
+                fn, model_type_name(h->cfg.model_type), h->cfg.num_states);
+  return SCRF_OK;
+}
+
+struct PostOut {
+  double* occ = nullptr;    // [sum T][L]
+  double* end = nullptr;    // [sum T]
+  double* seg = nullptr;    // [n queries]
+  const uint32_t *q_u = nullptr, *q_e = nullptr, *q_lab = nullptr;
+  const uint64_t* lab_off = nullptr;   // host
+};
+
+// scores, the recursion of the handle's precision and the posterior-output kernels, chunk by chunk on the engine stream.
+// Nothing that needs labels or feeds the gradient runs: no true scores, numerator, xi, R, counts, staging or commit.
+static int post_run(scrf_handle h, scrf_batch b, const PostOut& po, int latch[2]) {
+  const ScrfLayout& l = h->lay;
+  HIPCHK(h, hipMemsetAsync(b->d_status, 0, sizeof(int) * b->U, h->stream));
+  hipLaunchKernelGGL(k_latch_reset, dim3(1), dim3(1), 0, h->stream, h->d_latch);
+  const bool fast = h->cfg.train_precision >= SCRF_PREC_FAST;
+  const int f32 = h->cfg.train_precision == SCRF_PREC_FAST32;
+  const int frame_model = h->cfg.model_type == SCRF_STDFRAME || h->frame_mass;
+  Need nd{true, false, true, false};
+  nd.ponly = true;
+  nd.plog = !fast;   // SCRF_PREC_EXACT: the log-domain recursion and k_post_occ_log
+  // the batch forms of scrf_fb_batch (scrf_batch_is_fused)
+  nd.fused = fast && b->fused_ok && h->fuse_windows;
+  nd.hybrid = fast && !nd.fused && b->hybrid_ok && h->hybrid && h->fuse_windows && h->lin_dp && !h->force_fb && wave_path(h, true) && !f32;
+  nd.la = nd.fused && h->cfg.train_precision == SCRF_PREC_FASTLIN && h->lin_dp && !h->force_fb && wave_path(h, true) &&
+          fused_la_supported(l, b->recipe[0].in_width);
+  ScrfBatchView bv = b->view();
+  if (!h->m0_valid && !l.use_tf) {
+    launch_scores_exact(h->stream, nullptr, l.F, nullptr, 1, h->d_lambda, l, 1, l.L * l.L, h->d_m0);
+    launch_exp_m(h->stream, h->d_m0, l.L, 1, h->d_e0, h->d_et0, h->d_msh0);
+    h->m0_valid = true;
+  }
+  if (sparse(h)) {
+    launch_sp_relay(h->stream, h->d_lambda, l, 0, h->d_lamT[0]);
+    if (l.use_tf) launch_sp_relay(h->stream, h->d_lambda, l, 1, h->d_lamT[1]);
+  }
+  for (uint32_t u0 = 0; u0 < b->U;) {
+    const uint32_t u1 = plan_chunk(h, b, u0, nd);
+    ChunkBufs cb;
+    int rc = carve(h, b, u0, u1, nd, &cb, 0);
+    if (rc != SCRF_OK) return rc;
+    cb.lamT_ready = sparse(h);
+    const uint64_t nutt = u1 - u0, nfr = b->frame_off[u1] - b->frame_off[u0];
+    rc = run_scores(h, b, u0, u1, cb, fast, f32);
+    if (rc != SCRF_OK) return rc;
+    PhaseTimer tm(h, PH_FB, cb.st);
+    uint32_t nl = 0;
+    rc = run_dp(h, b, u0, u1, cb, false, &nl, true);
+    if (rc != SCRF_OK) return rc;
+    double* occ = po.occ ? po.occ + b->frame_off[u0] * l.L : nullptr;
+    if (cb.lin) {
+      uint32_t t_max = 0;   // the longest utterance of the chunk: a launch of few utterances splits each into frame segments
+      for (uint64_t u = u0; u < u1; u++) t_max = std::max(t_max, b->T[u]);
+      uint32_t nz = 1;
+      KT_RUN("k_post_occ", cb.st, nz = launch_post_occ(cb.st, l, bv, u0, (uint32_t)nutt, t_max, nfr, cb.S, cb.smax, cb.dl, b->d_zx, b->d_status, occ,
+                      cb.mass_part, cb.mass_s, h->post_split ? 1 : 0));
+      if (nz > 1) h->n_post_split++; else h->n_post_whole++;
+      if (post_occ_groups(l) > 1) nl++;   // k_sum_groups
+      KT_RUN("k_mass_check", cb.st, launch_mass_check(cb.st, bv, b->d_frame_u, u0, nfr, l.L, frame_model, 1, cb.dl.a, cb.dl.ga, cb.dl.b, cb.dl.gb,
+                        b->d_zx, cb.mass_s, b->d_status));
+    } else {
+      KT_RUN("k_post_occ_log", cb.st, launch_post_occ_log(cb.st, l, bv, b->d_frame_u, u0, nfr, cb.AD, cb.beta, b->d_zx, b->d_status, occ, cb.mass_s));
+      KT_RUN("k_mass_check", cb.st, launch_mass_check(cb.st, bv, b->d_frame_u, u0, nfr, l.L, frame_model, 0, cb.alpha, nullptr, cb.beta, nullptr,
+                        b->d_zx, cb.mass_s, b->d_status));
+    }
+    nl += 2;
+    if (po.end) HIPCHK(h, hipMemcpyAsync(po.end + b->frame_off[u0], cb.mass_s, sizeof(double) * nfr, hipMemcpyDeviceToDevice, cb.st));
+    if (po.seg) {
+      const uint64_t q0 = po.lab_off[u0], nq = po.lab_off[u1] - q0;
+      KT_RUN("k_seg_post", cb.st, launch_seg_post(cb.st, l, bv, u0, po.q_u, po.q_e, po.q_lab, q0, nq, cb.lin ? 1 : 0, cb.lin ? cb.S : cb.AD, cb.smax,
+                      cb.dl, cb.beta, b->d_zx, po.seg));
+      nl++;
+    }
+    tm.stop(nl);
+    HIPCHK(h, hipGetLastError());
+    u0 = u1;
+  }
+  int rc = queue_status(h, b);
+  if (rc != SCRF_OK) return rc;
+  HIPCHK(h, hipEventSynchronize(h->ev_status));
+  latch_decode(h->h_latch, latch);
+  return SCRF_OK;
+}
+
+extern "C" int scrf_posteriors_batch(scrf_handle h, scrf_batch b, double* zx, double* frame_post, double* end_post,
+                                     const uint32_t* seg_labels, const uint64_t* lab_off, double* seg_post) {
+  if (!h || !b) return SCRF_ERR_INVALID;
+  int rc = post_model_ok(h, "scrf_posteriors_batch");
+  if (rc != SCRF_OK) return rc;
+  HIPCHK(h, hipSetDevice(h->device));
+  const ScrfLayout& l = h->lay;
+  const uint64_t nF = b->frame_off[b->U];
+  // the queries: the segments of a path, back to back per utterance, label value l + L (d - 1)
+  std::vector<uint32_t> q;   // [3][nq]: utterance, end frame, label value
+  uint64_t nq = 0;
+  if (seg_post) {
+    if (!seg_labels || !lab_off) return fail(h, SCRF_ERR_INVALID, "scrf_posteriors_batch: seg_post needs seg_labels and lab_off");
+    nq = lab_off[b->U];
+    if (lab_off[0] != 0 || nq > nF) return fail(h, SCRF_ERR_INVALID, "scrf_posteriors_batch: lab_off does not describe back-to-back segments of this batch");
+    q.resize(3 * (size_t)nq + 1);
+    for (uint32_t u = 0; u < b->U; u++) {
+      if (lab_off[u + 1] < lab_off[u] || lab_off[u + 1] > nq) return fail(h, SCRF_ERR_INVALID, "scrf_posteriors_batch: lab_off is not ascending at utterance %u", u);
+      uint64_t e = 0;   // frames consumed so far
+      for (uint64_t i = lab_off[u]; i < lab_off[u + 1]; i++) {
+        const uint32_t v = seg_labels[i];
+        if (v >= l.L * l.D) return fail(h, SCRF_ERR_INVALID, "scrf_posteriors_batch: utterance %u, segment %llu: label %u is out of range (labels x maximum duration = %u)",
+                                        u, (unsigned long long)(i - lab_off[u]), v, l.L * l.D);
+        e += v / l.L + 1;
+        if (e > b->T[u]) return fail(h, SCRF_ERR_INVALID, "scrf_posteriors_batch: utterance %u, segment %llu ends at frame %llu, past the utterance's %u frames",
+                                     u, (unsigned long long)(i - lab_off[u]), (unsigned long long)(e - 1), b->T[u]);
+        q[i] = u; q[nq + i] = (uint32_t)(e - 1); q[2 * nq + i] = v;
+      }
+    }
+  }
+  const size_t by_occ = frame_post ? pad256(sizeof(double) * nF * l.L) : 0, by_end = end_post ? pad256(sizeof(double) * nF) : 0;
+  const size_t by_seg = pad256(sizeof(double) * nq), by_q = pad256(sizeof(uint32_t) * 3 * nq);
+  const size_t need = by_occ + by_end + by_seg + by_q + 256;
+  if (need > h->post_cap) {   // grown on demand, kept until scrf_destroy (scrf_abi.h)
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    hipFree(h->post_buf); h->post_buf = nullptr; h->post_cap = 0;
+    HIPCHK(h, hipMalloc((void**)&h->post_buf, need));
+    h->post_cap = need;
+  }
+  PostOut po;
+  char* pb = h->post_buf;
+  if (frame_post) po.occ = (double*)pb;
+  pb += by_occ;
+  if (end_post) po.end = (double*)pb;
+  pb += by_end;
+  if (seg_post && nq) {
+    po.seg = (double*)pb;
+    uint32_t* dq = (uint32_t*)(pb + by_seg);
+    HIPCHK(h, hipMemcpyAsync(dq, q.data(), sizeof(uint32_t) * 3 * nq, hipMemcpyHostToDevice, h->stream));
+    po.q_u = dq; po.q_e = dq + nq; po.q_lab = dq + 2 * nq;
+    po.lab_off = lab_off;
+  }
+  if (h->timing) {
+    memset(h->ms, 0, sizeof(h->ms)); memset(h->nlaunch, 0, sizeof(h->nlaunch)); h->ktimes.clear();
+    hipEventRecord(h->ev[SCRF_N_PHASES][0], h->stream);
+  }
+  int latch[2] = {0, 0};
+  rc = post_run(h, b, po, latch);
+  if (rc != SCRF_OK) return rc;
+  if (latch[0] == SCRF_ERR_NUMERIC && wave_path(h, true)) {
+    // as scrf_fb_batch: a wavefront recursion that gave up (or a failed mass check) is redone with the workgroup kernel,
+    // the reference's LogMath, and k_post_occ_log; every output of the first pass is overwritten
+    h->n_lin_fallback++;
+    h->force_fb = true;
+    rc = post_run(h, b, po, latch);
+    h->force_fb = false;
+    if (rc != SCRF_OK) return rc;
+  }
+  if (h->timing) {
+    hipEventRecord(h->ev[SCRF_N_PHASES][1], h->stream);
+    hipEventSynchronize(h->ev[SCRF_N_PHASES][1]);
+    hipEventElapsedTime(&h->ms[PH_ALL], h->ev[SCRF_N_PHASES][0], h->ev[SCRF_N_PHASES][1]);
+  }
+  if (latch[0] != 0) return fail(h, latch[0], "utterance %d: %s", latch[1], status_text(latch[0]));
+  if (zx) HIPCHK(h, hipMemcpyAsync(zx, b->d_zx, sizeof(double) * b->U, hipMemcpyDeviceToHost, h->stream));
+  if (frame_post) HIPCHK(h, hipMemcpyAsync(frame_post, po.occ, sizeof(double) * nF * l.L, hipMemcpyDeviceToHost, h->stream));
+  if (end_post) HIPCHK(h, hipMemcpyAsync(end_post, po.end, sizeof(double) * nF, hipMemcpyDeviceToHost, h->stream));
+  if (po.seg) HIPCHK(h, hipMemcpyAsync(seg_post, po.seg, sizeof(double) * nq, hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  return SCRF_OK;
+}
+
 extern "C" int scrf_add_grad(scrf_handle h, const double* g, uint32_t n) {
   if (!h || !g) return SCRF_ERR_INVALID;
   if (n != h->xlay.lambda_len) return fail(h, SCRF_ERR_INVALID, "scrf_add_grad: length mismatch");
@@ -2393,6 +2599,39 @@ extern "C" int scrf_forward_backward(scrf_handle h, scrf_batch b, uint32_t u, ui
   }
   return SCRF_OK;
 }
+
+extern "C" int scrf_seg_posteriors(scrf_handle h, scrf_batch b, uint32_t u, double* gamma) {
+  int rc = check_u(h, b, u, "scrf_seg_posteriors");
+  if (rc != SCRF_OK) return rc;
+  if (!gamma) return SCRF_ERR_INVALID;
+  rc = post_model_ok(h, "scrf_seg_posteriors");
+  if (rc != SCRF_OK) return rc;
+  HIPCHK(h, hipSetDevice(h->device));
+  const ScrfLayout& l = h->lay;
+  Need nd{true, false, true, false};
+  const uint64_t nseg = b->seg_off[u + 1] - b->seg_off[u];
+  // second attempt: the workgroup kernel (reference LogMath) when the wavefront recursion gave up
+  for (int attempt = 0; attempt < 2; attempt++) {
+    ChunkBufs cb;
+    rc = carve(h, b, u, u + 1, nd, &cb);
+    if (rc == SCRF_OK) rc = run_scores(h, b, u, u + 1, cb);
+    if (rc == SCRF_OK && hipMemsetAsync(b->d_status, 0, sizeof(int) * b->U, h->stream) != hipSuccess) rc = fail(h, SCRF_ERR_HIP, "scrf_seg_posteriors: memset failed");
+    if (rc == SCRF_OK) rc = run_dp(h, b, u, u + 1, cb, false, nullptr);
+    int st = 0;
+    if (rc == SCRF_OK && hipMemcpyAsync(&st, b->d_status + u, sizeof(int), hipMemcpyDeviceToHost, h->stream) != hipSuccess) rc = fail(h, SCRF_ERR_HIP, "scrf_seg_posteriors: status copy failed");
+    if (rc == SCRF_OK && hipStreamSynchronize(h->stream) != hipSuccess) rc = fail(h, SCRF_ERR_HIP, "scrf_seg_posteriors: synchronize failed");
+    if (rc != SCRF_OK) { h->force_fb = false; return rc; }
+    if (st == SCRF_ERR_NUMERIC && !h->force_fb && wave_path(h, false)) { h->force_fb = true; continue; }
+    h->force_fb = false;
+    if (st != SCRF_OK && st != SCRF_ERR_BAD_LABEL) return fail(h, st, "utterance %u: numeric failure in forward-backward", u);
+    launch_gamma_log(h->stream, l, b->T[u], cb.AD, cb.beta, b->d_zx + u, cb.AD);
+    HIPCHK(h, hipMemcpyAsync(gamma, cb.AD, sizeof(double) * nseg * l.L, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    break;
+  }
+  return SCRF_OK;
+}
+
 
 // ---------------------------------------------------------------------------------------------
 // decode
@@ -2976,6 +3215,12 @@ extern "C" int scrf_kernel_timing(scrf_handle h, char* buf, size_t cap) {
 extern "C" int scrf_train_stats(scrf_handle h, uint64_t* n_lin_fallback) {
   if (!h) return SCRF_ERR_INVALID;
   if (n_lin_fallback) *n_lin_fallback = h->n_lin_fallback;
+  return SCRF_OK;
+}
+extern "C" int scrf_posterior_stats(scrf_handle h, uint64_t* n_split, uint64_t* n_whole) {
+  if (!h) return SCRF_ERR_INVALID;
+  if (n_split) *n_split = h->n_post_split;
+  if (n_whole) *n_whole = h->n_post_whole;
   return SCRF_OK;
 }
 extern "C" int scrf_enable_timing(scrf_handle h, int on) { if (!h) return SCRF_ERR_INVALID; h->timing = on != 0; return SCRF_OK; }

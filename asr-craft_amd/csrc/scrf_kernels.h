@@ -112,6 +112,27 @@ void launch_xi_scale(hipStream_t st, ScrfBatchView bv, const uint32_t* frame_u, 
                      const ScrfDpLin& o, const double* zx);
 void launch_lin_to_log(hipStream_t st, uint64_t n_frames, uint32_t L, const double* m, const double* g, double* out);
 
+// scrf_post.hip: posterior output (scrf_posteriors_batch): frame posteriors occ [frames][L] (nullptr: not formed) and the
+// per-frame state mass mass_s [frames] (= the boundary posterior) from the linear-domain vectors / the log-domain arrays;
+// mass_part [post_occ_groups][frames] holds the per-group partial masses when L > 64 (not used with one group).
+// launch_post_occ returns the number of frame segments every utterance's walk was split into (1: one piece); split_ok = 0
+// keeps every walk in one piece
+uint32_t post_occ_groups(const ScrfLayout& lay);
+uint32_t launch_post_occ(hipStream_t st, const ScrfLayout& lay, ScrfBatchView bv, uint32_t u0, uint32_t n_utts, uint32_t t_max,
+                         uint64_t n_frames, const double* ES, const double* smax, const ScrfDpLin& o, const double* zx,
+                         int* status, double* occ, double* mass_part, double* mass_s, int split_ok);
+void launch_post_occ_log(hipStream_t st, const ScrfLayout& lay, ScrfBatchView bv, const uint32_t* frame_u, uint32_t u0,
+                         uint64_t n_frames, const double* AD, const double* beta, const double* zx, int* status,
+                         double* occ, double* mass_s);
+// gamma of the queries q0 .. q0 + nq - 1 (utterance, end frame, label + L * (duration - 1)); SA = exp(S - smax) (lin) or
+// alpha_dur
+void launch_seg_post(hipStream_t st, const ScrfLayout& lay, ScrfBatchView bv, uint32_t u0, const uint32_t* q_u,
+                     const uint32_t* q_e, const uint32_t* q_lab, uint64_t q0, uint64_t nq, int lin, const double* SA,
+                     const double* smax, const ScrfDpLin& o, const double* beta, const double* zx, double* out);
+// gamma [N_seg][L] = exp(alpha_dur + beta - Zx) of one utterance (zx points at its log-partition); may run in place over AD
+void launch_gamma_log(hipStream_t st, const ScrfLayout& lay, uint32_t T, const double* AD, const double* beta, const double* zx,
+                      double* gamma);
+
 // scrf_fused.hip: state contractions with the window synthesis fused in (X never materialised)
 #define SCRF_FUSED_ROWS_SCORES 256
 uint32_t fused_scores_tb(uint32_t W, uint32_t D);   // whole frames per score tile (0: shape not supported)

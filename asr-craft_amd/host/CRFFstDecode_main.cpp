@@ -16,7 +16,21 @@
 // (:935-940).  With a phone FST or a pruning weight the chain is materialised left to right as the reference does it
 // (a Prune does not commute with the compositions behind it); otherwise everything right of the lattice is one machine.
 // crf_pre_phn_wt, crf_lm_wt and crf_lm_arpa are declared by the reference (:118-128) and read by nothing there: accepted, no effect.
+// Two extensions of the reference's flag set (posterior output):
+//   crf_decode_mode=posteriors with crf_output_posteriorfile=PATH: no decoding; the per-frame label posteriors of every
+//   utterance (what CRF_NewLocalPosteriorBuilder::buildFtrSeq yields, for segmental models the summed posterior of the
+//   segments covering the frame), one row of L values per frame, device batches of crf_bunch_size utterances, under
+//   crf_precision (default fast).  crf_output_posterior_format=ascii (default; lines `sent frame p_0 .. p_{L-1}`, 17
+//   significant digits) | pfile (float32 features, no labels).  crf_posterior_log=1 writes logs; crf_posterior_norm=0
+//   (with crf_posterior_log=1 only: the exponential of a log-partition of hundreds of nats is not a number a file can hold)
+//   the unnormalised form, log posterior + Zx.  Refused together with an LM, a dictionary, a phone FST,
+//   crf_align_mlffile, crf_output_mlffile or crf_lat_outdir.
+//   crf_output_conffile=PATH, on the best-paths-only branch (no crf_lat_outdir, no MLF, not align): beside the label
+//   file, `sent seg first_frame last_frame label posterior` per segment of the best path (label = phone, posterior = the
+//   segment's posterior gamma).  The label file itself does not change.
 #include "cli_common.h"
+
+#include <math.h>
 
 #include <limits>
 #include <set>
@@ -42,8 +56,25 @@ int main(int argc, char** argv) {
   // crf_decode_mode=align (Main.cpp:464-471, :841-848): the best path of lattice o label acceptor -- the labels of
   // hardtarget_file in their order, every run of equal node labels stretched or shrunk to fit -- written to the label file
   const std::string mode = a.str("crf_decode_mode", "decode");
-  if (mode != "decode" && mode != "align") { std::cerr << "crf_decode_mode=" << mode << " (decode|align)" << std::endl; return 1; }
-  const bool align_mode = mode == "align";
+  if (mode != "decode" && mode != "align" && mode != "posteriors") { std::cerr << "crf_decode_mode=" << mode << " (decode|align|posteriors)" << std::endl; return 1; }
+  const bool align_mode = mode == "align", post_mode = mode == "posteriors";
+  if (post_mode) {
+    for (const char* k : {"crf_lm_txt", "crf_lm_bin", "crf_dict_txt", "crf_dict_bin", "crf_phn_txt", "crf_phn_bin", "crf_align_mlffile", "crf_output_mlffile", "crf_lat_outdir"})
+      if (a.has(k)) { std::cerr << "crf_decode_mode=posteriors writes frame posteriors only: " << k << " makes no sense with it" << std::endl; return 1; }
+    if (!a.has("crf_output_posteriorfile")) { std::cerr << "crf_output_posteriorfile required when crf_decode_mode=posteriors" << std::endl; return 1; }
+    if (a.num("crf_posterior_norm", 1) == 0 && a.num("crf_posterior_log", 0) == 0) {
+      std::cerr << "crf_posterior_norm=0 needs crf_posterior_log=1: the unnormalised posterior exp(log p + Zx) overflows for any real utterance" << std::endl;
+      return 1;
+    }
+  } else if (a.has("crf_output_posteriorfile")) { std::cerr << "crf_output_posteriorfile needs crf_decode_mode=posteriors" << std::endl; return 1; }
+  const std::string pfmt = a.str("crf_output_posterior_format", "ascii");
+  if (pfmt != "ascii" && pfmt != "pfile") { std::cerr << "crf_output_posterior_format=" << pfmt << " (ascii|pfile)" << std::endl; return 1; }
+  const bool want_conf = a.has("crf_output_conffile");
+  if (want_conf && (post_mode || align_mode || a.has("crf_lat_outdir") || a.has("crf_output_mlffile"))) {
+    std::cerr << "crf_output_conffile goes with the best paths of the label file only: not with crf_decode_mode=" << mode
+              << ", crf_lat_outdir or crf_output_mlffile" << std::endl;
+    return 1;
+  }
   if (align_mode && !a.has("hardtarget_file")) { std::cerr << "hardtarget_file required when crf_decode_mode=align" << std::endl; return -1; }
   std::vector<std::vector<uint32_t> > hard_labs;
   if (align_mode) {
@@ -101,6 +132,7 @@ int main(int argc, char** argv) {
   crf.setNActualLabs(m.fmap.nActualLabs);
   crf.setModelType(m.mtype);
   crf.setDevice((int)a.num("crf_device", 0));
+  if (post_mode || want_conf) crf.setTrainPrecision(parse_precision(a));   // the posterior pass runs under the training precision
   try {
     crf.setFeatureMap(CRF_FeatureMap::createFeatureMap(&m.fmap));
   } catch (std::exception& e) { std::cerr << "Exception: " << e.what() << std::endl; return -1; }
@@ -222,14 +254,78 @@ int main(int argc, char** argv) {
     mlf << "." << std::endl;
     std::cout << ". (weight " << total << ")" << std::endl;
   };
+  if (post_mode) {
+    // frame posteriors only, whole device batches of utterances
+    const size_t bunch = (size_t)std::max(1L, a.num("crf_bunch_size", 256));
+    const bool want_log = a.num("crf_posterior_log", 0) != 0, norm = a.num("crf_posterior_norm", 1) != 0;
+    const std::string ppath = a.str("crf_output_posteriorfile");
+    try {
+      std::ofstream pf;
+      std::unique_ptr<qn::PFileWriter> pw;
+      if (pfmt == "pfile") pw.reset(new qn::PFileWriter(ppath, m.L, 0));
+      else {
+        pf.open(ppath.c_str());
+        if (!pf.is_open()) { std::cerr << "ERROR: Failed opening file: " << ppath << std::endl; return -1; }
+        pf.precision(17);
+      }
+      bool at_end = strm.nextseg() == QN_SEGID_BAD;
+      std::vector<float> row32;
+      while (!at_end) {
+        std::vector<std::vector<double> > fp;
+        std::vector<double> zx;
+        crf_amd_posteriors(&strm, &crf, bunch, &fp, nullptr, &zx, nullptr, nullptr, nullptr, &at_end);
+        for (size_t i = 0; i < fp.size(); i++, u++) {
+          std::vector<double>& v = fp[i];
+          for (double& x : v) {
+            if (want_log) x = log(x) + (norm ? 0.0 : zx[i]);
+          }
+          const size_t T = v.size() / m.L;
+          if (pw) {
+            row32.assign(v.begin(), v.end());
+            pw->write_sent(row32.data(), nullptr, (uint32_t)T);
+          } else {
+            for (size_t t = 0; t < T; t++) {
+              pf << u << " " << t;
+              for (uint32_t l = 0; l < m.L; l++) pf << " " << v[t * m.L + l];
+              pf << "\n";
+            }
+          }
+        }
+      }
+      if (pw) pw->close();
+    } catch (std::exception& e) {
+      std::cerr << "Exception: " << e.what() << std::endl;
+      return -1;
+    }
+    return 0;
+  }
   if (!a.has("crf_lat_outdir") && !want_mlf && !align_mode) {
     // best paths only: whole device batches of utterances (crf_bunch_size of them, default 256)
     const size_t bunch = (size_t)std::max(1L, a.num("crf_bunch_size", 256));
+    std::ofstream conf;
+    if (want_conf) {
+      conf.open(a.str("crf_output_conffile").c_str());
+      if (!conf.is_open()) { std::cerr << "ERROR: Failed opening file: " << a.str("crf_output_conffile") << std::endl; return -1; }
+      conf.precision(17);
+    }
     bool at_end = strm.nextseg() == QN_SEGID_BAD;
     while (!at_end) {
       try {
         std::vector<std::vector<uint32_t> > labs;
         std::vector<float> costs;
+        if (want_conf) {
+          // the same best paths (scrf_viterbi_batch on the same batch) with the posterior of each of their segments
+          std::vector<std::vector<double> > sp;
+          crf_amd_posteriors(&strm, &crf, bunch, nullptr, nullptr, nullptr, &labs, &costs, &sp, &at_end);
+          for (size_t i = 0; i < labs.size(); i++) {
+            uint32_t frame = 0;
+            for (size_t k = 0; k < labs[i].size(); k++) {
+              const uint32_t dur = labs[i][k] / m.L + 1;
+              conf << u + i << " " << k << " " << frame << " " << frame + dur - 1 << " " << labs[i][k] % m.L << " " << sp[i][k] << "\n";
+              frame += dur;
+            }
+          }
+        } else
         crf_amd_best_paths(&strm, &crf, bunch, &labs, &costs, &at_end);
         for (const auto& l : labs) emit(l);
       } catch (std::exception& e) {

@@ -713,6 +713,28 @@ void make_batch(crf_amd::Engine* e, CRF_FeatureStream* strm, const std::vector<H
 
 }  // namespace
 
+// crf_amd::StreamBatch: the two helpers above for translation units outside this one (crf_posteriors.cpp)
+struct crf_amd::StreamBatch::Held { std::vector<HeldUtt> utts; };
+crf_amd::StreamBatch::StreamBatch(CRF_FeatureStream* ftr_strm, CRF_Model* crf, size_t max_utts, bool advance) : held(new Held) {
+  e = crf->engine();
+  crf->pushLambda();
+  if (max_utts == 0 || !advance) max_utts = 1;
+  held->utts.reserve(max_utts);
+  while (held->utts.size() < max_utts) {
+    held->utts.emplace_back();
+    grab(ftr_strm, crf, &held->utts.back());
+    T.push_back(held->utts.back().u.T);
+    frames += T.back();
+    if (!advance) break;
+    if (ftr_strm->nextseg() == QN_SEGID_BAD) { at_end = true; break; }
+  }
+  BatchGuard g{e};
+  make_batch(e, ftr_strm, held->utts, &g);
+  b = g.b;
+  g.b = nullptr;
+}
+crf_amd::StreamBatch::~StreamBatch() { if (b) scrf_batch_destroy(e->h, b); }
+
 // ------------------------------------------------------------------------------------------
 // CRF_GradBuilder
 // ------------------------------------------------------------------------------------------

@@ -12,6 +12,7 @@
 //   CRF_Trainer / CRF_SGTrainer                                  trainers/CRF_Trainer.h, CRF_SGTrainer.h:45-48
 //   CRF_StateNode / CRF_StateVector (read-only node view)        nodes/CRF_StateNode.h:67-115
 //   CRF_LatticeBuilder_* ::buildLattice<Fst>                     decoders/...WithoutSegTransFtr.h:26
+//   CRF_NewLocalPosteriorBuilder::buildFtrSeq                    decoders/CRF_NewLocalPosteriorBuilder.h:38-53
 //
 // QuickNet3 and OpenFST are not dependencies: feature streams are an abstract interface the
 // caller implements (a QuickNet-backed one is a 30-line subclass), and
@@ -289,6 +290,25 @@ class Engine {
 };
 
 scrf_config makeConfig(CRF_Model* crf, int device, uint32_t precision);
+// One device batch of the stream's CURRENT utterance and up to max_utts - 1 following ones (the stream is advanced with
+// nextseg() past every utterance taken; at_end is set when it ran out).  advance = false: the current utterance alone,
+// the stream stays where it is.  The model's lambda is pushed first.  Owns the batch.
+class StreamBatch {
+ public:
+  StreamBatch(CRF_FeatureStream* ftr_strm, CRF_Model* crf, size_t max_utts, bool advance = true);
+  ~StreamBatch();
+  StreamBatch(const StreamBatch&) = delete;
+  StreamBatch& operator=(const StreamBatch&) = delete;
+  Engine* e = nullptr;
+  scrf_batch b = nullptr;
+  std::vector<uint32_t> T;   // frames per utterance
+  size_t frames = 0;
+  bool at_end = false;
+
+ private:
+  struct Held;
+  std::unique_ptr<Held> held;
+};
 bool frameAsSegmental(CRF_Model* crf, uint32_t precision);   // the n-state frame model recast as the n-state segmental model with maximum duration 1
 // One process per GPU (CRFTrain under RANK / WORLD_SIZE): rank r only ever walks child view r of the training stream
 // (io/CRF_FeatureStreamManager.cpp:425-464: [r floor(n/N), ...)), so a CRF_FeatureStreamManager built afterwards with N
@@ -547,6 +567,7 @@ class CRF_StateNode {
   virtual double* getAlpha() { return alpha; }          // [nActualLabs]
   virtual double* getBeta() { return beta; }
   virtual double* getAlphaWithDur() { return alpha_dur; }   // [nodeMaxDur][nActualLabs]: row d-1 = duration d
+  virtual double* getAlphaBeta() { return alpha_beta; }     // [nActualLabs]: nodes of CRF_NewLocalPosteriorBuilder only
   virtual double getStateValue(QNUInt32 lab, QNUInt32 dur = 1);
   virtual double getTransValue(QNUInt32 prev_lab, QNUInt32 cur_lab);
   virtual double getFullTransValue(QNUInt32 prev_lab, QNUInt32 cur_lab, QNUInt32 dur = 1);
@@ -556,7 +577,8 @@ class CRF_StateNode {
 
  protected:
   friend class CRF_StateVector;
-  double *alpha = nullptr, *beta = nullptr, *alpha_dur = nullptr, *S = nullptr, *M = nullptr;
+  friend class CRF_NewLocalPosteriorBuilder;
+  double *alpha = nullptr, *beta = nullptr, *alpha_dur = nullptr, *S = nullptr, *M = nullptr, *alpha_beta = nullptr;
   QNUInt32 nLabs = 0, nodeMaxDur = 0, label = CRF_LAB_BAD;
   double zx = 0.0;
   bool last = false;
@@ -570,10 +592,41 @@ class CRF_StateVector {
   double getZx() { return zx; }
 
  private:
+  friend class CRF_NewLocalPosteriorBuilder;
+  CRF_StateVector() {}   // filled by CRF_NewLocalPosteriorBuilder::buildFtrSeq
   std::vector<CRF_StateNode> nodes;
-  std::vector<double> S, M, AD, AL, BE;
+  std::vector<double> S, M, AD, AL, BE, AB;
   double zx = 0.0;
 };
+
+// decoders/CRF_NewLocalPosteriorBuilder.{h,cpp}: the per-frame label posteriors ("CRANDEM" features) of the stream's
+// CURRENT utterance, from scrf_posteriors_batch under the model's training precision.  buildFtrSeq returns a vector of
+// read-only nodes (owned by the builder, valid until the next call) whose getAlphaBeta() row holds, per label,
+//   norm = true : the log of the frame posterior (for the frame model the reference's alpha + beta - Zx);
+//   norm = false: that plus Zx (the frame model's alpha + beta, the reference's norm_const = 0).
+// For a segmental model the frame posterior is the summed posterior of the segments that cover the frame (DESIGN.md
+// 4.13).  As there, a frame whose posterior mass leaves [0.9, 1.1] throws.  The other node accessors are not filled.
+class CRF_NewLocalPosteriorBuilder {
+ public:
+  CRF_NewLocalPosteriorBuilder(CRF_Model* crf_in, bool norm = true);
+  virtual ~CRF_NewLocalPosteriorBuilder();
+  virtual CRF_StateVector* buildFtrSeq(CRF_FeatureStream* ftr_strm);
+
+ protected:
+  CRF_Model* crf;
+  CRF_StateVector* nodeList = nullptr;
+  bool normalize;
+};
+
+// Posteriors of the stream's CURRENT utterance and up to max_utts - 1 following ones in one device batch (the stream is
+// advanced with nextseg(); *at_end is set when it ran out), in the style of crf_amd_best_paths below.  Per utterance:
+// frame_post [T * L] (row f = the posteriors of frame f's labels), end_post [T] (posterior that a segment ends at the
+// frame; may be NULL), zx.  With `labels` (may be NULL) the best paths of the same batch come back as
+// crf_amd_best_paths returns them, with `costs` and, per segment of each path, its posterior in `seg_post`.
+size_t crf_amd_posteriors(CRF_FeatureStream* ftr_strm, CRF_Model* crf, size_t max_utts,
+                          std::vector<std::vector<double> >* frame_post, std::vector<std::vector<double> >* end_post,
+                          std::vector<double>* zx, std::vector<std::vector<uint32_t> >* labels, std::vector<float>* costs,
+                          std::vector<std::vector<double> >* seg_post, bool* at_end);
 
 // lattice builders: same call as the reference's templates; the arcs come from the engine in
 // AddArc order and are replayed into the caller's FST object

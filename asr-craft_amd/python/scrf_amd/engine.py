@@ -101,9 +101,10 @@ def _p(a):
 
 
 class Batch:
-    def __init__(self, eng, handle, n, keep):
+    def __init__(self, eng, handle, n, keep, Ts=None):
         self.eng, self.handle, self.n = eng, handle, n
         self._keep = keep
+        self.Ts = Ts   # frames per utterance (posteriors_batch splits its per-frame outputs by them)
         nu = C.c_uint32(); nf = C.c_uint64(); ns = C.c_uint64(); na = C.c_uint64()
         eng._chk(eng.lib.scrf_batch_info(eng.h, handle, C.byref(nu), C.byref(nf), C.byref(ns), C.byref(na)))
         self.n_frames, self.n_segs, self.n_arcs = nf.value, ns.value, na.value
@@ -251,7 +252,7 @@ class Engine:
         rec = (StreamRecipe * len(recipes))(*recipes)
         hb = C.c_void_p()
         self._chk(self.lib.scrf_batch_create(self.h, utts, C.c_uint32(n), C.c_uint32(len(recipes)), rec, C.byref(hb)))
-        return Batch(self, hb, n, None)
+        return Batch(self, hb, n, None, [int(utts[u].T) for u in range(n)])
 
     def batch_from_windows(self, windows_list, T_list, labels_list=None):
         n = len(windows_list)
@@ -268,7 +269,7 @@ class Engine:
                 utts[u].labels = lb.ctypes.data
         hb = C.c_void_p()
         self._chk(self.lib.scrf_batch_create(self.h, utts, C.c_uint32(n), C.c_uint32(0), None, C.byref(hb)))
-        return Batch(self, hb, n, None)
+        return Batch(self, hb, n, None, [int(t) for t in T_list])
 
     # ---- hot path
     def fb_batch(self, batch, want_scalars=True):
@@ -323,6 +324,59 @@ class Engine:
         self._chk(self.lib.scrf_forward_backward(self.h, batch.handle, C.c_uint32(u), C.c_uint32(prec), _p(ad), _p(al),
                                                  _p(be), C.byref(zx)))
         return ad, al, be, zx.value
+
+    # ---- posterior output
+    def posteriors_batch(self, batch, frame=True, end=True, segments=None):
+        """Posteriors of a (label-less) batch under the engine's precision.  Returns a dict: "zx" [U]; "frame": per
+        utterance the frame-level label posteriors [T, L] (rows sum to 1); "end": per utterance the posterior [T] that a
+        segment ends at each frame; "segments": per utterance the posterior of every segment of `segments`, which takes
+        what viterbi_batch returns (its RaggedLabels, or a list of per-utterance label arrays).  The per-utterance
+        arrays are views into one array each ("frame_flat", "end_flat", "segments_flat"), split by T."""
+        U = batch.n
+        if batch.Ts is None:
+            raise ValueError("posteriors_batch: the batch does not know its utterance lengths (Batch.Ts)")
+        if segments is not None and len(segments) != U:
+            raise ValueError("posteriors_batch: segments has %d entries for a batch of %d utterances" % (len(segments), U))
+        out = {"zx": np.empty(U)}
+        fp = np.empty((batch.n_frames, self.L)) if frame else None
+        ep = np.empty(batch.n_frames) if end else None
+        labs = off = sp = None
+        if segments is not None:
+            if isinstance(segments, RaggedLabels):
+                labs = np.ascontiguousarray(segments.flat, dtype=np.uint32)
+                off = np.ascontiguousarray(segments.off, dtype=np.uint64)
+            else:
+                off = np.zeros(U + 1, dtype=np.uint64)
+                off[1:] = np.cumsum([len(s) for s in segments])
+                labs = np.ascontiguousarray(np.concatenate([np.asarray(s, dtype=np.uint32) for s in segments]) if U else [], dtype=np.uint32)
+            sp = np.empty(int(off[U]))
+        self._chk(self.lib.scrf_posteriors_batch(self.h, batch.handle, _p(out["zx"]), _p(fp) if frame else None,
+                                                 _p(ep) if end else None, _p(labs) if sp is not None else None,
+                                                 _p(off) if sp is not None else None, _p(sp) if sp is not None else None))
+        fo = np.concatenate([[0], np.cumsum(batch.Ts)]).astype(np.int64)
+        if frame:
+            out["frame_flat"] = fp
+            out["frame"] = [fp[fo[u]:fo[u + 1]] for u in range(U)]
+        if end:
+            out["end_flat"] = ep
+            out["end"] = [ep[fo[u]:fo[u + 1]] for u in range(U)]
+        if sp is not None:
+            out["segments_flat"] = sp
+            out["segments"] = [sp[int(off[u]):int(off[u + 1])] for u in range(U)]
+        return out
+
+    def posterior_stats(self):
+        """(launches of the posterior walk in frame segments, launches in one piece) since create"""
+        a = C.c_uint64(); b = C.c_uint64()
+        self._chk(self.lib.scrf_posterior_stats(self.h, C.byref(a), C.byref(b)))
+        return a.value, b.value
+
+    def seg_posteriors(self, batch, u, T):
+        """parity hook: gamma [N_seg, L] of utterance u (row seg_base(t) + d - 1 = the segment ending at t with duration d)
+        from the EXACT scores and the log-domain recursion"""
+        g = np.zeros((self.num_segs(T), self.L))
+        self._chk(self.lib.scrf_seg_posteriors(self.h, batch.handle, C.c_uint32(u), _p(g)))
+        return g
 
     # ---- decode
     def lattice_arcs(self, batch, u, norm=False):

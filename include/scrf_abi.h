@@ -216,7 +216,7 @@ int scrf_batch_is_fused(scrf_handle h, scrf_batch b, int* fused);
  * kernels, which follow the reference's LogMath, and only their verdict is reported (scrf_train_stats
  * counts these batches). */
 int scrf_fb_batch(scrf_handle h, scrf_batch b, double* numer, double* zx);
-/* batches scrf_fb_batch had to redo through the log-domain recursion since scrf_create */
+/* batches scrf_fb_batch (and scrf_posteriors_batch) had to redo through the log-domain recursion since scrf_create */
 int scrf_train_stats(scrf_handle h, uint64_t* n_lin_fallback);
 int scrf_zero_grad(scrf_handle h);
 int scrf_get_grad(scrf_handle h, double* grad, uint32_t n);      /* device -> host copy */
@@ -279,6 +279,38 @@ int scrf_decode_stats(scrf_handle h, uint64_t* n_recomputed, uint64_t* n_fallbac
  * utterance the reference's frame node accepts must not abort training because the stricter segmental check is applied. */
 int scrf_set_frame_mass_check(scrf_handle h, int on);
 
+/* ---- posterior output ------------------------------------------------------------------------ */
+/* replaces: CRF_NewLocalPosteriorBuilder::buildFtrSeq (decoders/CRF_NewLocalPosteriorBuilder.cpp:61-188) for every
+ * utterance of the batch; the batch needs no labels.  With gamma(t, d, l) the posterior of the segment that ends at
+ * frame t with duration d and label l:
+ *   frame_post[f][l] = sum of gamma(t, d, l) over the segments covering frame f (t-d+1 <= f <= t); every row sums to 1.
+ *                      Frame model (lab_max_dur 1): the node posterior exp(alpha + beta - Zx) of buildFtrSeq;
+ *   end_post[t]      = sum over d, l of gamma(t, d, l): the posterior that a segment ends at t (1 at the last frame);
+ *   seg_post[i]      = gamma of segment i of a path as scrf_viterbi_batch returns it (label value l + L*(d-1), segments
+ *                      back to back from frame 0, lab_off[u]..lab_off[u+1]).  A segment that runs past its utterance or a
+ *                      label >= num_labs * lab_max_dur is SCRF_ERR_INVALID.
+ * Runs under the handle's train_precision on the kernels of scrf_fb_batch (same batch forms, same chunking), minus
+ * everything that needs labels or feeds the gradient: the gradient, the batch sums and the optimizer state are not
+ * touched.  The posterior-mass self-checks run as in training; SCRF_ERR_NUMERIC names the first failed utterance, and a
+ * failure of the wavefront recursions is redone in the log domain first (counted by scrf_train_stats).  Outputs are host
+ * arrays; one that is NULL is neither copied nor, where that saves work, computed.  SCRF_STDSEG, SCRF_STDSEG_NO_DUR and
+ * num_states > 1 are refused (SCRF_ERR_INVALID).
+ * Device memory: the outputs of the whole batch sit in one array the handle owns OUTSIDE the scratch_bytes budget
+ * (8 * sum T * (L + 1) bytes with frame_post: 472 MB at 4096 x 300 frames x 48 labels).  It grows to the largest call
+ * seen and is kept for the next one (calls that alternate between output sets do not reallocate); scrf_destroy frees it. */
+int scrf_posteriors_batch(scrf_handle h, scrf_batch b,
+                          double* zx,          /* [n_utts] or NULL */
+                          double* frame_post,  /* [sum T][L] or NULL */
+                          double* end_post,    /* [sum T] or NULL */
+                          const uint32_t* seg_labels, const uint64_t* lab_off,   /* as scrf_viterbi_batch wrote them, or NULL */
+                          double* seg_post);   /* [lab_off[n_utts]] or NULL */
+/* parity hook: gamma [N_seg][L] of utterance u from the EXACT scores and the log-domain recursion */
+int scrf_seg_posteriors(scrf_handle h, scrf_batch b, uint32_t u, double* gamma);
+/* launches of the linear-domain posterior walk since scrf_create that split every utterance into frame segments (a
+ * launch of few utterances) / that walked every utterance in one piece.  SCRF_POSTOCC_SPLIT=0 at scrf_create: never
+ * split.  The two forms give bit-identical results; the counters let a test know which one ran. */
+int scrf_posterior_stats(scrf_handle h, uint64_t* n_split, uint64_t* n_whole);
+
 /* ---- minibatch reduce + optimizer ------------------------------------------------------------ */
 /* replaces the join/sum/average of CRF_Minibatch_GradAccumulator::accumulateGradient
  * (trainers/accumulators/CRF_Minibatch_GradAccumulator.cpp:277-312): all-reduce (sum) of the
@@ -336,7 +368,7 @@ int scrf_sgd_step(scrf_handle h, double lr_or_eta, int use_adagrad, double eps);
  * kernel (the three that dominate a step). */
 #define SCRF_N_PHASES 10
 int scrf_last_timing(scrf_handle h, float* ms, uint32_t* n_launch);
-/* HIP-event time of every kernel of the last timed scrf_fb_batch / scrf_viterbi_batch, one line per kernel
+/* HIP-event time of every kernel of the last timed scrf_fb_batch / scrf_posteriors_batch / scrf_viterbi_batch, one line per kernel
  * name: "name\tmilliseconds\tlaunches\n" (events recorded on the stream the kernel is launched on) */
 int scrf_kernel_timing(scrf_handle h, char* buf, size_t cap);
 int scrf_enable_timing(scrf_handle h, int on);
