@@ -11,6 +11,7 @@
 #include <string.h>
 
 #include <algorithm>
+#include <cmath>
 #include <string>
 #include <unordered_map>
 #include <vector>
@@ -170,6 +171,15 @@ struct scrf_engine_s {
   // result arrays of scrf_posteriors_batch (whole batch: chunking stays invisible), kept across calls like the decode buffers
   char* post_buf = nullptr;
   size_t post_cap = 0;
+  // result of scrf_lattice_prune_batch: the kept arcs of the whole batch, back to back, outside the scratch
+  // budget; grows geometrically, kept across calls.  One result, tied to the batch and the weights it was computed from
+  scrf_arc* lp_arcs = nullptr;
+  uint64_t lp_cap = 0;             // arcs
+  char* lp_meta = nullptr;         // best [U] doubles | utterance offsets [U + 1]
+  size_t lp_meta_cap = 0;
+  scrf_batch lp_batch = nullptr;   // the batch of the valid result, or nullptr
+  std::vector<uint64_t> lp_off;    // [U + 1] host image of the offsets
+  uint64_t n_lp_calls = 0, n_lp_chunks = 0;
   std::string err;
   // per-kernel HIP-event times of the last timed call (scrf_kernel_timing)
   struct KTime { std::string name; double ms; uint32_t n; };
@@ -458,6 +468,7 @@ extern "C" int scrf_destroy(scrf_handle h) {
   if (h->ev_join) hipEventDestroy(h->ev_join);
   hipFree(h->dec_lab); hipFree(h->dec_n); hipFree(h->dec_cost);
   hipFree(h->post_buf);
+  hipFree(h->lp_arcs); hipFree(h->lp_meta);
   if (h->dec_hlab) hipHostFree(h->dec_hlab);
   if (h->dec_hn) hipHostFree(h->dec_hn);
   if (h->dec_hcost) hipHostFree(h->dec_hcost);
@@ -541,7 +552,7 @@ static int vec_io(scrf_handle h, double* dev, const double* in, double* out, uin
 }
 extern "C" int scrf_set_lambda(scrf_handle h, const double* v, uint32_t n) {
   int rc = vec_io(h, h ? h->d_lambda : nullptr, v, nullptr, n, "scrf_set_lambda");
-  if (rc == SCRF_OK) h->m0_valid = false;
+  if (rc == SCRF_OK) { h->m0_valid = false; h->lp_batch = nullptr; }
   return rc;
 }
 extern "C" int scrf_get_lambda(scrf_handle h, double* v, uint32_t n) { return vec_io(h, h ? h->d_lambda : nullptr, nullptr, v, n, "scrf_get_lambda"); }
@@ -733,6 +744,7 @@ static uint64_t shadow_num_arcs(scrf_handle h, uint32_t T) {
 extern "C" int scrf_batch_destroy(scrf_handle h, scrf_batch b) {
   if (!b) return SCRF_OK;
   if (h) hipSetDevice(h->device);
+  if (h && h->lp_batch == b) h->lp_batch = nullptr;
   if (h && !h->pool_on) hipStreamSynchronize(h->stream);
   // (pool: no synchronisation here -- the blocks wait in the pool until the engine stream has passed this point)
 #define BFREE(p) pool_release(h, (void*)(p))
@@ -1079,12 +1091,16 @@ struct ChunkBufs {
   double* slab_d = nullptr;  // duration + bias counts of the wave-specialised count kernel (behind slab_s)
   int expf_tiles = 1;        // tile list the fused count kernel walks
   ScrfSparseIndex spx[2];    // sparse maps: inverted index + bias slab of the state [0] / transition [1] counts
+  ScrfLatBufs lat = {nullptr, nullptr, nullptr, nullptr, nullptr};   // lattice beam: distances of the chunk's states
+  uint32_t* lat_counts = nullptr;   // [nodes of the chunk] kept arcs per node
+  uint64_t* lat_node_off = nullptr; // [nodes + 1]
   bool lamT_ready = false;   // sparse maps: h->d_lamT already re-laid for this call (scrf_fb_batch: once, before the lanes fork)
 };
 
 // ponly (scrf_posteriors_batch): the recursion of the training path without anything that needs labels or feeds the
 // gradient -- the linear-domain vectors (or alpha_dur / beta) and the per-frame state mass, no count buffers
-struct Need { bool fb, post, beta, vit; bool fused = false; bool vitfast = false; bool la = false; bool hybrid = false; bool ponly = false; bool plog = false; };
+struct Need { bool fb, post, beta, vit; bool fused = false; bool vitfast = false; bool la = false; bool hybrid = false; bool ponly = false; bool plog = false; bool lat = false; };
+// lat (scrf_lattice_prune_batch): four distance arrays over the chunk's frames and the node counts / offsets
 // plog: ponly through the log-domain recursion (SCRF_PREC_EXACT)
 static bool need_lin(const Need& nd) { return nd.post || (nd.ponly && !nd.plog); }
 
@@ -1188,6 +1204,7 @@ static size_t chunk_bytes(scrf_handle h, scrf_batch b, uint64_t nutt, uint64_t n
     }
   }
   if (nd.vit) tot += 2 * pad256(nfr * l.L * sizeof(uint16_t));
+  if (nd.lat) tot += 4 * pad256(nfr * l.L * sizeof(double)) + pad256((nfr + nutt) * sizeof(uint32_t)) + pad256((nfr + nutt + 1) * sizeof(uint64_t));
   return tot + 4096;
 }
 
@@ -1345,6 +1362,12 @@ static int carve(scrf_handle h, scrf_batch b, uint32_t u0, uint32_t u1, const Ne
   if (nd.vit) {
     cb->bp_b = a.take<uint16_t>(nfr * l.L);
     cb->bp_e = a.take<uint16_t>(nfr * l.L);
+  }
+  if (nd.lat) {
+    cb->lat.fB = a.take<double>(nfr * l.L); cb->lat.fE = a.take<double>(nfr * l.L);
+    cb->lat.bB = a.take<double>(nfr * l.L); cb->lat.bE = a.take<double>(nfr * l.L);
+    cb->lat_counts = a.take<uint32_t>(nfr + nutt);
+    cb->lat_node_off = a.take<uint64_t>(nfr + nutt + 1);
   }
   if (a.off > a.cap) return fail(h, SCRF_ERR_INVALID, "internal: scratch arena overflow");
   return SCRF_OK;
@@ -2767,6 +2790,118 @@ extern "C" int scrf_lattice_arcs(scrf_handle h, scrf_batch b, uint32_t u, int no
   return SCRF_OK;
 }
 
+// ---------------------------------------------------------------------------------------------
+// beam-pruned lattices of a batch
+// ---------------------------------------------------------------------------------------------
+extern "C" int scrf_lattice_prune_batch(scrf_handle h, scrf_batch b, double beam, uint64_t* arc_off, double* best_cost) {
+  if (!h || !b || !arc_off) return SCRF_ERR_INVALID;
+  h->lp_batch = nullptr;   // whatever happens, the previous result is gone
+  if (h->cfg.model_type == SCRF_STDSEG || h->cfg.model_type == SCRF_STDSEG_NO_DUR)
+    return fail(h, SCRF_ERR_INVALID, "scrf_lattice_prune_batch: the lattice beam is not built for the \"%s\" CRF model; use \"stdframe\", "
+                "\"stdseg_no_dur_no_transftr\" or \"stdseg_no_dur_no_segtransftr\"", model_type_name(h->cfg.model_type));
+  if (h->cfg.num_states > 1)
+    return fail(h, SCRF_ERR_INVALID, "scrf_lattice_prune_batch: the lattice beam is built for crf_states = 1 only (this \"%s\" model has crf_states = %u)",
+                model_type_name(h->cfg.model_type), h->cfg.num_states);
+  if (!(beam > 0.0) || !std::isfinite(beam))
+    return fail(h, SCRF_ERR_INVALID, "scrf_lattice_prune_batch: the beam must be finite and > 0 (got %g)", beam);
+  const ScrfLayout& l = h->lay;
+  if (lat_sweep_smem_bytes(l) > 160 * 1024)
+    return fail(h, SCRF_ERR_INVALID, "scrf_lattice_prune_batch: %u labels x maximum duration %u do not fit the sweep kernel's LDS window", l.L, l.D);
+  HIPCHK(h, hipSetDevice(h->device));
+  const bool frame_model = h->cfg.model_type == SCRF_STDFRAME;
+  const uint32_t U = b->U;
+  const size_t by_best = pad256(sizeof(double) * U), need_meta = by_best + pad256(sizeof(uint64_t) * (U + 1));
+  if (need_meta > h->lp_meta_cap) {
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    hipFree(h->lp_meta); h->lp_meta = nullptr; h->lp_meta_cap = 0;
+    HIPCHK(h, hipMalloc((void**)&h->lp_meta, need_meta));
+    h->lp_meta_cap = need_meta;
+  }
+  double* d_best = (double*)h->lp_meta;
+  uint64_t* d_uoff = (uint64_t*)(h->lp_meta + by_best);
+  if (h->timing) {
+    memset(h->ms, 0, sizeof(h->ms)); memset(h->nlaunch, 0, sizeof(h->nlaunch)); h->ktimes.clear();
+    hipEventRecord(h->ev[SCRF_N_PHASES][0], h->stream);
+  }
+  h->n_lp_calls++;
+  Need nd{false, false, false, false};
+  nd.lat = true;
+  ScrfBatchView bv = b->view();
+  uint64_t total = 0;   // kept arcs of the chunks done
+  for (uint32_t u0 = 0; u0 < U;) {
+    const uint32_t u1 = plan_chunk(h, b, u0, nd);
+    ChunkBufs cb;
+    int rc = carve(h, b, u0, u1, nd, &cb);
+    if (rc != SCRF_OK) return rc;
+    rc = run_scores(h, b, u0, u1, cb);
+    if (rc != SCRF_OK) return rc;
+    h->n_lp_chunks++;
+    const uint32_t nutt = u1 - u0;
+    const uint64_t nfr = b->frame_off[u1] - b->frame_off[u0], n_nodes = nfr + nutt;
+    uint32_t t_max = 0;
+    for (uint32_t u = u0; u < u1; u++) t_max = std::max(t_max, b->T[u]);
+    cb.lat.best = d_best;
+    KT_RUN("k_lat_sweep", cb.st, launch_lat_sweep(cb.st, l, bv, u0, nutt, cb.S, cb.M, cb.m_per_frame, frame_model, cb.lat));
+    KT_RUN("k_lat_count", cb.st, launch_lat_count(cb.st, l, bv, u0, nutt, t_max, cb.S, cb.M, cb.m_per_frame, frame_model, cb.lat, beam, cb.lat_counts));
+    KT_RUN("k_lat_scan", cb.st, launch_lat_scan(cb.st, bv, u0, nutt, cb.lat_counts, n_nodes, cb.lat_node_off, total, d_uoff));
+    uint64_t kept = 0;   // the chunk's arcs must have room before they are written
+    HIPCHK(h, hipMemcpyAsync(&kept, cb.lat_node_off + n_nodes, sizeof(uint64_t), hipMemcpyDeviceToHost, cb.st));
+    HIPCHK(h, hipStreamSynchronize(cb.st));
+    if (total + kept > h->lp_cap) {
+      const uint64_t cap = std::max<uint64_t>(std::max<uint64_t>(total + kept, 2 * h->lp_cap), 1u << 16);
+      scrf_arc* na = nullptr;
+      HIPCHK(h, hipMalloc((void**)&na, sizeof(scrf_arc) * cap));
+      hipError_t e = total ? hipMemcpyAsync(na, h->lp_arcs, sizeof(scrf_arc) * total, hipMemcpyDeviceToDevice, cb.st) : hipSuccess;
+      if (e == hipSuccess) e = hipStreamSynchronize(cb.st);
+      if (e != hipSuccess) { hipFree(na); return fail(h, SCRF_ERR_HIP, "scrf_lattice_prune_batch: %s", hipGetErrorString(e)); }
+      hipFree(h->lp_arcs);
+      h->lp_arcs = na; h->lp_cap = cap;
+    }
+    KT_RUN("k_lat_emit", cb.st, launch_lat_emit(cb.st, l, bv, u0, nutt, t_max, cb.S, cb.M, cb.m_per_frame, frame_model, cb.lat, beam, cb.lat_node_off,
+                                                total, h->lp_cap, h->lp_arcs));
+    HIPCHK(h, hipGetLastError());
+    total += kept;
+    u0 = u1;
+  }
+  h->lp_off.resize(U + 1);
+  HIPCHK(h, hipMemcpyAsync(h->lp_off.data(), d_uoff, sizeof(uint64_t) * (U + 1), hipMemcpyDeviceToHost, h->stream));
+  if (best_cost) HIPCHK(h, hipMemcpyAsync(best_cost, d_best, sizeof(double) * U, hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  if (h->timing) {
+    hipEventRecord(h->ev[SCRF_N_PHASES][1], h->stream);
+    hipEventSynchronize(h->ev[SCRF_N_PHASES][1]);
+    hipEventElapsedTime(&h->ms[PH_ALL], h->ev[SCRF_N_PHASES][0], h->ev[SCRF_N_PHASES][1]);
+  }
+  if (h->lp_off[U] != total) return fail(h, SCRF_ERR_INVALID, "scrf_lattice_prune_batch: arc count mismatch (internal)");
+  memcpy(arc_off, h->lp_off.data(), sizeof(uint64_t) * (U + 1));
+  h->lp_batch = b;
+  return SCRF_OK;
+}
+
+extern "C" int scrf_lattice_pruned_arcs(scrf_handle h, scrf_batch b, uint32_t u0, uint32_t n, scrf_arc* arcs, uint64_t cap) {
+  if (!h || !b) return SCRF_ERR_INVALID;
+  if (h->lp_batch != b)
+    return fail(h, SCRF_ERR_INVALID, "scrf_lattice_pruned_arcs: no valid result for this batch (call scrf_lattice_prune_batch first; new weights, "
+                "another prune call or destroying the batch drop it)");
+  if ((uint64_t)u0 + n > b->U) return fail(h, SCRF_ERR_INVALID, "scrf_lattice_pruned_arcs: utterances %u .. %llu of a batch of %u", u0,
+                                           (unsigned long long)u0 + n, b->U);
+  const uint64_t a0 = h->lp_off[u0], na = h->lp_off[u0 + n] - a0;
+  if (cap < na) return fail(h, SCRF_ERR_INVALID, "scrf_lattice_pruned_arcs: room for %llu arcs, %llu needed", (unsigned long long)cap, (unsigned long long)na);
+  if (na == 0) return SCRF_OK;
+  if (!arcs) return SCRF_ERR_INVALID;
+  HIPCHK(h, hipSetDevice(h->device));
+  HIPCHK(h, hipMemcpyAsync(arcs, h->lp_arcs + a0, sizeof(scrf_arc) * na, hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  return SCRF_OK;
+}
+
+extern "C" int scrf_lattice_prune_stats(scrf_handle h, uint64_t* n_calls, uint64_t* n_chunks) {
+  if (!h) return SCRF_ERR_INVALID;
+  if (n_calls) *n_calls = h->n_lp_calls;
+  if (n_chunks) *n_chunks = h->n_lp_chunks;
+  return SCRF_OK;
+}
+
 extern "C" int scrf_viterbi_batch(scrf_handle h, scrf_batch b, uint32_t* seg_labels, uint64_t max_labels,
                                   uint64_t* lab_off, float* best_cost) {
   if (!h || !b || !seg_labels || !lab_off) return SCRF_ERR_INVALID;
@@ -3193,6 +3328,7 @@ extern "C" int scrf_sgd_step(scrf_handle h, double lr_or_eta, int use_adagrad, d
                   use_adagrad, eps);
   HIPCHK(h, hipMemsetAsync(h->d_sums, 0, sizeof(double) * 4, h->stream));
   h->m0_valid = false;
+  h->lp_batch = nullptr;
   HIPCHK(h, hipGetLastError());
   return SCRF_OK;
 }

@@ -271,4 +271,23 @@ void launch_sp_scores(hipStream_t st, const float* X, uint32_t F, const uint64_t
 void launch_sp_counts(hipStream_t st, const float* X, uint32_t F, const uint64_t* xrow, uint64_t n_rows, const double* R,
                       const ScrfLayout& l, int kind, const ScrfSparseIndex& ix, double* grad);
 
+// ---- beam-pruned lattices (scrf_latprune.hip): fp64 tropical forward / backward distances of the lattice's
+// states, [frames of the chunk][L] each -- boundary states (B) and end states (E); the frame model uses the E arrays only --
+// and fwd[final] per utterance of the batch
+struct ScrfLatBufs {
+  double *fB, *fE, *bB, *bE;
+  double* best;   // [U], batch-absolute
+};
+size_t lat_sweep_smem_bytes(const ScrfLayout& lay);
+void launch_lat_sweep(hipStream_t st, const ScrfLayout& lay, ScrfBatchView bv, uint32_t u0, uint32_t n_utts, const double* S,
+                      const double* M, int m_per_frame, int frame_model, const ScrfLatBufs& lb);
+void launch_lat_count(hipStream_t st, const ScrfLayout& lay, ScrfBatchView bv, uint32_t u0, uint32_t n_utts, uint32_t t_max,
+                      const double* S, const double* M, int m_per_frame, int frame_model, const ScrfLatBufs& lb, double beam,
+                      uint32_t* counts);
+void launch_lat_scan(hipStream_t st, ScrfBatchView bv, uint32_t u0, uint32_t n_utts, const uint32_t* counts, uint64_t n_nodes,
+                     uint64_t* node_off, uint64_t base, uint64_t* utt_off);
+void launch_lat_emit(hipStream_t st, const ScrfLayout& lay, ScrfBatchView bv, uint32_t u0, uint32_t n_utts, uint32_t t_max,
+                     const double* S, const double* M, int m_per_frame, int frame_model, const ScrfLatBufs& lb, double beam,
+                     const uint64_t* node_off, uint64_t base, uint64_t cap, scrf_arc* out);
+
 #endif  // SCRF_KERNELS_H_

@@ -14,6 +14,7 @@
 // This translation unit is compiled with -ffp-contract=off: the EXACT kernels must not fuse
 // multiply and add (the reference is built without FMA contraction).
 #include "scrf_kernels.h"
+#include "scrf_arcw.h"
 #include "scrf_lse.h"
 
 #include <float.h>
@@ -1026,7 +1027,7 @@ __global__ void k_arcs_seg(ScrfLayout lay, uint32_t T, const double* __restrict_
     const int32_t pbase = (t == 1) ? scrf_node_start_state(0, L) : scrf_node_start_state(t - 1, L) + (int32_t)L;
     for (uint32_t idx = threadIdx.x; idx < L * L; idx += blockDim.x) {
       uint32_t lab = idx / L, pl = idx % L;
-      scrf_arc a = {pbase + (int32_t)pl, 0, 0, (float)(-1.0 * Mt[(size_t)pl * L + lab]), nss + (int32_t)lab};
+      scrf_arc a = {pbase + (int32_t)pl, 0, 0, scrf_w_boundary(Mt, L, pl, lab), nss + (int32_t)lab};
       arcs[ab + idx] = a;
     }
     eb += LL;
@@ -1036,7 +1037,7 @@ __global__ void k_arcs_seg(ScrfLayout lay, uint32_t T, const double* __restrict_
     uint32_t lab = idx / nd, d = idx % nd + 1;
     int32_t src = (d <= np) ? scrf_node_start_state(t - d + 1, L) + (int32_t)lab : 0;
     int32_t lb = (int32_t)(lab + L * (d - 1) + 1);
-    scrf_arc a = {src, lb, lb, (float)(-1.0 * S[(base + d - 1) * L + lab]), ebase + (int32_t)lab};
+    scrf_arc a = {src, lb, lb, scrf_w_segment(S, base, d, L, lab), ebase + (int32_t)lab};
     arcs[eb + idx] = a;
   }
 }
@@ -1058,7 +1059,7 @@ __global__ void k_arcs_frame(ScrfLayout lay, uint32_t T, const double* __restric
   }
   if (t == 0) {
     for (uint32_t c = threadIdx.x; c < L; c += blockDim.x) {
-      scrf_arc a = {0, (int32_t)c + 1, (int32_t)c + 1, (float)(-1.0 * S[c]), (int32_t)c + 1};
+      scrf_arc a = {0, (int32_t)c + 1, (int32_t)c + 1, scrf_w_segment(S, 0, 1, L, c), (int32_t)c + 1};
       arcs[c] = a;
     }
     return;
@@ -1067,7 +1068,7 @@ __global__ void k_arcs_frame(ScrfLayout lay, uint32_t T, const double* __restric
   const double* Mt = M + (m_per_frame ? (size_t)t * LL : 0);
   for (uint32_t idx = threadIdx.x; idx < L * L; idx += blockDim.x) {
     uint32_t c = idx / L, p = idx % L;
-    float w = (float)(-1.0 * (Mt[(size_t)p * L + c] + S[(size_t)t * L + c]));
+    float w = scrf_w_frame(Mt, S, t, L, p, c);
     scrf_arc a = {(int32_t)(L * (t - 1) + p + 1), (int32_t)c + 1, (int32_t)c + 1, w, (int32_t)(L * t + c + 1)};
     arcs[ab + idx] = a;
   }

@@ -28,6 +28,14 @@
 //   crf_output_conffile=PATH, on the best-paths-only branch (no crf_lat_outdir, no MLF, not align): beside the label
 //   file, `sent seg first_frame last_frame label posterior` per segment of the best path (label = phone, posterior = the
 //   segment's posterior gamma).  The label file itself does not change.
+// A third one (beam-pruned lattices):
+//   crf_lat_beam=B (B > 0), in crf_decode_mode=decode together with crf_lat_outdir and/or crf_output_mlffile: the
+//   utterances' lattices come from the device already cut by a tropical beam in fp64 -- an arc stays when the best path
+//   through it costs at most B more than the best path of the utterance -- in device batches of crf_bunch_size utterances,
+//   renumbered to the states the kept arcs touch.  Everything downstream (the binary and text lattice dump, the MLF path
+//   with its LM / dictionary / phone FST / crf_align_mlffile chain) consumes the pruned machine unchanged; the label file
+//   holds the same best paths.  Ends with `Lattice beam B: kept K of N arcs`.  Refused with crf_decode_mode=align (a
+//   transcript's path may be pruned away), crf_decode_mode=posteriors, or when nothing would consume a lattice.
 #include "cli_common.h"
 
 #include <math.h>
@@ -58,6 +66,17 @@ int main(int argc, char** argv) {
   const std::string mode = a.str("crf_decode_mode", "decode");
   if (mode != "decode" && mode != "align" && mode != "posteriors") { std::cerr << "crf_decode_mode=" << mode << " (decode|align|posteriors)" << std::endl; return 1; }
   const bool align_mode = mode == "align", post_mode = mode == "posteriors";
+  const bool have_beam = a.has("crf_lat_beam");
+  const double lat_beam = a.real("crf_lat_beam", 0.0);
+  if (have_beam) {
+    if (!(lat_beam > 0.0) || !std::isfinite(lat_beam)) { std::cerr << "crf_lat_beam=" << a.str("crf_lat_beam") << ": the lattice beam must be a finite number > 0" << std::endl; return 1; }
+    if (align_mode) { std::cerr << "crf_lat_beam makes no sense with crf_decode_mode=align: the transcript's path may be pruned away" << std::endl; return 1; }
+    if (post_mode) { std::cerr << "crf_lat_beam makes no sense with crf_decode_mode=posteriors: no lattice is built there" << std::endl; return 1; }
+    if (!a.has("crf_lat_outdir") && !a.has("crf_output_mlffile")) {
+      std::cerr << "crf_lat_beam needs crf_lat_outdir and/or crf_output_mlffile: nothing else consumes a lattice" << std::endl;
+      return 1;
+    }
+  }
   if (post_mode) {
     for (const char* k : {"crf_lm_txt", "crf_lm_bin", "crf_dict_txt", "crf_dict_bin", "crf_phn_txt", "crf_phn_bin", "crf_align_mlffile", "crf_output_mlffile", "crf_lat_outdir"})
       if (a.has(k)) { std::cerr << "crf_decode_mode=posteriors writes frame posteriors only: " << k << " makes no sense with it" << std::endl; return 1; }
@@ -299,7 +318,51 @@ int main(int argc, char** argv) {
     }
     return 0;
   }
-  if (!a.has("crf_lat_outdir") && !want_mlf && !align_mode) {
+  // the lattice of sentence n as the reference writes it, fst.<n>.final.fst (:832-837; layout unpinned, crf_amd.h), plus the
+  // same arcs as text
+  auto dump_lattice = [&](const crf_amd::ArcListFst& fst, size_t n) {
+    crf_amd::writeFstBinary((a.str("crf_lat_outdir") + "/fst." + std::to_string(n) + ".final.fst").c_str(), fst);
+    std::ofstream lf((a.str("crf_lat_outdir") + "/fst." + std::to_string(n) + ".txt").c_str());
+    for (const scrf_arc& c : fst.arcs) lf << c.src << " " << c.dst << " " << c.ilabel << " " << c.olabel << " " << c.w << "\n";
+    lf << fst.final_state << "\n";
+  };
+  if (have_beam) {
+    // pruned lattices, whole device batches of utterances (crf_bunch_size of them, default 256)
+    const size_t bunch = (size_t)std::max(1L, a.num("crf_bunch_size", 256));
+    crf_amd::ArcListFst id;   // the label file's best path: ShortestPath over the pruned machine alone
+    id.n_states = 1; id.start = 0; id.SetFinal(0, 0.0f);
+    for (uint32_t l = 1; l <= m.L * m.D; l++) id.arcs.push_back(scrf_arc{0, (int)l, (int)l, 0.0f, 0});
+    uint64_t kept = 0, full = 0;
+    bool at_end = strm.nextseg() == QN_SEGID_BAD;
+    while (!at_end) {
+      std::vector<crf_amd::ArcListFst> lats;
+      try {
+        uint64_t nf = 0;
+        crf_amd_pruned_lattices(&strm, &crf, bunch, lat_beam, &lats, nullptr, &nf, &at_end);
+        full += nf;
+      } catch (std::exception& e) {
+        std::cerr << "Exception: " << e.what() << std::endl;
+        return -1;
+      }
+      for (const crf_amd::ArcListFst& fst : lats) {
+        kept += fst.arcs.size();
+        try {
+          if (a.has("crf_lat_outdir")) dump_lattice(fst, u);
+          if (want_mlf) write_mlf(fst, sents[u]);
+          crf_amd::ArcListFst best;
+          float total = 0;
+          std::vector<uint32_t> labs;
+          if (crf_amd::composeShortestPath(fst, id, &best, &total))
+            for (const scrf_arc& c : best.arcs) { if (c.olabel != 0) labs.push_back((uint32_t)(c.olabel - 1)); }
+          emit(labs);
+        } catch (std::exception& e) {
+          std::cerr << "Exception: " << e.what() << std::endl;
+          emit(std::vector<uint32_t>());
+        }
+      }
+    }
+    std::cout << "Lattice beam " << lat_beam << ": kept " << kept << " of " << full << " arcs" << std::endl;
+  } else if (!a.has("crf_lat_outdir") && !want_mlf && !align_mode) {
     // best paths only: whole device batches of utterances (crf_bunch_size of them, default 256)
     const size_t bunch = (size_t)std::max(1L, a.num("crf_bunch_size", 256));
     std::ofstream conf;
@@ -339,14 +402,7 @@ int main(int argc, char** argv) {
         crf_amd::ArcListFst fst, lab_fst;
         CRF_LatticeBuilder lb(&strm, &crf);
         lb.buildLattice(&fst, align_mode, align_mode ? &lab_fst : (crf_amd::ArcListFst*)nullptr, false);
-        if (a.has("crf_lat_outdir")) {
-          // the reference writes the lattice as an OpenFST binary, fst.<n>.final.fst (:832-837); here that file
-          // (layout unpinned, crf_amd.h) plus the same arcs as text
-          crf_amd::writeFstBinary((a.str("crf_lat_outdir") + "/fst." + std::to_string(u) + ".final.fst").c_str(), fst);
-          std::ofstream lf((a.str("crf_lat_outdir") + "/fst." + std::to_string(u) + ".txt").c_str());
-          for (const scrf_arc& c : fst.arcs) lf << c.src << " " << c.dst << " " << c.ilabel << " " << c.olabel << " " << c.w << "\n";
-          lf << fst.final_state << "\n";
-        }
+        if (a.has("crf_lat_outdir")) dump_lattice(fst, u);
         if (want_mlf) write_mlf(fst, sents[u]);
         if (align_mode) {   // ShortestPath(Compose(lattice, labels)), Project(output), RmEpsilon: olabel - 1 per arc
           crf_amd::ArcListFst best;

@@ -385,6 +385,11 @@ void pruneFst(const ArcListFst& in, ArcListFst* out, float threshold);
 // kept); returns false and leaves the machine alone when it has a cycle.
 bool topSortFst(ArcListFst* fst);
 void writeFstBinary(const char* fname, const ArcListFst& fst, const char* arc_type = "standard");
+// A pruned arc list (scrf_lattice_pruned_arcs: full-lattice state ids, arcs in the full lattice's order) as a machine of its
+// own: states that no kept arc touches are dropped, the rest renumbered in ascending old id -- the start stays 0 and a
+// topological order stays one --, arcs keep their order, the final state gets final weight 0.  Zero arcs give an empty
+// machine (no states).  Pure host code (crf_lattice_prune.cpp).
+void compactLattice(const scrf_arc* arcs, size_t n, int32_t final_state, ArcListFst* out);
 
 }  // namespace crf_amd
 
@@ -627,6 +632,15 @@ size_t crf_amd_posteriors(CRF_FeatureStream* ftr_strm, CRF_Model* crf, size_t ma
                           std::vector<std::vector<double> >* frame_post, std::vector<std::vector<double> >* end_post,
                           std::vector<double>* zx, std::vector<std::vector<uint32_t> >* labels, std::vector<float>* costs,
                           std::vector<std::vector<double> >* seg_post, bool* at_end);
+
+// Beam-pruned lattices of the stream's CURRENT utterance and up to max_utts - 1 following ones: one device
+// batch, one scrf_lattice_prune_batch and one fetch, in the style of crf_amd_best_paths (the stream is advanced with
+// nextseg(); *at_end is set when it ran out).  lats[u] = compactLattice of utterance u's kept arcs (weights unnormalised, as
+// buildLattice(norm = false) gives them), best[u] the fp64 cost of its best path, *n_full_arcs the arcs of the batch's full
+// lattices.  Returns the number of utterances.  A model the engine refuses throws the engine's message.
+size_t crf_amd_pruned_lattices(CRF_FeatureStream* ftr_strm, CRF_Model* crf, size_t max_utts, double beam,
+                               std::vector<crf_amd::ArcListFst>* lats, std::vector<double>* best, uint64_t* n_full_arcs,
+                               bool* at_end);
 
 // lattice builders: same call as the reference's templates; the arcs come from the engine in
 // AddArc order and are replayed into the caller's FST object

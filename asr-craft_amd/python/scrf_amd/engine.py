@@ -388,6 +388,33 @@ class Engine:
                                              C.byref(na), C.byref(ns), C.byref(fin)))
         return arcs, ns.value, fin.value
 
+    def lattice_prune_batch(self, batch, beam):
+        """Beam-pruned lattices of every utterance (scrf_lattice_prune_batch): returns (arc_off [U + 1], the prefix sums of
+        the kept arcs, and best_cost [U] = the fp64 cost of the best path).  The arcs stay on the device: pruned_arcs."""
+        off = np.empty(batch.n + 1, dtype=np.uint64); best = np.empty(batch.n, dtype=np.float64)
+        self._chk(self.lib.scrf_lattice_prune_batch(self.h, batch.handle, C.c_double(beam), _p(off), _p(best)))
+        self._lp_off = (batch.handle.value, off)
+        return off, best
+
+    def pruned_arcs(self, batch, u0=0, n=None):
+        """kept arcs (ARC_DTYPE, full-lattice state ids) of utterances u0 .. u0 + n - 1 of the last lattice_prune_batch on
+        this batch, back to back (n=None: to the end of the batch)"""
+        if n is None:
+            n = batch.n - u0
+        lp = getattr(self, "_lp_off", None)
+        na = 0
+        if lp is not None and lp[0] == batch.handle.value and 0 <= u0 and u0 + n <= batch.n:
+            na = int(lp[1][u0 + n] - lp[1][u0])
+        arcs = np.zeros(na, dtype=ARC_DTYPE)
+        self._chk(self.lib.scrf_lattice_pruned_arcs(self.h, batch.handle, C.c_uint32(u0), C.c_uint32(n), _p(arcs), C.c_uint64(na)))
+        return arcs
+
+    def lattice_prune_stats(self):
+        """(scrf_lattice_prune_batch calls, chunks they ran) since create"""
+        a = C.c_uint64(); b = C.c_uint64()
+        self._chk(self.lib.scrf_lattice_prune_stats(self.h, C.byref(a), C.byref(b)))
+        return a.value, b.value
+
     def viterbi_batch(self, batch):
         """Best-path segment labels of every utterance and the path costs.  The labels come back as the C ABI delivers
         them -- one flat array and U + 1 offsets -- behind a sequence view (`RaggedLabels`): `labs[u]` is utterance u's

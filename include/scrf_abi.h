@@ -311,6 +311,32 @@ int scrf_seg_posteriors(scrf_handle h, scrf_batch b, uint32_t u, double* gamma);
  * split.  The two forms give bit-identical results; the counters let a test know which one ran. */
 int scrf_posterior_stats(scrf_handle h, uint64_t* n_split, uint64_t* n_whole);
 
+/* ---- beam-pruned lattices ----------------------------------------------------------------------- */
+/* The lattice of every utterance of the batch exactly as scrf_lattice_arcs(..., norm = 0, ...) defines it -- state ids, arc
+ * order (the reference's AddArc order), float weights w -- cut by a tropical beam in fp64.  With wd = (double)w:
+ *   fwd[0] = 0, fwd[s] = min over arcs into s of fwd[src] + wd;  bwd[final] = 0, bwd[s] = min over arcs out of s of wd + bwd[dst];
+ *   an arc is kept iff (fwd[src] + wd) + bwd[dst] <= fwd[final] + beam, in fp64 with exactly that association.
+ * min is exact and every + rounds once, so the kept set is defined bit for bit and does not depend on an evaluation order (OpenFST
+ * Prune's criterion in fp64 instead of float).  The kept arcs are a subsequence of the full arc list, and every kept arc lies on a
+ * complete path of kept arcs (the result is trim).  Sums of float weights of one magnitude are exact in fp64, so the best path has
+ * slack exactly 0 and is kept by any beam; a beam below the rounding of |best| (~1e-13 relative) does not formally guarantee it.
+ * beam must be finite and > 0.  Scores come from the EXACT path; the batch runs in chunks under scratch_bytes, the full lattice
+ * is never materialised, and only the kept arcs cross to the host.  They sit in one device array the handle owns outside
+ * scratch_bytes (20 bytes per kept arc); it grows geometrically, is kept for the next call and freed by scrf_destroy.
+ * Models: SCRF_STDFRAME, SCRF_STDSEG_NO_DUR_NO_TRANSFTR, SCRF_STDSEG_NO_DUR_NO_SEGTRANSFTR with num_states == 1 (dense and sparse
+ * maps, batches of frames or of windows); SCRF_STDSEG, SCRF_STDSEG_NO_DUR and num_states > 1 are refused (SCRF_ERR_INVALID). */
+/* beam-pruned lattices of every utterance of the batch; arc_off [n_utts+1] = prefix sums of the kept arcs,
+   best_cost [n_utts] (may be NULL) = fwd[final].  The arcs stay on the device until fetched. */
+int scrf_lattice_prune_batch(scrf_handle h, scrf_batch b, double beam, uint64_t* arc_off, double* best_cost);
+/* kept arcs of utterances u0 .. u0+n-1 of the last scrf_lattice_prune_batch on this batch, back to back,
+   full-lattice state ids (n_states / final_state: scrf_lattice_arcs with arcs == NULL).  The handle holds ONE result, tied to the
+   batch and the weights it was computed from: scrf_set_lambda, scrf_sgd_step, destroying that batch or another prune call drop
+   it.  Without a valid result, with u0 + n > n_utts or with cap (in arcs) too small: SCRF_ERR_INVALID, the message names the
+   count needed. */
+int scrf_lattice_pruned_arcs(scrf_handle h, scrf_batch b, uint32_t u0, uint32_t n, scrf_arc* arcs, uint64_t cap);
+/* calls and chunks run since scrf_create (lets a test know that a batch really went through several chunks) */
+int scrf_lattice_prune_stats(scrf_handle h, uint64_t* n_calls, uint64_t* n_chunks);
+
 /* ---- minibatch reduce + optimizer ------------------------------------------------------------ */
 /* replaces the join/sum/average of CRF_Minibatch_GradAccumulator::accumulateGradient
  * (trainers/accumulators/CRF_Minibatch_GradAccumulator.cpp:277-312): all-reduce (sum) of the
@@ -368,7 +394,7 @@ int scrf_sgd_step(scrf_handle h, double lr_or_eta, int use_adagrad, double eps);
  * kernel (the three that dominate a step). */
 #define SCRF_N_PHASES 10
 int scrf_last_timing(scrf_handle h, float* ms, uint32_t* n_launch);
-/* HIP-event time of every kernel of the last timed scrf_fb_batch / scrf_posteriors_batch / scrf_viterbi_batch, one line per kernel
+/* HIP-event time of every kernel of the last timed scrf_fb_batch / scrf_posteriors_batch / scrf_viterbi_batch / scrf_lattice_prune_batch, one line per kernel
  * name: "name\tmilliseconds\tlaunches\n" (events recorded on the stream the kernel is launched on) */
 int scrf_kernel_timing(scrf_handle h, char* buf, size_t cap);
 int scrf_enable_timing(scrf_handle h, int on);
