@@ -630,17 +630,18 @@ extern "C" int scrf_take_batch_sums(scrf_handle h, double* sums3) {
 // ---------------------------------------------------------------------------------------------
 // scratch arena
 // ---------------------------------------------------------------------------------------------
+static size_t pad256(size_t b) { return (b + 255) & ~(size_t)255; }
+// A null base is the measuring mode: take() advances `off` by the same padded amounts and hands out nullptr, so the walk
+// that carves a chunk's buffers also gives the chunk's size (its final `off`) -- the layout is written once.
 struct Arena {
   char* base;
   size_t cap, off;
   template <class Tp> Tp* take(size_t n) {
-    size_t bytes = (n * sizeof(Tp) + 255) & ~(size_t)255;
-    Tp* p = (Tp*)(base + off);
-    off += bytes;
+    Tp* p = base ? (Tp*)(base + off) : nullptr;
+    off += pad256(n * sizeof(Tp));
     return p;
   }
 };
-static size_t pad256(size_t b) { return (b + 255) & ~(size_t)255; }
 
 static int ensure_scratch(scrf_handle h, size_t bytes, int lane = 0) {
   char*& buf = lane ? h->scratch2 : h->scratch;
@@ -1141,99 +1142,13 @@ static ScrfGemmSpec spec_dense_x(const ScrfLayout& l, uint32_t W) {   // the who
   return ScrfGemmSpec{0, 0, 3 * W + l.D, (uint32_t)l.use_sb, l.sbv, 5 * W, 0};
 }
 
-static size_t chunk_bytes(scrf_handle h, scrf_batch b, uint64_t nutt, uint64_t nfr, uint64_t nseg, const Need& nd) {
-  const ScrfLayout& l = h->lay;
-  const size_t LL = (size_t)l.L * l.L;
-  size_t tot = 0;
-  const uint32_t W0 = b->mode == 1 ? b->recipe[0].in_width : 0;
-  if (nd.fused) {
-    const size_t ng = nd.la ? 6 : 5;
-    tot += pad256(nfr * ng * l.L * sizeof(double));                // P (scores) / Z (counts)
-    if (nd.post) tot += pad256((size_t)512 * ng * l.L * W0 * sizeof(double));
-    if (b->mixed) tot += pad256(nseg * l.F * sizeof(float));     // the transition streams' windows
-  } else if (b->mode == 1) tot += pad256(nseg * (nd.hybrid ? hybrid_row_floats(l, W0) : l.F) * sizeof(float));
-  if (nd.hybrid) tot += pad256(nfr * 5 * l.L * sizeof(double)) + pad256((size_t)512 * 5 * l.L * W0 * sizeof(double)) +   // P / Z, slab_l
-                        pad256((size_t)(nutt + 1024) * l.L * (l.D + 1) * sizeof(double));                                 // per-duration sums
-  if (nd.vitfast) tot += pad256(nseg * l.L * sizeof(float)) + pad256((size_t)decode_fix_cap(nseg, l.L) * 8) + 256;  // Wn, list, count
-  else tot += pad256(nseg * l.L * sizeof(double));                  // S
-  if (segtrans(h)) tot += pad256(nseg * LL * sizeof(double));               // M2: one matrix per window
-  else if (l.use_tf) tot += pad256(nfr * LL * sizeof(double)) + pad256(nfr * 8);  // M, xrow_cur
-  if (nd.fb) {
-    const bool wave = wave_path(h, need_lin(nd));
-    if (wave && need_lin(nd) && h->lin_dp) {
-      // scaled linear-domain recursion: no alpha-with-duration array
-      tot += pad256(nseg * sizeof(double)) + pad256(nfr * sizeof(double));               // smax, s_true
-      tot += 4 * pad256(nfr * l.L * sizeof(double)) + 4 * pad256(nfr * sizeof(double));  // a, p, b, sd + log-scales
-    } else {
-      tot += pad256(nseg * l.L * sizeof(double));                     // AD
-      tot += pad256(nfr * l.L * sizeof(double));                      // alpha
-      if (nd.beta || wave || segtrans(h)) tot += pad256(nfr * l.L * sizeof(double));
-      if (wave) tot += pad256(nfr * l.L * sizeof(double));            // sd
-      if (wave && nd.post) tot += 2 * pad256(nfr * l.L * sizeof(double));  // A, B
-    }
-    if (wave) {
-      if (l.use_tf) tot += 2 * pad256(nfr * LL * sizeof(double)) + pad256(nfr * sizeof(double));  // E, ET, shift
-      if (nd.post) {
-        tot += pad256(nfr * sizeof(double));                          // numer_f
-        if (!l.use_tf) tot += pad256(((nfr + atb_rows_per_chunk(nfr) - 1) / atb_rows_per_chunk(nfr)) * LL * sizeof(double));
-      }
-    }
-    if (nd.ponly) tot += (1 + (size_t)(post_occ_groups(l) > 1 ? post_occ_groups(l) : 0)) * pad256(nfr * sizeof(double));   // mass_s + its per-group parts
-    if (nd.post) {
-      tot += pad256(nfr * sizeof(double));                            // mass_s
-      if (segtrans(h)) {
-        tot += pad256(nseg * LL * sizeof(double));                    // XI2
-        tot += pad256((size_t)segtrans_chunks(nseg, LL, l.ntf) * LL * l.ntf * sizeof(double));
-      } else if (l.use_tf && sparse(h)) {
-        tot += pad256(nfr * LL * sizeof(double)) + pad256(nfr * 8);  // XI, xrow_next
-      } else if (l.use_tf) {
-        tot += pad256(nfr * LL * sizeof(double)) + pad256(nfr * 8);  // XI, xrow_next
-        uint32_t nch_t = transframe_chunks(nfr, (uint32_t)LL, scrf_spec_trans(l).nfun(), h->cfg.train_precision == SCRF_PREC_FAST32);
-        tot += pad256((size_t)nch_t * LL * l.ntf * sizeof(double));
-      } else if (!wave_path(h, nd.post)) {
-        tot += pad256(nutt * LL * sizeof(double));
-      }
-      if (sparse(h)) {
-        tot += sparse_counts_bytes(nseg, l.F, l.nsfe, l.L);
-        if (l.use_tf) tot += sparse_counts_bytes(nfr, l.F, l.ntfe, (uint32_t)LL);
-      } else {
-        const uint64_t rpc_s = expf_rows_per_chunk(nseg);
-        uint64_t nch_s = nd.fused ? 512 : (nseg + rpc_s - 1) / rpc_s;
-        tot += pad256(nch_s * l.L * l.nsf * sizeof(double));
-      }
-    }
-  }
-  if (nd.vit) tot += 2 * pad256(nfr * l.L * sizeof(uint16_t));
-  if (nd.lat) tot += 4 * pad256(nfr * l.L * sizeof(double)) + pad256((nfr + nutt) * sizeof(uint32_t)) + pad256((nfr + nutt + 1) * sizeof(uint64_t));
-  return tot + 4096;
-}
-
-static uint64_t l_F2(scrf_handle h) { return h->lay.F / 2; }
-// largest u1 > u0 whose chunk fits the budget (always at least one utterance)
-static uint32_t plan_chunk(scrf_handle h, scrf_batch b, uint32_t u0, const Need& nd) {
-  uint32_t u1 = u0 + 1;
-  const uint32_t max_utts = 65535;  // grid.x of the per-frame kernels stays small enough anyway
-  while (u1 < b->U && u1 - u0 < max_utts) {
-    uint64_t nfr = b->frame_off[u1 + 1] - b->frame_off[u0], nseg = b->seg_off[u1 + 1] - b->seg_off[u0];
-    if (chunk_bytes(h, b, u1 + 1 - u0, nfr, nseg, nd) > h->cfg.scratch_bytes) break;
-    if (nfr > 0x7fffffffull) break;
-    if (sparse(h) && nseg * (l_F2(h)) > 0xffffffffull) break;   // the sparse index's entry positions are 32-bit
-    u1++;
-  }
-  return u1;
-}
-
-static int carve(scrf_handle h, scrf_batch b, uint32_t u0, uint32_t u1, const Need& nd, ChunkBufs* cb, int lane = 0) {
+// The scratch layout of chunk [u0, u1) under `nd`, written once: every buffer of the chunk is taken from `a` in a fixed order
+// and recorded in *cb.  On a measuring arena the same walk sizes the chunk (chunk_size, the planner); on the lane's scratch
+// it carves it (carve).  A new buffer is one more take here.
+static void chunk_layout(scrf_handle h, scrf_batch b, uint32_t u0, uint32_t u1, const Need& nd, Arena& a, ChunkBufs* cb) {
   const ScrfLayout& l = h->lay;
   const size_t LL = (size_t)l.L * l.L;
   const uint64_t nutt = u1 - u0, nfr = b->frame_off[u1] - b->frame_off[u0], nseg = b->seg_off[u1] - b->seg_off[u0];
-  size_t need = chunk_bytes(h, b, nutt, nfr, nseg, nd);
-  int rc = ensure_scratch(h, need, lane);
-  if (rc != SCRF_OK) return rc;
-  Arena a{lane ? h->scratch2 : h->scratch, lane ? h->scratch2_cap : h->scratch_cap, 0};
-  cb->st = lane ? h->stream2 : h->stream;
-  cb->grad = lane ? h->d_grad2 : h->d_grad;
-  cb->sums = lane ? h->d_sums2 : h->d_sums;
   if (nd.fused) {
     const uint32_t W0 = b->recipe[0].in_width;
     cb->X = b->mixed ? a.take<float>(nseg * l.F) : nullptr;
@@ -1320,7 +1235,11 @@ static int carve(scrf_handle h, scrf_batch b, uint32_t u0, uint32_t u1, const Ne
     }
     if (nd.ponly) {
       cb->mass_s = a.take<double>(nfr);
-      if (post_occ_groups(l) > 1) cb->mass_part = a.take<double>(nfr * post_occ_groups(l));
+      // [groups][nfr], read as one array; sized one padded row per group, as the planner has always counted it
+      if (post_occ_groups(l) > 1) {
+        cb->mass_part = a.take<double>(nfr);
+        for (uint32_t g = 1; g < post_occ_groups(l); g++) a.take<double>(nfr);
+      }
     }
     if (nd.post) {
       cb->mass_s = a.take<double>(nfr);
@@ -1329,34 +1248,34 @@ static int carve(scrf_handle h, scrf_batch b, uint32_t u0, uint32_t u1, const Ne
         cb->nch_t = segtrans_chunks(nseg, LL, l.ntf);
         cb->rpc_t = (nseg + cb->nch_t - 1) / cb->nch_t;
         cb->slab_t = a.take<double>((size_t)cb->nch_t * LL * l.ntf);
-      } else if (l.use_tf && sparse(h)) {
-        cb->XI = a.take<double>(nfr * LL);
-        cb->xrow_next = a.take<uint64_t>(nfr);
       } else if (l.use_tf) {
         cb->XI = a.take<double>(nfr * LL);
         cb->xrow_next = a.take<uint64_t>(nfr);
-        cb->nch_t = transframe_chunks(nfr, (uint32_t)LL, scrf_spec_trans(l).nfun(), h->cfg.train_precision == SCRF_PREC_FAST32);
-        cb->rpc_t = (nfr + cb->nch_t - 1) / cb->nch_t;
-        cb->slab_t = a.take<double>((size_t)cb->nch_t * LL * l.ntf);
+        if (!sparse(h)) {   // the sparse transition counts have their own slab (below)
+          cb->nch_t = transframe_chunks(nfr, (uint32_t)LL, scrf_spec_trans(l).nfun(), h->cfg.train_precision == SCRF_PREC_FAST32);
+          cb->rpc_t = (nfr + cb->nch_t - 1) / cb->nch_t;
+          cb->slab_t = a.take<double>((size_t)cb->nch_t * LL * l.ntf);
+        }
       } else if (!cb->wave) {
         cb->xi_acc = a.take<double>(nutt * LL);
       }
       if (sparse(h)) {
-        sparse_counts_carve(a.take<char>(sparse_counts_bytes(nseg, l.F, l.nsfe, l.L)), nseg, l.F, l.nsfe, l.L, &cb->spx[0]);
-        if (l.use_tf) sparse_counts_carve(a.take<char>(sparse_counts_bytes(nfr, l.F, l.ntfe, (uint32_t)LL)), nfr, l.F, l.ntfe, (uint32_t)LL, &cb->spx[1]);
+        char* sp = a.take<char>(sparse_counts_bytes(nseg, l.F, l.nsfe, l.L));
+        if (sp) sparse_counts_carve(sp, nseg, l.F, l.nsfe, l.L, &cb->spx[0]);
+        sp = l.use_tf ? a.take<char>(sparse_counts_bytes(nfr, l.F, l.ntfe, (uint32_t)LL)) : nullptr;
+        if (sp) sparse_counts_carve(sp, nfr, l.F, l.ntfe, (uint32_t)LL, &cb->spx[1]);
       }
       cb->rpc_s = expf_rows_per_chunk(nseg);
       cb->nch_s = (uint32_t)((nseg + cb->rpc_s - 1) / cb->rpc_s);
-      ScrfFusedExpfPlan plan;
-      if (nd.fused) {
-        plan = fused_expf_plan(l, b->recipe[0].in_width, h->cfg.train_precision == SCRF_PREC_FAST32, nd.la);
+      if (!sparse(h)) cb->slab_s = a.take<double>((size_t)(nd.fused ? 512 : cb->nch_s) * l.L * l.nsf);
+      if (nd.fused && cb->slab_s) {   // the fused count kernel's plan lives inside its 512 slabs: nothing of it is measured
+        const ScrfFusedExpfPlan plan = fused_expf_plan(l, b->recipe[0].in_width, h->cfg.train_precision == SCRF_PREC_FAST32, nd.la);
         cb->expf_tiles = plan.tile_list;
         cb->nch_s = fused_expf_blocks(l, b->recipe[0].in_width, h->cfg.train_precision == SCRF_PREC_FAST32,
                                       b->tile_off[plan.tile_list][u1] - b->tile_off[plan.tile_list][u0], nd.la);
+        // dense columns + durations + bias <= nsf: the duration slab fits behind the dense one
+        cb->slab_d = cb->slab_s + (size_t)cb->nch_s * l.L * plan.ncol;
       }
-      if (!sparse(h)) cb->slab_s = a.take<double>((size_t)(nd.fused ? 512 : cb->nch_s) * l.L * l.nsf);
-      // dense columns + durations + bias <= nsf: the duration slab fits behind the dense one
-      if (nd.fused) cb->slab_d = cb->slab_s + (size_t)cb->nch_s * l.L * plan.ncol;
     }
   }
   if (nd.vit) {
@@ -1369,6 +1288,38 @@ static int carve(scrf_handle h, scrf_batch b, uint32_t u0, uint32_t u1, const Ne
     cb->lat_counts = a.take<uint32_t>(nfr + nutt);
     cb->lat_node_off = a.take<uint64_t>(nfr + nutt + 1);
   }
+}
+
+// (*tmp takes the walk's pointers, which a measurement does not use: the planner passes the same one for every candidate)
+static size_t chunk_size(scrf_handle h, scrf_batch b, uint32_t u0, uint32_t u1, const Need& nd, ChunkBufs* tmp) {
+  Arena m{nullptr, 0, 0};
+  chunk_layout(h, b, u0, u1, nd, m, tmp);
+  return m.off + 4096;
+}
+
+// largest u1 > u0 whose chunk fits the budget (always at least one utterance)
+static uint32_t plan_chunk(scrf_handle h, scrf_batch b, uint32_t u0, const Need& nd) {
+  uint32_t u1 = u0 + 1;
+  const uint32_t max_utts = 65535;  // grid.x of the per-frame kernels stays small enough anyway
+  ChunkBufs tmp;
+  while (u1 < b->U && u1 - u0 < max_utts) {
+    uint64_t nfr = b->frame_off[u1 + 1] - b->frame_off[u0], nseg = b->seg_off[u1 + 1] - b->seg_off[u0];
+    if (chunk_size(h, b, u0, u1 + 1, nd, &tmp) > h->cfg.scratch_bytes) break;
+    if (nfr > 0x7fffffffull) break;
+    if (sparse(h) && nseg * (h->lay.F / 2) > 0xffffffffull) break;   // the sparse index's entry positions are 32-bit
+    u1++;
+  }
+  return u1;
+}
+
+static int carve(scrf_handle h, scrf_batch b, uint32_t u0, uint32_t u1, const Need& nd, ChunkBufs* cb, int lane = 0) {
+  int rc = ensure_scratch(h, chunk_size(h, b, u0, u1, nd, cb), lane);
+  if (rc != SCRF_OK) return rc;
+  Arena a{lane ? h->scratch2 : h->scratch, lane ? h->scratch2_cap : h->scratch_cap, 0};
+  cb->st = lane ? h->stream2 : h->stream;
+  cb->grad = lane ? h->d_grad2 : h->d_grad;
+  cb->sums = lane ? h->d_sums2 : h->d_sums;
+  chunk_layout(h, b, u0, u1, nd, a, cb);
   if (a.off > a.cap) return fail(h, SCRF_ERR_INVALID, "internal: scratch arena overflow");
   return SCRF_OK;
 }
@@ -1413,6 +1364,23 @@ struct KernelTimer {
 };
 #define KT_RUN(name, st, ...) do { KernelTimer kt_(h, name, st); __VA_ARGS__; kt_.stop(); } while (0)
 
+// the bracket of a timed batch call (scrf_enable_timing): clears the phase and kernel times, then times the whole call on
+// the engine stream; each entry point closes it where its timed region ends
+struct CallTimer {
+  scrf_handle h;
+  explicit CallTimer(scrf_handle h_) : h(h_) {
+    if (!h->timing) return;
+    memset(h->ms, 0, sizeof(h->ms)); memset(h->nlaunch, 0, sizeof(h->nlaunch)); h->ktimes.clear();
+    hipEventRecord(h->ev[SCRF_N_PHASES][0], h->stream);
+  }
+  void stop() {
+    if (!h->timing) return;
+    hipEventRecord(h->ev[SCRF_N_PHASES][1], h->stream);
+    hipEventSynchronize(h->ev[SCRF_N_PHASES][1]);
+    hipEventElapsedTime(&h->ms[PH_ALL], h->ev[SCRF_N_PHASES][0], h->ev[SCRF_N_PHASES][1]);
+  }
+};
+
 static ScrfFusedArgs fused_args(scrf_handle h, scrf_batch b, uint32_t u0, int which) {
   ScrfFusedArgs fa;
   memset(&fa, 0, sizeof(fa));
@@ -1424,6 +1392,46 @@ static ScrfFusedArgs fused_args(scrf_handle h, scrf_batch b, uint32_t u0, int wh
   fa.W = b->recipe[0].in_width;
   fa.TB = fused_scores_tb(fa.W, h->lay.D);
   return fa;
+}
+
+// window vectors of chunk [u0, u1) into X, stream by stream (batches made from frames).  skip0: stream 0 is synthesised
+// inside the fused kernels; hybrid: rows of hybrid_row_floats without the sampled blocks
+static void launch_chunk_windows(scrf_handle h, scrf_batch b, uint32_t u0, uint32_t u1, hipStream_t st, float* X, bool skip0 = false,
+                                 bool fast = false, bool hybrid = false) {
+  const ScrfLayout& l = h->lay;
+  const uint64_t nfr = b->frame_off[u1] - b->frame_off[u0];
+  ScrfBatchView bv = b->view();
+  uint32_t col = 0;
+  for (uint32_t s = 0; s < b->n_streams; col += b->width[s++]) {
+    const scrf_stream_recipe& r = b->recipe[s];
+    if (skip0 && s == 0) continue;
+    // FAST training path with per-frame transition features: a stream whose columns hold no state feature is read through
+    // the frame rows (k_frame_rows: the node's first window) only -- its other window rows are not written (the TIMIT
+    // demo's +-6-frame context stream: 5.8 GB of the 9.3 GB window image).  The window hook (scrf_windows) and EXACT
+    // precision materialise every row.
+    const bool first_only = fast && !sparse(h) && l.use_tf && !segtrans(h) && l.D > 1 && (col > l.sfe || col + b->width[s] <= l.sfs);
+    KT_RUN("k_windows", st, launch_windows(st, b->d_frames[s], b->d_sframe_off[s], bv, u0, u1, nfr, r.in_width, l.D, r.left_ctx, r.right_ctx,
+                                           r.extract_seg_ftr, X, hybrid ? hybrid_row_floats(l, r.in_width) : l.F, col,
+                                           (first_only ? 1 : 0) | (hybrid ? 2 : 0)));
+  }
+}
+
+// bias-only transitions: the one L x L matrix of every frame (the bias value) and its exponential, unless the current
+// weights' are there already; true when it was launched.  No feature is read (ntfe = 0), so no window pointer is passed.
+static bool ensure_m0(scrf_handle h, hipStream_t st) {
+  if (h->m0_valid) return false;
+  const ScrfLayout& l = h->lay;
+  launch_scores_exact(st, nullptr, l.F, nullptr, 1, h->d_lambda, l, 1, l.L * l.L, h->d_m0);
+  launch_exp_m(st, h->d_m0, l.L, 1, h->d_e0, h->d_et0, h->d_msh0);
+  h->m0_valid = true;
+  return true;
+}
+
+// sparse maps: lambda index-major, once per batch call on the engine stream (before the lanes fork): every chunk's score
+// kernel reads it
+static void relay_sparse_lambda(scrf_handle h, hipStream_t st) {
+  launch_sp_relay(st, h->d_lambda, h->lay, 0, h->d_lamT[0]);
+  if (h->lay.use_tf) launch_sp_relay(st, h->d_lambda, h->lay, 1, h->d_lamT[1]);
 }
 
 // windows + exact scores of a chunk (both training and decode start here)
@@ -1491,20 +1499,7 @@ static int run_scores(scrf_handle h, scrf_batch b, uint32_t u0, uint32_t u1, Chu
   }
   if (b->mode == 1) {
     PhaseTimer tm(h, PH_WIN, cb.st);
-    uint32_t col = 0;
-    for (uint32_t s = 0; s < b->n_streams; s++) {
-      const scrf_stream_recipe& r = b->recipe[s];
-      if (cb.fused && s == 0) { col += b->width[s]; continue; }   // stream 0 is synthesised inside the fused kernels
-      // FAST training path with per-frame transition features: a stream whose columns hold no state feature is read through
-      // the frame rows (k_frame_rows: the node's first window) only -- its other window rows are not written (the TIMIT
-      // demo's +-6-frame context stream: 5.8 GB of the 9.3 GB window image).  The window hook (scrf_windows) and EXACT
-      // precision materialise every row.
-      const bool first_only = fast && !sparse(h) && l.use_tf && !segtrans(h) && l.D > 1 && (col > l.sfe || col + b->width[s] <= l.sfs);
-      KT_RUN("k_windows", cb.st, launch_windows(cb.st, b->d_frames[s], b->d_sframe_off[s], bv, u0, u1, nfr, r.in_width, l.D, r.left_ctx,
-                     r.right_ctx, r.extract_seg_ftr, cb.X, cb.hybrid ? hybrid_row_floats(l, r.in_width) : l.F, col,
-                     (first_only ? 1 : 0) | (cb.hybrid ? 2 : 0)));
-      col += b->width[s];
-    }
+    launch_chunk_windows(h, b, u0, u1, cb.st, cb.X, cb.fused, fast, cb.hybrid);
     tm.stop(b->n_streams);
   }
   PhaseTimer tm(h, PH_SCORE, cb.st);
@@ -1543,12 +1538,7 @@ static int run_scores(scrf_handle h, scrf_batch b, uint32_t u0, uint32_t u1, Chu
     tk.stop(1);
   }
   if (sparse(h)) {
-    if (!l.use_tf && !h->m0_valid) {   // bias-only transitions: the dense path's M0 (the bias value is 1 here)
-      launch_scores_exact(cb.st, cb.X, l.F, nullptr, 1, h->d_lambda, l, 1, l.L * l.L, h->d_m0);
-      launch_exp_m(cb.st, h->d_m0, l.L, 1, h->d_e0, h->d_et0, h->d_msh0);
-      h->m0_valid = true;
-      nl += 2;
-    }
+    if (!l.use_tf && ensure_m0(h, cb.st)) nl += 2;   // the dense path's M0 (the bias value is 1 here)
   } else if (segtrans(h)) {
     // one transition matrix per window: the same contraction over every row of X; the rows of the
     // utterance-initial segments (no predecessor) are zeroed like the reference leaves them unused
@@ -1561,13 +1551,7 @@ static int run_scores(scrf_handle h, scrf_batch b, uint32_t u0, uint32_t u1, Chu
     if (fast) KT_RUN("k_scores_mfma(trans)", cb.st, launch_scores_mfma(cb.st, cb.X, l.F, cb.xrow_cur, nfr, h->d_lambda, l, scrf_spec_trans(l), l.L * l.L, cb.M, f32));
     else KT_RUN("k_scores_exact(trans)", cb.st, launch_scores_exact(cb.st, cb.X, l.F, cb.xrow_cur, nfr, h->d_lambda, l, 1, l.L * l.L, cb.M));
     nl += 2;
-  } else if (!h->m0_valid && !segtrans(h)) {
-    // transition scores carry only the bias: one L x L matrix for every frame
-    launch_scores_exact(cb.st, cb.X, l.F, nullptr, 1, h->d_lambda, l, 1, l.L * l.L, h->d_m0);
-    launch_exp_m(cb.st, h->d_m0, l.L, 1, h->d_e0, h->d_et0, h->d_msh0);
-    h->m0_valid = true;
-    nl += 2;
-  }
+  } else if (ensure_m0(h, cb.st)) nl += 2;
   tm.stop(nl);
   HIPCHK(h, hipGetLastError());
   return SCRF_OK;
@@ -1747,15 +1731,26 @@ struct StdsegBufs {
   float* X; uint32_t *row_t, *row_d, *row_u;
   double *S, *MX, *alpha, *beta, *G, *XI, *mass_s, *mass_t;
 };
-static size_t stdseg_chunk_bytes(scrf_handle h, scrf_batch b, uint64_t nfr, uint64_t nseg, bool post) {
+// scratch layout of a chunk (one walk for sizing and carving, like chunk_layout)
+static void stdseg_layout(scrf_handle h, scrf_batch b, uint32_t u0, uint32_t u1, bool post, Arena& a, StdsegBufs* sb) {
   const ScrfLayout& l = h->lay;
   const uint32_t La = stdseg_La(h);
-  size_t tot = 0;
-  if (b->mode == 1) tot += pad256(nseg * l.F * sizeof(float));
-  tot += 3 * pad256(nseg * sizeof(uint32_t));
-  tot += 3 * pad256(nseg * La * sizeof(double)) + pad256(nseg * (size_t)l.L * La * sizeof(double));   // S, alpha, beta, MX
-  if (post) tot += pad256(nseg * La * sizeof(double)) + pad256(nseg * (size_t)l.L * La * sizeof(double)) + 2 * pad256(nfr * sizeof(double));
-  return tot;
+  const uint64_t nfr = b->frame_off[u1] - b->frame_off[u0], nseg = b->seg_off[u1] - b->seg_off[u0];
+  memset(sb, 0, sizeof(*sb));
+  sb->X = b->mode == 1 ? a.take<float>(nseg * l.F) : b->d_windows + b->seg_off[u0] * l.F;
+  sb->row_t = a.take<uint32_t>(nseg); sb->row_d = a.take<uint32_t>(nseg); sb->row_u = a.take<uint32_t>(nseg);
+  sb->S = a.take<double>(nseg * La); sb->alpha = a.take<double>(nseg * La); sb->beta = a.take<double>(nseg * La);
+  sb->MX = a.take<double>(nseg * (size_t)l.L * La);
+  if (post) {
+    sb->G = a.take<double>(nseg * La); sb->XI = a.take<double>(nseg * (size_t)l.L * La);
+    sb->mass_s = a.take<double>(nfr); sb->mass_t = a.take<double>(nfr);
+  }
+}
+static size_t stdseg_chunk_size(scrf_handle h, scrf_batch b, uint32_t u0, uint32_t u1, bool post) {
+  Arena m{nullptr, 0, 0};
+  StdsegBufs sb;
+  stdseg_layout(h, b, u0, u1, post, m, &sb);
+  return m.off;
 }
 // ---- STDSEG, bias-only transitions, FAST precisions, training path: scrf_stdseg_lin.hip
 static bool stdseg_lin(scrf_handle h) {
@@ -1766,79 +1761,76 @@ static uint64_t sl_rows_per_chunk(uint64_t nfr) {   // K-chunks of the count con
   uint64_t rpc = ((nfr + 255) / 256 + 31) & ~31ull;
   return rpc < 64 ? 64 : rpc;
 }
-static size_t stdseg_lin_chunk_bytes(scrf_handle h, scrf_batch b, uint64_t nfr, uint64_t nseg) {
+struct StdsegLinBufs {
+  float* X; uint64_t* xrow;
+  double *Sd, *Ad, *Bd, *Rd, *Bp, *Am, *ga, *numer_f;
+  double *slab_s, *slab_t, *obs;   // state-count slabs (one duration at a time), transition slabs, observed transitions
+  uint64_t rpc; uint32_t nch;
+};
+static void stdseg_lin_layout(scrf_handle h, scrf_batch b, uint32_t u0, uint32_t u1, Arena& a, StdsegLinBufs* sb) {
   const ScrfLayout& l = h->lay;
   const uint32_t La = stdseg_La(h);
-  const size_t node = pad256((size_t)l.D * nfr * La * sizeof(double));
-  const uint64_t nch = (nfr + sl_rows_per_chunk(nfr) - 1) / sl_rows_per_chunk(nfr);
-  size_t tot = 0;
-  if (b->mode == 1) tot += pad256(nseg * l.F * sizeof(float));
-  tot += pad256((size_t)l.D * nfr * sizeof(uint64_t));                // xrow
-  tot += 5 * node;                                                    // Sd, Ad, Bd, Rd, Bp
-  tot += pad256(nfr * (size_t)l.L * sizeof(double)) + 2 * pad256(nfr * sizeof(double));   // Am, ga, numer_f
-  tot += pad256(nch * (size_t)La * l.nsf * sizeof(double));           // state-count slabs (one duration at a time)
-  tot += pad256(nch * (size_t)l.L * l.L * sizeof(double)) + pad256((size_t)l.L * l.L * sizeof(double));   // transition slabs, observed
-  return tot + 4096;
+  const uint64_t nfr = b->frame_off[u1] - b->frame_off[u0], nseg = b->seg_off[u1] - b->seg_off[u0];
+  const size_t nn = (size_t)l.D * nfr * La;
+  sb->X = b->mode == 1 ? a.take<float>(nseg * l.F) : b->d_windows + b->seg_off[u0] * l.F;
+  sb->xrow = a.take<uint64_t>((size_t)l.D * nfr);
+  sb->Sd = a.take<double>(nn); sb->Ad = a.take<double>(nn); sb->Bd = a.take<double>(nn);
+  sb->Rd = a.take<double>(nn); sb->Bp = a.take<double>(nn);
+  sb->Am = a.take<double>(nfr * (size_t)l.L);
+  sb->ga = a.take<double>(nfr); sb->numer_f = a.take<double>(nfr);
+  sb->rpc = sl_rows_per_chunk(nfr);
+  sb->nch = (uint32_t)((nfr + sb->rpc - 1) / sb->rpc);
+  sb->slab_s = a.take<double>((size_t)sb->nch * La * l.nsf);
+  sb->slab_t = a.take<double>((size_t)sb->nch * l.L * l.L);
+  sb->obs = a.take<double>((size_t)l.L * l.L);
+}
+static size_t stdseg_lin_chunk_size(scrf_handle h, scrf_batch b, uint32_t u0, uint32_t u1) {
+  Arena m{nullptr, 0, 0};
+  StdsegLinBufs sb;
+  stdseg_lin_layout(h, b, u0, u1, m, &sb);
+  return m.off + 4096;
 }
 static int stdseg_lin_run_chunk(scrf_handle h, scrf_batch b, uint32_t u0, uint32_t u1, double* grad) {
   const ScrfLayout& l = h->lay;
   const uint32_t La = stdseg_La(h);
-  const uint64_t nfr = b->frame_off[u1] - b->frame_off[u0], nseg = b->seg_off[u1] - b->seg_off[u0];
-  int rc = ensure_scratch(h, stdseg_lin_chunk_bytes(h, b, nfr, nseg));
+  const uint64_t nfr = b->frame_off[u1] - b->frame_off[u0];
+  int rc = ensure_scratch(h, stdseg_lin_chunk_size(h, b, u0, u1));
   if (rc != SCRF_OK) return rc;
   Arena a{h->scratch, h->scratch_cap, 0};
+  StdsegLinBufs sb;
+  stdseg_lin_layout(h, b, u0, u1, a, &sb);
+  if (a.off > a.cap) return fail(h, SCRF_ERR_INVALID, "internal: scratch arena overflow");
   ScrfBatchView bv = b->view();
   hipStream_t st = h->stream;
   const int f32 = h->cfg.train_precision == SCRF_PREC_FAST32;
-  float* X;
-  if (b->mode == 1) {
-    X = a.take<float>(nseg * l.F);
-    uint32_t col = 0;
-    for (uint32_t s = 0; s < b->n_streams; s++) {
-      const scrf_stream_recipe& r = b->recipe[s];
-      KT_RUN("k_windows", st, launch_windows(st, b->d_frames[s], b->d_sframe_off[s], bv, u0, u1, nfr, r.in_width, l.D, r.left_ctx, r.right_ctx,
-                                             r.extract_seg_ftr, X, l.F, col));
-      col += b->width[s];
-    }
-  } else X = b->d_windows + b->seg_off[u0] * l.F;
-  const size_t nn = (size_t)l.D * nfr * La;
-  uint64_t* xrow = a.take<uint64_t>((size_t)l.D * nfr);
-  double* Sd = a.take<double>(nn); double* Ad = a.take<double>(nn); double* Bd = a.take<double>(nn);
-  double* Rd = a.take<double>(nn); double* Bp = a.take<double>(nn);
-  double* Am = a.take<double>(nfr * (size_t)l.L);
-  double* ga = a.take<double>(nfr); double* numer_f = a.take<double>(nfr);
-  const uint64_t rpc = sl_rows_per_chunk(nfr);
-  const uint32_t nch = (uint32_t)((nfr + rpc - 1) / rpc);
-  double* slab_s = a.take<double>((size_t)nch * La * l.nsf);
-  double* slab_t = a.take<double>((size_t)nch * l.L * l.L);
-  double* obs = a.take<double>((size_t)l.L * l.L);
-  if (a.off > a.cap) return fail(h, SCRF_ERR_INVALID, "internal: scratch arena overflow");
+  if (b->mode == 1) launch_chunk_windows(h, b, u0, u1, st, sb.X);
   // the transition table and its exponential (once per call: lambda may have changed)
   double* E = h->d_sl_tab; double* ET = E + (size_t)l.L * l.L; double* mmax = ET + (size_t)l.L * l.L;
   launch_sl_tables(st, l, h->d_lambda, E, ET, mmax);
-  launch_sl_rows(st, bv, b->d_frame_u, u0, nfr, l.D, xrow);
+  launch_sl_rows(st, bv, b->d_frame_u, u0, nfr, l.D, sb.xrow);
   {
     KernelTimer kt(h, "k_scores_mfma(state, per duration)", st);
     for (uint32_t d0 = 0; d0 < l.D; d0++) {
       const ScrfGemmSpec sp{0, l.sfs, l.nsfe, (uint32_t)l.use_sb, l.sbv, d0 * La * l.stride, 0};
-      launch_scores_mfma(st, X, l.F, xrow + (size_t)d0 * nfr, nfr, h->d_lambda, l, sp, La, Sd + (size_t)d0 * nfr * La, f32);
+      launch_scores_mfma(st, sb.X, l.F, sb.xrow + (size_t)d0 * nfr, nfr, h->d_lambda, l, sp, La, sb.Sd + (size_t)d0 * nfr * La, f32);
     }
     kt.stop(l.D);
   }
-  KT_RUN("k_sl_fb", st, launch_sl_fb(st, l, La, bv, u0, u1 - u0, nfr, Sd, E, ET, mmax, Ad, Bd, Am, ga, b->d_zx, b->d_status));
-  KT_RUN("k_sl_post", st, launch_sl_post(st, l, La, bv, b->d_frame_u, u0, u1 - u0, nfr, b->d_prev_lab, h->d_lambda, Sd, Ad, Bd, ga, b->d_zx, Rd, Bp,
-                                         numer_f, b->d_numer, b->d_status));
+  KT_RUN("k_sl_fb", st, launch_sl_fb(st, l, La, bv, u0, u1 - u0, nfr, sb.Sd, E, ET, mmax, sb.Ad, sb.Bd, sb.Am, sb.ga, b->d_zx, b->d_status));
+  KT_RUN("k_sl_post", st, launch_sl_post(st, l, La, bv, b->d_frame_u, u0, u1 - u0, nfr, b->d_prev_lab, h->d_lambda, sb.Sd, sb.Ad, sb.Bd, sb.ga, b->d_zx,
+                                         sb.Rd, sb.Bp, sb.numer_f, b->d_numer, b->d_status));
   {
     KernelTimer kt(h, "k_expf_mfma(state, per duration)", st);
     for (uint32_t d0 = 0; d0 < l.D; d0++) {
       const ScrfGemmSpec sp{0, l.sfs, l.nsfe, (uint32_t)l.use_sb, l.sbv, d0 * La * l.stride, 0};
-      launch_expf_mfma(st, Rd + (size_t)d0 * nfr * La, La, X, l.F, xrow + (size_t)d0 * nfr, nfr, l, sp, rpc, nch, slab_s, f32);
-      launch_reduce_slabs(st, slab_s, nch, La, l, sp, grad);
+      launch_expf_mfma(st, sb.Rd + (size_t)d0 * nfr * La, La, sb.X, l.F, sb.xrow + (size_t)d0 * nfr, nfr, l, sp, sb.rpc, sb.nch, sb.slab_s, f32);
+      launch_reduce_slabs(st, sb.slab_s, sb.nch, La, l, sp, grad);
     }
     kt.stop(2 * l.D);
   }
-  HIPCHK(h, hipMemsetAsync(obs, 0, sizeof(double) * l.L * l.L, st));
-  KT_RUN("k_sl_atb", st, launch_sl_trans_counts(st, l, La, bv, b->d_frame_u, u0, nfr, b->d_prev_lab, rpc, nch, Am, Bp, E, mmax, slab_t, obs, grad));
+  HIPCHK(h, hipMemsetAsync(sb.obs, 0, sizeof(double) * l.L * l.L, st));
+  KT_RUN("k_sl_atb", st, launch_sl_trans_counts(st, l, La, bv, b->d_frame_u, u0, nfr, b->d_prev_lab, sb.rpc, sb.nch, sb.Am, sb.Bp, E, mmax, sb.slab_t,
+                                                sb.obs, grad));
   HIPCHK(h, hipGetLastError());
   return SCRF_OK;
 }
@@ -1849,35 +1841,19 @@ static int stdseg_run_chunk(scrf_handle h, scrf_batch b, uint32_t u0, uint32_t u
   const ScrfLayout& l = h->lay;
   const uint32_t La = stdseg_La(h);
   const uint64_t nfr = b->frame_off[u1] - b->frame_off[u0], nseg = b->seg_off[u1] - b->seg_off[u0];
-  const size_t need = stdseg_chunk_bytes(h, b, nfr, nseg, post);
-  int rc = ensure_scratch(h, need);
+  int rc = ensure_scratch(h, stdseg_chunk_size(h, b, u0, u1, post));
   if (rc != SCRF_OK) return rc;
   Arena a{h->scratch, h->scratch_cap, 0};
   StdsegBufs sb;
-  memset(&sb, 0, sizeof(sb));
+  stdseg_layout(h, b, u0, u1, post, a, &sb);
+  if (a.off > a.cap) return fail(h, SCRF_ERR_INVALID, "internal: scratch arena overflow");
   ScrfBatchView bv = b->view();
   hipStream_t st = h->stream;
-  if (b->mode == 1) {
-    sb.X = a.take<float>(nseg * l.F);
-    uint32_t col = 0;
-    for (uint32_t s = 0; s < b->n_streams; s++) {
-      const scrf_stream_recipe& r = b->recipe[s];
-      launch_windows(st, b->d_frames[s], b->d_sframe_off[s], bv, u0, u1, nfr, r.in_width, l.D, r.left_ctx, r.right_ctx, r.extract_seg_ftr,
-                     sb.X, l.F, col);
-      col += b->width[s];
-    }
-  } else {
-    sb.X = b->d_windows + b->seg_off[u0] * l.F;
-  }
-  sb.row_t = a.take<uint32_t>(nseg); sb.row_d = a.take<uint32_t>(nseg); sb.row_u = a.take<uint32_t>(nseg);
-  sb.S = a.take<double>(nseg * La); sb.alpha = a.take<double>(nseg * La); sb.beta = a.take<double>(nseg * La);
-  sb.MX = a.take<double>(nseg * (size_t)l.L * La);
+  if (b->mode == 1) launch_chunk_windows(h, b, u0, u1, st, sb.X);
   launch_stdseg_rowinfo(st, bv, b->d_frame_u, u0, nfr, l.D, sb.row_t, sb.row_d, sb.row_u);
   KT_RUN("k_stdseg_scores", st, launch_stdseg_scores(st, l, La, sb.X, nseg, sb.row_t, sb.row_d, h->d_lambda, sb.S, sb.MX));
   KT_RUN("k_stdseg_fb", st, launch_stdseg_fb(st, l, La, bv, u0, u1 - u0, sb.S, sb.MX, sb.alpha, sb.beta, b->d_zx, b->d_status));
   if (post) {
-    sb.G = a.take<double>(nseg * La); sb.XI = a.take<double>(nseg * (size_t)l.L * La);
-    sb.mass_s = a.take<double>(nfr); sb.mass_t = a.take<double>(nfr);
     HIPCHK(h, hipMemsetAsync(sb.mass_s, 0, sizeof(double) * nfr, st));
     HIPCHK(h, hipMemsetAsync(sb.mass_t, 0, sizeof(double) * nfr, st));
     KT_RUN("k_stdseg_post", st, launch_stdseg_post(st, l, La, bv, u0, u1 - u0, nseg, sb.row_t, sb.row_d, sb.row_u, b->d_prev_lab, sb.S, sb.MX, sb.alpha, sb.beta,
@@ -1891,11 +1867,10 @@ static int stdseg_run_chunk(scrf_handle h, scrf_batch b, uint32_t u0, uint32_t u
 static uint32_t stdseg_plan_chunk(scrf_handle h, scrf_batch b, uint32_t u0, bool post) {
   uint32_t u1 = u0 + 1;
   if (post && stdseg_lin(h)) {
-    while (u1 < b->U && u1 - u0 < 32767 &&
-           stdseg_lin_chunk_bytes(h, b, b->frame_off[u1 + 1] - b->frame_off[u0], b->seg_off[u1 + 1] - b->seg_off[u0]) <= h->cfg.scratch_bytes) u1++;
+    while (u1 < b->U && u1 - u0 < 32767 && stdseg_lin_chunk_size(h, b, u0, u1 + 1) <= h->cfg.scratch_bytes) u1++;
     return u1;
   }
-  while (u1 < b->U && stdseg_chunk_bytes(h, b, b->frame_off[u1 + 1] - b->frame_off[u0], b->seg_off[u1 + 1] - b->seg_off[u0], post) <= h->cfg.scratch_bytes) u1++;
+  while (u1 < b->U && stdseg_chunk_size(h, b, u0, u1 + 1, post) <= h->cfg.scratch_bytes) u1++;
   return u1;
 }
 
@@ -1906,55 +1881,50 @@ static bool nstate(scrf_handle h) { return h->lay.K > 1; }
 struct NstateBufs {
   float* X;
   double *S, *TD, *TO, *TE, *alpha, *beta, *G, *XD, *XO, *XE, *mass_s, *mass_t;
+  double* slab;   // the gradient's frame-slice partials
 };
-static size_t nstate_chunk_bytes(scrf_handle h, scrf_batch b, uint64_t nfr, bool post) {
-  const ScrfLayout& l = h->lay;
-  const uint64_t P = l.L / l.K;
-  size_t tot = 0;
-  if (b->mode == 1) tot += pad256(nfr * l.F * sizeof(float));
-  tot += 5 * pad256(nfr * l.L * sizeof(double)) + pad256(nfr * P * P * sizeof(double));              // S, TD, TO, alpha, beta, TE
-  if (post) tot += 3 * pad256(nfr * l.L * sizeof(double)) + pad256(nfr * P * P * sizeof(double)) + 2 * pad256(nfr * sizeof(double)) +
-                   pad256((size_t)ns_expf_slices(nfr) * l.lambda_len * sizeof(double));   // + the gradient's frame-slice partials
-  return tot;
-}
-static int nstate_run_chunk(scrf_handle h, scrf_batch b, uint32_t u0, uint32_t u1, bool post, double* grad, NstateBufs* out) {
+static void nstate_layout(scrf_handle h, scrf_batch b, uint32_t u0, uint32_t u1, bool post, Arena& a, NstateBufs* nb) {
   const ScrfLayout& l = h->lay;
   const uint64_t P = l.L / l.K;
   const uint64_t nfr = b->frame_off[u1] - b->frame_off[u0];
-  int rc = ensure_scratch(h, nstate_chunk_bytes(h, b, nfr, post));
+  memset(nb, 0, sizeof(*nb));
+  nb->X = b->mode == 1 ? a.take<float>(nfr * l.F) : b->d_windows + b->seg_off[u0] * l.F;
+  nb->S = a.take<double>(nfr * l.L); nb->TD = a.take<double>(nfr * l.L); nb->TO = a.take<double>(nfr * l.L);
+  nb->alpha = a.take<double>(nfr * l.L); nb->beta = a.take<double>(nfr * l.L);
+  nb->TE = a.take<double>(nfr * P * P);
+  if (post) {
+    nb->G = a.take<double>(nfr * l.L); nb->XD = a.take<double>(nfr * l.L); nb->XO = a.take<double>(nfr * l.L);
+    nb->XE = a.take<double>(nfr * P * P);
+    nb->mass_s = a.take<double>(nfr); nb->mass_t = a.take<double>(nfr);
+    nb->slab = a.take<double>((size_t)ns_expf_slices(nfr) * l.lambda_len);
+  }
+}
+static size_t nstate_chunk_size(scrf_handle h, scrf_batch b, uint32_t u0, uint32_t u1, bool post) {
+  Arena m{nullptr, 0, 0};
+  NstateBufs nb;
+  nstate_layout(h, b, u0, u1, post, m, &nb);
+  return m.off;
+}
+static int nstate_run_chunk(scrf_handle h, scrf_batch b, uint32_t u0, uint32_t u1, bool post, double* grad, NstateBufs* out) {
+  const ScrfLayout& l = h->lay;
+  const uint64_t nfr = b->frame_off[u1] - b->frame_off[u0];
+  int rc = ensure_scratch(h, nstate_chunk_size(h, b, u0, u1, post));
   if (rc != SCRF_OK) return rc;
   Arena a{h->scratch, h->scratch_cap, 0};
   NstateBufs nb;
-  memset(&nb, 0, sizeof(nb));
+  nstate_layout(h, b, u0, u1, post, a, &nb);
+  if (a.off > a.cap) return fail(h, SCRF_ERR_INVALID, "internal: scratch arena overflow");
   ScrfBatchView bv = b->view();
   hipStream_t st = h->stream;
-  if (b->mode == 1) {
-    nb.X = a.take<float>(nfr * l.F);
-    uint32_t col = 0;
-    for (uint32_t s = 0; s < b->n_streams; s++) {
-      const scrf_stream_recipe& r = b->recipe[s];
-      launch_windows(st, b->d_frames[s], b->d_sframe_off[s], bv, u0, u1, nfr, r.in_width, l.D, r.left_ctx, r.right_ctx, r.extract_seg_ftr,
-                     nb.X, l.F, col);
-      col += b->width[s];
-    }
-  } else {
-    nb.X = b->d_windows + b->seg_off[u0] * l.F;
-  }
-  nb.S = a.take<double>(nfr * l.L); nb.TD = a.take<double>(nfr * l.L); nb.TO = a.take<double>(nfr * l.L);
-  nb.alpha = a.take<double>(nfr * l.L); nb.beta = a.take<double>(nfr * l.L);
-  nb.TE = a.take<double>(nfr * P * P);
+  if (b->mode == 1) launch_chunk_windows(h, b, u0, u1, st, nb.X);
   KT_RUN("k_ns_scores", st, launch_ns_scores(st, l, nb.X, nfr, h->d_lambda, nb.S, nb.TD, nb.TO, nb.TE));
   KT_RUN("k_ns_fb", st, launch_ns_fb(st, l, bv, u0, u1 - u0, nb.S, nb.TD, nb.TO, nb.TE, nb.alpha, nb.beta, b->d_zx, b->d_status));
   if (post) {
-    nb.G = a.take<double>(nfr * l.L); nb.XD = a.take<double>(nfr * l.L); nb.XO = a.take<double>(nfr * l.L);
-    nb.XE = a.take<double>(nfr * P * P);
-    nb.mass_s = a.take<double>(nfr); nb.mass_t = a.take<double>(nfr);
     HIPCHK(h, hipMemsetAsync(nb.mass_s, 0, sizeof(double) * nfr, st));
     HIPCHK(h, hipMemsetAsync(nb.mass_t, 0, sizeof(double) * nfr, st));
     KT_RUN("k_ns_post", st, launch_ns_post(st, l, bv, b->d_frame_u, u0, u1 - u0, nfr, nb.S, nb.TD, nb.TO, nb.TE, nb.alpha, nb.beta, b->d_zx, nb.G, nb.XD, nb.XO,
                                            nb.XE, nb.mass_s, nb.mass_t, b->d_numer, b->d_status));
-    double* slab = a.take<double>((size_t)ns_expf_slices(nfr) * l.lambda_len);
-    KT_RUN("k_ns_expf", st, launch_ns_expf(st, l, bv, b->d_frame_u, u0, nfr, nb.X, nb.G, nb.XD, nb.XO, nb.XE, slab, grad));
+    KT_RUN("k_ns_expf", st, launch_ns_expf(st, l, bv, b->d_frame_u, u0, nfr, nb.X, nb.G, nb.XD, nb.XO, nb.XE, nb.slab, grad));
   }
   HIPCHK(h, hipGetLastError());
   if (out) *out = nb;
@@ -1962,8 +1932,30 @@ static int nstate_run_chunk(scrf_handle h, scrf_batch b, uint32_t u0, uint32_t u
 }
 static uint32_t nstate_plan_chunk(scrf_handle h, scrf_batch b, uint32_t u0, bool post) {
   uint32_t u1 = u0 + 1;
-  while (u1 < b->U && nstate_chunk_bytes(h, b, b->frame_off[u1 + 1] - b->frame_off[u0], post) <= h->cfg.scratch_bytes) u1++;
+  while (u1 < b->U && nstate_chunk_size(h, b, u0, u1 + 1, post) <= h->cfg.scratch_bytes) u1++;
   return u1;
+}
+
+// The form a batch's training and posterior passes take, by ingredient (scrf_batch_is_fused reports them as they are):
+// fusable: window synthesis inside the fused kernels (a training pass also needs a FAST precision for it); hybrid: materialised
+// dense statistics, sampled blocks through the per-frame projections; la: SCRF_PREC_FASTLIN on a shape whose kernels take the
+// linear window average -- it needs the fused kernels and the linear-domain recursion (k_post_z builds Z_avg), anything else
+// runs as FAST.  wave_path is false during a log-domain redo (force_fb), which therefore runs neither hybrid nor la.
+struct BatchForm { bool fusable, hybrid, la; };
+static BatchForm batch_form(scrf_handle h, scrf_batch b) {
+  const uint32_t prec = h->cfg.train_precision;
+  BatchForm f;
+  f.fusable = b->fused_ok && h->fuse_windows;
+  f.hybrid = !f.fusable && b->hybrid_ok && h->hybrid && h->fuse_windows && prec >= SCRF_PREC_FAST && prec != SCRF_PREC_FAST32 && h->lin_dp &&
+             wave_path(h, true);
+  f.la = prec == SCRF_PREC_FASTLIN && h->lin_dp && wave_path(h, true) && fused_la_supported(h->lay, b->recipe[0].in_width);
+  return f;
+}
+static void set_batch_form(scrf_handle h, scrf_batch b, Need* nd) {
+  const BatchForm f = batch_form(h, b);
+  nd->fused = f.fusable && h->cfg.train_precision >= SCRF_PREC_FAST;
+  nd->hybrid = f.hybrid;
+  nd->la = nd->fused && f.la;
 }
 
 // One pass of the forward-backward pipeline over the batch into the staging gradient.  latch[2] receives
@@ -2000,12 +1992,7 @@ static int fb_run(scrf_handle h, scrf_batch b, int latch[2], bool* used_lin) {
   ScrfBatchView bv = b->view();
   const bool fast = h->cfg.train_precision >= SCRF_PREC_FAST;
   const int f32 = h->cfg.train_precision == SCRF_PREC_FAST32;
-  nd.fused = fast && b->fused_ok && h->fuse_windows;
-  // the linear window average needs the fused kernels, the linear-domain recursion (k_post_z builds Z_avg) and a
-  // shape its kernels take; anything else runs as FAST
-  nd.hybrid = fast && !nd.fused && b->hybrid_ok && h->hybrid && h->fuse_windows && h->lin_dp && !h->force_fb && wave_path(h, true) && !f32;
-  nd.la = nd.fused && h->cfg.train_precision == SCRF_PREC_FASTLIN && h->lin_dp && !h->force_fb && wave_path(h, true) &&
-          fused_la_supported(l, b->recipe[0].in_width);
+  set_batch_form(h, b, &nd);
 
   // plan the chunks first: each must fit the scratch budget; with two lanes a batch is cut into
   // at least four chunks so that both streams always have work
@@ -2022,18 +2009,8 @@ static int fb_run(scrf_handle h, scrf_batch b, int latch[2], bool* used_lin) {
   }
   const size_t n_chunks = cuts.size() - 1;
   const bool use2 = two_lanes && n_chunks >= 2;
-  if (!h->m0_valid && !l.use_tf && !segtrans(h)) {
-    // transition scores carry only the bias: one L x L matrix (and its exp) for every frame;
-    // computed before the lanes fork
-    launch_scores_exact(h->stream, nullptr, l.F, nullptr, 1, h->d_lambda, l, 1, l.L * l.L, h->d_m0);
-    launch_exp_m(h->stream, h->d_m0, l.L, 1, h->d_e0, h->d_et0, h->d_msh0);
-    h->m0_valid = true;
-  }
-  if (sparse(h)) {
-    // lambda index-major once per call, on the engine stream before the lanes fork: every chunk's score kernel reads it
-    launch_sp_relay(h->stream, h->d_lambda, l, 0, h->d_lamT[0]);
-    if (l.use_tf) launch_sp_relay(h->stream, h->d_lambda, l, 1, h->d_lamT[1]);
-  }
+  if (!l.use_tf && !segtrans(h)) ensure_m0(h, h->stream);   // before the lanes fork
+  if (sparse(h)) relay_sparse_lambda(h, h->stream);
   if (use2) {
     HIPCHK(h, hipMemsetAsync(h->d_grad2, 0, sizeof(double) * l.lambda_len, h->stream));
     HIPCHK(h, hipMemsetAsync(h->d_sums2, 0, sizeof(double) * 4, h->stream));
@@ -2233,34 +2210,32 @@ static int fb_run(scrf_handle h, scrf_batch b, int latch[2], bool* used_lin) {
   return SCRF_OK;
 }
 
+// One pass over a batch and, where it raised NUMERIC on the wavefront kernels, a second one.  The wavefront recursions take
+// their transition step on exp(M - max M) (and the linear-domain one flushes what lies ~700 nats below a frame's maximum);
+// where that empties a whole vector or breaks a posterior-mass check, the batch is redone with the workgroup kernel, a
+// column-wise max-shifted log-sum-exp like the reference's LogMath.  Nothing of the first pass survives: its staged
+// gradient was dropped, its outputs are overwritten.
+template <class Pass>
+static int run_with_redo(scrf_handle h, const int latch[2], Pass pass) {
+  int rc = pass();
+  if (rc != SCRF_OK || latch[0] != SCRF_ERR_NUMERIC || !wave_path(h, true)) return rc;
+  h->n_lin_fallback++;
+  h->force_fb = true;
+  rc = pass();
+  h->force_fb = false;
+  return rc;
+}
+
 extern "C" int scrf_fb_batch(scrf_handle h, scrf_batch b, double* numer, double* zx) {
   if (!h || !b) return SCRF_ERR_INVALID;
   HIPCHK(h, hipSetDevice(h->device));
   if (!b->d_labels) return fail(h, SCRF_ERR_INVALID, "scrf_fb_batch: the batch carries no labels");
-  if (h->timing) {
-    memset(h->ms, 0, sizeof(h->ms)); memset(h->nlaunch, 0, sizeof(h->nlaunch)); h->ktimes.clear();
-    hipEventRecord(h->ev[SCRF_N_PHASES][0], h->stream);
-  }
+  CallTimer call(h);
   int latch[2] = {0, 0};
   bool used_lin = false;
-  int rc = fb_run(h, b, latch, &used_lin);
+  int rc = run_with_redo(h, latch, [&] { return fb_run(h, b, latch, &used_lin); });
   if (rc != SCRF_OK) return rc;
-  if (latch[0] == SCRF_ERR_NUMERIC && wave_path(h, true)) {
-    // the wavefront recursions take their transition step on exp(M - max M) (and the linear-domain one
-    // flushes what lies ~700 nats below a frame's maximum); where that empties a whole vector or breaks a
-    // posterior-mass check, the batch is redone with the workgroup kernel, a column-wise max-shifted
-    // log-sum-exp like the reference's LogMath -- the staged gradient of the first pass was dropped
-    h->n_lin_fallback++;
-    h->force_fb = true;
-    rc = fb_run(h, b, latch, &used_lin);
-    h->force_fb = false;
-    if (rc != SCRF_OK) return rc;
-  }
-  if (h->timing) {
-    hipEventRecord(h->ev[SCRF_N_PHASES][1], h->stream);
-    hipEventSynchronize(h->ev[SCRF_N_PHASES][1]);
-    hipEventElapsedTime(&h->ms[PH_ALL], h->ev[SCRF_N_PHASES][0], h->ev[SCRF_N_PHASES][1]);
-  }
+  call.stop();
   if (latch[0] != 0) return fail(h, latch[0], "utterance %d: %s", latch[1], status_text(latch[0]));
   if (numer || zx) {
     if (numer) HIPCHK(h, hipMemcpyAsync(numer, b->d_numer, sizeof(double) * b->U, hipMemcpyDeviceToHost, h->stream));
@@ -2309,21 +2284,10 @@ static int post_run(scrf_handle h, scrf_batch b, const PostOut& po, int latch[2]
   Need nd{true, false, true, false};
   nd.ponly = true;
   nd.plog = !fast;   // SCRF_PREC_EXACT: the log-domain recursion and k_post_occ_log
-  // the batch forms of scrf_fb_batch (scrf_batch_is_fused)
-  nd.fused = fast && b->fused_ok && h->fuse_windows;
-  nd.hybrid = fast && !nd.fused && b->hybrid_ok && h->hybrid && h->fuse_windows && h->lin_dp && !h->force_fb && wave_path(h, true) && !f32;
-  nd.la = nd.fused && h->cfg.train_precision == SCRF_PREC_FASTLIN && h->lin_dp && !h->force_fb && wave_path(h, true) &&
-          fused_la_supported(l, b->recipe[0].in_width);
+  set_batch_form(h, b, &nd);   // the batch forms of scrf_fb_batch
   ScrfBatchView bv = b->view();
-  if (!h->m0_valid && !l.use_tf) {
-    launch_scores_exact(h->stream, nullptr, l.F, nullptr, 1, h->d_lambda, l, 1, l.L * l.L, h->d_m0);
-    launch_exp_m(h->stream, h->d_m0, l.L, 1, h->d_e0, h->d_et0, h->d_msh0);
-    h->m0_valid = true;
-  }
-  if (sparse(h)) {
-    launch_sp_relay(h->stream, h->d_lambda, l, 0, h->d_lamT[0]);
-    if (l.use_tf) launch_sp_relay(h->stream, h->d_lambda, l, 1, h->d_lamT[1]);
-  }
+  if (!l.use_tf) ensure_m0(h, h->stream);
+  if (sparse(h)) relay_sparse_lambda(h, h->stream);
   for (uint32_t u0 = 0; u0 < b->U;) {
     const uint32_t u1 = plan_chunk(h, b, u0, nd);
     ChunkBufs cb;
@@ -2424,27 +2388,11 @@ extern "C" int scrf_posteriors_batch(scrf_handle h, scrf_batch b, double* zx, do
     po.q_u = dq; po.q_e = dq + nq; po.q_lab = dq + 2 * nq;
     po.lab_off = lab_off;
   }
-  if (h->timing) {
-    memset(h->ms, 0, sizeof(h->ms)); memset(h->nlaunch, 0, sizeof(h->nlaunch)); h->ktimes.clear();
-    hipEventRecord(h->ev[SCRF_N_PHASES][0], h->stream);
-  }
+  CallTimer call(h);
   int latch[2] = {0, 0};
-  rc = post_run(h, b, po, latch);
+  rc = run_with_redo(h, latch, [&] { return post_run(h, b, po, latch); });   // the redo runs k_post_occ_log
   if (rc != SCRF_OK) return rc;
-  if (latch[0] == SCRF_ERR_NUMERIC && wave_path(h, true)) {
-    // as scrf_fb_batch: a wavefront recursion that gave up (or a failed mass check) is redone with the workgroup kernel,
-    // the reference's LogMath, and k_post_occ_log; every output of the first pass is overwritten
-    h->n_lin_fallback++;
-    h->force_fb = true;
-    rc = post_run(h, b, po, latch);
-    h->force_fb = false;
-    if (rc != SCRF_OK) return rc;
-  }
-  if (h->timing) {
-    hipEventRecord(h->ev[SCRF_N_PHASES][1], h->stream);
-    hipEventSynchronize(h->ev[SCRF_N_PHASES][1]);
-    hipEventElapsedTime(&h->ms[PH_ALL], h->ev[SCRF_N_PHASES][0], h->ev[SCRF_N_PHASES][1]);
-  }
+  call.stop();
   if (latch[0] != 0) return fail(h, latch[0], "utterance %d: %s", latch[1], status_text(latch[0]));
   if (zx) HIPCHK(h, hipMemcpyAsync(zx, b->d_zx, sizeof(double) * b->U, hipMemcpyDeviceToHost, h->stream));
   if (frame_post) HIPCHK(h, hipMemcpyAsync(frame_post, po.occ, sizeof(double) * nF * l.L, hipMemcpyDeviceToHost, h->stream));
@@ -2480,6 +2428,59 @@ static int check_u(scrf_handle h, scrf_batch b, uint32_t u, const char* fn) {
   if (u >= b->U) return fail(h, SCRF_ERR_INVALID, "%s: utterance %u >= %u", fn, u, b->U);
   return SCRF_OK;
 }
+
+// the n-state / STDSEG pipelines through one call: scores and recursion of chunk [u0, u1), no posteriors
+struct SmallBufs { NstateBufs ns; StdsegBufs sg; };
+static int run_small_chunk(scrf_handle h, scrf_batch b, uint32_t u0, uint32_t u1, SmallBufs* sb) {
+  return nstate(h) ? nstate_run_chunk(h, b, u0, u1, false, nullptr, &sb->ns) : stdseg_run_chunk(h, b, u0, u1, false, nullptr, &sb->sg);
+}
+// ... of one utterance, for the hooks
+static int hook_small_chunk(scrf_handle h, scrf_batch b, uint32_t u, SmallBufs* sb) {
+  HIPCHK(h, hipMemsetAsync(b->d_status, 0, sizeof(int) * b->U, h->stream));
+  return run_small_chunk(h, b, u, u + 1, sb);
+}
+
+// Zx = -computeAlphaSum() of utterance u, read back (the final arcs of a normalised lattice carry it)
+static int read_zx(scrf_handle h, scrf_batch b, uint32_t u, double* Zx) {
+  double asum = 0;
+  HIPCHK(h, hipMemcpyAsync(&asum, b->d_zx + u, sizeof(double), hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  *Zx = -1 * asum;
+  return SCRF_OK;
+}
+
+// One utterance through carve, EXACT scores and the log-domain recursion, for hook `fn`: *cb holds the node values on success.
+// Second attempt: the workgroup kernel (reference LogMath) when the wavefront recursion gave up.  A label out of range
+// does not stop a hook that reads no label.
+static int hook_fb(scrf_handle h, scrf_batch b, uint32_t u, const char* fn, ChunkBufs* cb) {
+  const Need nd{true, false, true, false};
+  for (;;) {
+    *cb = ChunkBufs();
+    int rc = carve(h, b, u, u + 1, nd, cb);
+    if (rc == SCRF_OK) rc = run_scores(h, b, u, u + 1, *cb);
+    if (rc == SCRF_OK && hipMemsetAsync(b->d_status, 0, sizeof(int) * b->U, h->stream) != hipSuccess) rc = fail(h, SCRF_ERR_HIP, "%s: memset failed", fn);
+    if (rc == SCRF_OK) rc = run_dp(h, b, u, u + 1, *cb, false, nullptr);
+    int st = 0;
+    if (rc == SCRF_OK && hipMemcpyAsync(&st, b->d_status + u, sizeof(int), hipMemcpyDeviceToHost, h->stream) != hipSuccess) rc = fail(h, SCRF_ERR_HIP, "%s: status copy failed", fn);
+    if (rc == SCRF_OK && hipStreamSynchronize(h->stream) != hipSuccess) rc = fail(h, SCRF_ERR_HIP, "%s: synchronize failed", fn);
+    if (rc == SCRF_OK && st == SCRF_ERR_NUMERIC && !h->force_fb && wave_path(h, false)) { h->force_fb = true; continue; }
+    h->force_fb = false;
+    if (rc != SCRF_OK) return rc;
+    if (st != SCRF_OK && st != SCRF_ERR_BAD_LABEL) return fail(h, st, "utterance %u: numeric failure in forward-backward", u);
+    return SCRF_OK;
+  }
+}
+
+// device buffer owned by a scope (the one-off arrays of the hooks and of the small decode paths)
+template <class Tp>
+struct DevBuf {
+  Tp* p = nullptr;
+  DevBuf() = default;
+  DevBuf(const DevBuf&) = delete;
+  DevBuf& operator=(const DevBuf&) = delete;
+  ~DevBuf() { hipFree(p); }
+  hipError_t alloc(size_t n) { return hipMalloc((void**)&p, sizeof(Tp) * n); }
+};
 
 extern "C" int scrf_windows(scrf_handle h, scrf_batch b, uint32_t u, float* out) {
   int rc = check_u(h, b, u, "scrf_windows");
@@ -2519,10 +2520,10 @@ extern "C" int scrf_scores(scrf_handle h, scrf_batch b, uint32_t u, double* S, d
   if (rc != SCRF_OK) return rc;
   HIPCHK(h, hipSetDevice(h->device));
   if (nstate(h)) {   // S [T][nLabs]; M [T][2*nLabs + P*P]: self transitions | c -> c+1 | end state of p -> start state of q
-    NstateBufs nb;
-    HIPCHK(h, hipMemsetAsync(b->d_status, 0, sizeof(int) * b->U, h->stream));
-    rc = nstate_run_chunk(h, b, u, u + 1, false, nullptr, &nb);
+    SmallBufs sm;
+    rc = hook_small_chunk(h, b, u, &sm);
     if (rc != SCRF_OK) return rc;
+    const NstateBufs& nb = sm.ns;
     const uint64_t T = b->T[u], L = h->lay.L, P = L / h->lay.K, w = 2 * L + P * P;
     if (S) HIPCHK(h, hipMemcpyAsync(S, nb.S, sizeof(double) * T * L, hipMemcpyDeviceToHost, h->stream));
     if (M) {
@@ -2534,10 +2535,10 @@ extern "C" int scrf_scores(scrf_handle h, scrf_batch b, uint32_t u, double* S, d
     return SCRF_OK;
   }
   if (stdseg(h)) {   // S [N_seg][nActualLabs], M [N_seg][nLabs][nActualLabs]
-    StdsegBufs sb;
-    HIPCHK(h, hipMemsetAsync(b->d_status, 0, sizeof(int) * b->U, h->stream));
-    rc = stdseg_run_chunk(h, b, u, u + 1, false, nullptr, &sb);
+    SmallBufs sm;
+    rc = hook_small_chunk(h, b, u, &sm);
     if (rc != SCRF_OK) return rc;
+    const StdsegBufs& sb = sm.sg;
     const uint64_t ns = b->seg_off[u + 1] - b->seg_off[u];
     const uint32_t La = stdseg_La(h);
     if (S) HIPCHK(h, hipMemcpyAsync(S, sb.S, sizeof(double) * ns * La, hipMemcpyDeviceToHost, h->stream));
@@ -2565,10 +2566,10 @@ extern "C" int scrf_forward_backward(scrf_handle h, scrf_batch b, uint32_t u, ui
   if (prec != SCRF_PREC_EXACT) return fail(h, SCRF_ERR_INVALID, "scrf_forward_backward: the node-value hook runs at SCRF_PREC_EXACT only");
   HIPCHK(h, hipSetDevice(h->device));
   if (nstate(h)) {   // alpha, beta: [T][nLabs]; alpha_dur is not written
-    NstateBufs nb;
-    HIPCHK(h, hipMemsetAsync(b->d_status, 0, sizeof(int) * b->U, h->stream));
-    rc = nstate_run_chunk(h, b, u, u + 1, false, nullptr, &nb);
+    SmallBufs sm;
+    rc = hook_small_chunk(h, b, u, &sm);
     if (rc != SCRF_OK) return rc;
+    const NstateBufs& nb = sm.ns;
     const uint64_t n = (uint64_t)b->T[u] * h->lay.L;
     int st = 0;
     if (alpha) HIPCHK(h, hipMemcpyAsync(alpha, nb.alpha, sizeof(double) * n, hipMemcpyDeviceToHost, h->stream));
@@ -2580,10 +2581,10 @@ extern "C" int scrf_forward_backward(scrf_handle h, scrf_batch b, uint32_t u, ui
     return SCRF_OK;
   }
   if (stdseg(h)) {   // alpha_dur and beta: the nodes' alpha / beta over full labels, [N_seg][nActualLabs]; `alpha` is not written
-    StdsegBufs sb;
-    HIPCHK(h, hipMemsetAsync(b->d_status, 0, sizeof(int) * b->U, h->stream));
-    rc = stdseg_run_chunk(h, b, u, u + 1, false, nullptr, &sb);
+    SmallBufs sm;
+    rc = hook_small_chunk(h, b, u, &sm);
     if (rc != SCRF_OK) return rc;
+    const StdsegBufs& sb = sm.sg;
     const uint64_t ns = b->seg_off[u + 1] - b->seg_off[u];
     const uint32_t La = stdseg_La(h);
     int st = 0;
@@ -2596,30 +2597,16 @@ extern "C" int scrf_forward_backward(scrf_handle h, scrf_batch b, uint32_t u, ui
     return SCRF_OK;
   }
   const ScrfLayout& l = h->lay;
-  Need nd{true, false, true, false};
-  uint64_t nseg = b->seg_off[u + 1] - b->seg_off[u];
-  uint32_t T = b->T[u];
-  // second attempt: the workgroup kernel (reference LogMath) when the wavefront recursion gave up
-  for (int attempt = 0; attempt < 2; attempt++) {
-    ChunkBufs cb;
-    rc = carve(h, b, u, u + 1, nd, &cb);
-    if (rc == SCRF_OK) rc = run_scores(h, b, u, u + 1, cb);
-    if (rc == SCRF_OK && hipMemsetAsync(b->d_status, 0, sizeof(int) * b->U, h->stream) != hipSuccess) rc = fail(h, SCRF_ERR_HIP, "scrf_forward_backward: memset failed");
-    if (rc == SCRF_OK) rc = run_dp(h, b, u, u + 1, cb, false, nullptr);
-    int st = 0;
-    if (rc == SCRF_OK && hipMemcpyAsync(&st, b->d_status + u, sizeof(int), hipMemcpyDeviceToHost, h->stream) != hipSuccess) rc = fail(h, SCRF_ERR_HIP, "scrf_forward_backward: status copy failed");
-    if (rc == SCRF_OK && hipStreamSynchronize(h->stream) != hipSuccess) rc = fail(h, SCRF_ERR_HIP, "scrf_forward_backward: synchronize failed");
-    if (rc != SCRF_OK) { h->force_fb = false; return rc; }
-    if (st == SCRF_ERR_NUMERIC && !h->force_fb && wave_path(h, false)) { h->force_fb = true; continue; }
-    h->force_fb = false;
-    if (st != SCRF_OK && st != SCRF_ERR_BAD_LABEL) return fail(h, st, "utterance %u: numeric failure in forward-backward", u);
-    if (alpha_dur) HIPCHK(h, hipMemcpyAsync(alpha_dur, cb.AD, sizeof(double) * nseg * l.L, hipMemcpyDeviceToHost, h->stream));
-    if (alpha) HIPCHK(h, hipMemcpyAsync(alpha, cb.alpha, sizeof(double) * T * l.L, hipMemcpyDeviceToHost, h->stream));
-    if (beta) HIPCHK(h, hipMemcpyAsync(beta, cb.beta, sizeof(double) * T * l.L, hipMemcpyDeviceToHost, h->stream));
-    if (zx) HIPCHK(h, hipMemcpyAsync(zx, b->d_zx + u, sizeof(double), hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    break;
-  }
+  const uint64_t nseg = b->seg_off[u + 1] - b->seg_off[u];
+  const uint32_t T = b->T[u];
+  ChunkBufs cb;
+  rc = hook_fb(h, b, u, "scrf_forward_backward", &cb);
+  if (rc != SCRF_OK) return rc;
+  if (alpha_dur) HIPCHK(h, hipMemcpyAsync(alpha_dur, cb.AD, sizeof(double) * nseg * l.L, hipMemcpyDeviceToHost, h->stream));
+  if (alpha) HIPCHK(h, hipMemcpyAsync(alpha, cb.alpha, sizeof(double) * T * l.L, hipMemcpyDeviceToHost, h->stream));
+  if (beta) HIPCHK(h, hipMemcpyAsync(beta, cb.beta, sizeof(double) * T * l.L, hipMemcpyDeviceToHost, h->stream));
+  if (zx) HIPCHK(h, hipMemcpyAsync(zx, b->d_zx + u, sizeof(double), hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(h, hipStreamSynchronize(h->stream));
   return SCRF_OK;
 }
 
@@ -2631,27 +2618,13 @@ extern "C" int scrf_seg_posteriors(scrf_handle h, scrf_batch b, uint32_t u, doub
   if (rc != SCRF_OK) return rc;
   HIPCHK(h, hipSetDevice(h->device));
   const ScrfLayout& l = h->lay;
-  Need nd{true, false, true, false};
   const uint64_t nseg = b->seg_off[u + 1] - b->seg_off[u];
-  // second attempt: the workgroup kernel (reference LogMath) when the wavefront recursion gave up
-  for (int attempt = 0; attempt < 2; attempt++) {
-    ChunkBufs cb;
-    rc = carve(h, b, u, u + 1, nd, &cb);
-    if (rc == SCRF_OK) rc = run_scores(h, b, u, u + 1, cb);
-    if (rc == SCRF_OK && hipMemsetAsync(b->d_status, 0, sizeof(int) * b->U, h->stream) != hipSuccess) rc = fail(h, SCRF_ERR_HIP, "scrf_seg_posteriors: memset failed");
-    if (rc == SCRF_OK) rc = run_dp(h, b, u, u + 1, cb, false, nullptr);
-    int st = 0;
-    if (rc == SCRF_OK && hipMemcpyAsync(&st, b->d_status + u, sizeof(int), hipMemcpyDeviceToHost, h->stream) != hipSuccess) rc = fail(h, SCRF_ERR_HIP, "scrf_seg_posteriors: status copy failed");
-    if (rc == SCRF_OK && hipStreamSynchronize(h->stream) != hipSuccess) rc = fail(h, SCRF_ERR_HIP, "scrf_seg_posteriors: synchronize failed");
-    if (rc != SCRF_OK) { h->force_fb = false; return rc; }
-    if (st == SCRF_ERR_NUMERIC && !h->force_fb && wave_path(h, false)) { h->force_fb = true; continue; }
-    h->force_fb = false;
-    if (st != SCRF_OK && st != SCRF_ERR_BAD_LABEL) return fail(h, st, "utterance %u: numeric failure in forward-backward", u);
-    launch_gamma_log(h->stream, l, b->T[u], cb.AD, cb.beta, b->d_zx + u, cb.AD);
-    HIPCHK(h, hipMemcpyAsync(gamma, cb.AD, sizeof(double) * nseg * l.L, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    break;
-  }
+  ChunkBufs cb;
+  rc = hook_fb(h, b, u, "scrf_seg_posteriors", &cb);
+  if (rc != SCRF_OK) return rc;
+  launch_gamma_log(h->stream, l, b->T[u], cb.AD, cb.beta, b->d_zx + u, cb.AD);
+  HIPCHK(h, hipMemcpyAsync(gamma, cb.AD, sizeof(double) * nseg * l.L, hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(h, hipStreamSynchronize(h->stream));
   return SCRF_OK;
 }
 
@@ -2671,23 +2644,18 @@ extern "C" int scrf_lattice_arcs(scrf_handle h, scrf_batch b, uint32_t u, int no
     if (n_states) *n_states = L * T + 2;
     if (final_state) *final_state = (int32_t)(L * T + 1);
     if (!arcs) return SCRF_OK;
-    NstateBufs nb;
-    HIPCHK(h, hipMemsetAsync(b->d_status, 0, sizeof(int) * b->U, h->stream));
-    rc = nstate_run_chunk(h, b, u, u + 1, false, nullptr, &nb);
+    SmallBufs sm;
+    rc = hook_small_chunk(h, b, u, &sm);
     if (rc != SCRF_OK) return rc;
-    float final_w = 0.0f;
-    if (norm) {
-      double asum = 0;
-      HIPCHK(h, hipMemcpyAsync(&asum, b->d_zx + u, sizeof(double), hipMemcpyDeviceToHost, h->stream));
-      HIPCHK(h, hipStreamSynchronize(h->stream));
-      final_w = (float)(-1 * asum);
-    }
-    scrf_arc* d_arcs = nullptr;
-    HIPCHK(h, hipMalloc((void**)&d_arcs, sizeof(scrf_arc) * na));
-    launch_ns_arcs(h->stream, h->lay, T, nb.S, nb.TD, nb.TO, nb.TE, final_w, d_arcs);
-    hipError_t e = hipMemcpyAsync(arcs, d_arcs, sizeof(scrf_arc) * na, hipMemcpyDeviceToHost, h->stream);
+    const NstateBufs& nb = sm.ns;
+    double Zx = 0.0;
+    if (norm && (rc = read_zx(h, b, u, &Zx)) != SCRF_OK) return rc;
+    const float final_w = norm ? (float)Zx : 0.0f;
+    DevBuf<scrf_arc> d_arcs;
+    HIPCHK(h, d_arcs.alloc(na));
+    launch_ns_arcs(h->stream, h->lay, T, nb.S, nb.TD, nb.TO, nb.TE, final_w, d_arcs.p);
+    hipError_t e = hipMemcpyAsync(arcs, d_arcs.p, sizeof(scrf_arc) * na, hipMemcpyDeviceToHost, h->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
-    hipFree(d_arcs);
     if (e != hipSuccess) return fail(h, SCRF_ERR_HIP, "scrf_lattice_arcs: %s", hipGetErrorString(e));
     return SCRF_OK;
   }
@@ -2698,31 +2666,25 @@ extern "C" int scrf_lattice_arcs(scrf_handle h, scrf_batch b, uint32_t u, int no
     if (n_states) *n_states = (uint32_t)(2 + ns * La);
     if (final_state) *final_state = (int32_t)(1 + ns * La);
     if (!arcs) return SCRF_OK;
-    StdsegBufs sb;
-    HIPCHK(h, hipMemsetAsync(b->d_status, 0, sizeof(int) * b->U, h->stream));
-    rc = stdseg_run_chunk(h, b, u, u + 1, false, nullptr, &sb);
+    SmallBufs sm;
+    rc = hook_small_chunk(h, b, u, &sm);
     if (rc != SCRF_OK) return rc;
-    float final_w = -0.0f;
-    if (norm) {
-      double asum = 0;
-      HIPCHK(h, hipMemcpyAsync(&asum, b->d_zx + u, sizeof(double), hipMemcpyDeviceToHost, h->stream));
-      HIPCHK(h, hipStreamSynchronize(h->stream));
-      const double Zx = -1 * asum;
-      final_w = (float)(-Zx);
-    }
+    const StdsegBufs& sb = sm.sg;
+    double Zx = 0.0;
+    if (norm && (rc = read_zx(h, b, u, &Zx)) != SCRF_OK) return rc;
+    const float final_w = norm ? (float)(-Zx) : -0.0f;
     std::vector<uint64_t> off;
     stdseg_row_arc_offsets(T, La, h->lay.D, &off);
-    uint64_t* d_off = nullptr;
-    scrf_arc* d_arcs = nullptr;
-    hipError_t e = hipMalloc((void**)&d_off, sizeof(uint64_t) * off.size());
-    if (e == hipSuccess) e = hipMalloc((void**)&d_arcs, sizeof(scrf_arc) * na);
-    if (e == hipSuccess) e = hipMemcpyAsync(d_off, off.data(), sizeof(uint64_t) * off.size(), hipMemcpyHostToDevice, h->stream);
+    DevBuf<uint64_t> d_off;
+    DevBuf<scrf_arc> d_arcs;
+    hipError_t e = d_off.alloc(off.size());
+    if (e == hipSuccess) e = d_arcs.alloc(na);
+    if (e == hipSuccess) e = hipMemcpyAsync(d_off.p, off.data(), sizeof(uint64_t) * off.size(), hipMemcpyHostToDevice, h->stream);
     if (e == hipSuccess) {
-      launch_stdseg_arcs(h->stream, h->lay, La, T, ns, d_off, sb.S, sb.MX, final_w, d_arcs);
-      e = hipMemcpyAsync(arcs, d_arcs, sizeof(scrf_arc) * na, hipMemcpyDeviceToHost, h->stream);
+      launch_stdseg_arcs(h->stream, h->lay, La, T, ns, d_off.p, sb.S, sb.MX, final_w, d_arcs.p);
+      e = hipMemcpyAsync(arcs, d_arcs.p, sizeof(scrf_arc) * na, hipMemcpyDeviceToHost, h->stream);
     }
     if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
-    hipFree(d_off); hipFree(d_arcs);
     if (e != hipSuccess) return fail(h, SCRF_ERR_HIP, "scrf_lattice_arcs: %s", hipGetErrorString(e));
     return SCRF_OK;
   }
@@ -2747,21 +2709,19 @@ extern "C" int scrf_lattice_arcs(scrf_handle h, scrf_batch b, uint32_t u, int no
     HIPCHK(h, hipMemsetAsync(b->d_status, 0, sizeof(int) * b->U, h->stream));
     rc = run_dp(h, b, u, u + 1, cb, false, nullptr);
     if (rc != SCRF_OK) return rc;
-    double asum = 0;
-    HIPCHK(h, hipMemcpyAsync(&asum, b->d_zx + u, sizeof(double), hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    double Zx = -1 * asum;
+    double Zx = 0.0;
+    rc = read_zx(h, b, u, &Zx);
+    if (rc != SCRF_OK) return rc;
     final_w = frame_model ? (float)Zx : (float)(-Zx);
   }
-  scrf_arc* d_arcs = nullptr;
-  HIPCHK(h, hipMalloc((void**)&d_arcs, sizeof(scrf_arc) * na));
-  if (segtrans(h)) launch_arcs_segtrans(h->stream, l, T, cb.S, cb.M, final_w, d_arcs);
-  else launch_arcs(h->stream, l, T, frame_model, cb.S, cb.M, cb.m_per_frame, final_w, d_arcs);
+  DevBuf<scrf_arc> d_arcs;
+  HIPCHK(h, d_arcs.alloc(na));
+  if (segtrans(h)) launch_arcs_segtrans(h->stream, l, T, cb.S, cb.M, final_w, d_arcs.p);
+  else launch_arcs(h->stream, l, T, frame_model, cb.S, cb.M, cb.m_per_frame, final_w, d_arcs.p);
   std::vector<scrf_arc> dense;
   if (h->shadow) dense.resize(na);
-  hipError_t e = hipMemcpyAsync(h->shadow ? dense.data() : arcs, d_arcs, sizeof(scrf_arc) * na, hipMemcpyDeviceToHost, h->stream);
+  hipError_t e = hipMemcpyAsync(h->shadow ? dense.data() : arcs, d_arcs.p, sizeof(scrf_arc) * na, hipMemcpyDeviceToHost, h->stream);
   if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
-  hipFree(d_arcs);
   if (e != hipSuccess) return fail(h, SCRF_ERR_HIP, "scrf_lattice_arcs: %s", hipGetErrorString(e));
   if (h->shadow) {
     // nStateBuildLattice :563-597: of the L*L boundary arcs of a frame (state-major, previous label ascending) a
@@ -2819,10 +2779,7 @@ extern "C" int scrf_lattice_prune_batch(scrf_handle h, scrf_batch b, double beam
   }
   double* d_best = (double*)h->lp_meta;
   uint64_t* d_uoff = (uint64_t*)(h->lp_meta + by_best);
-  if (h->timing) {
-    memset(h->ms, 0, sizeof(h->ms)); memset(h->nlaunch, 0, sizeof(h->nlaunch)); h->ktimes.clear();
-    hipEventRecord(h->ev[SCRF_N_PHASES][0], h->stream);
-  }
+  CallTimer call(h);
   h->n_lp_calls++;
   Need nd{false, false, false, false};
   nd.lat = true;
@@ -2867,11 +2824,7 @@ extern "C" int scrf_lattice_prune_batch(scrf_handle h, scrf_batch b, double beam
   HIPCHK(h, hipMemcpyAsync(h->lp_off.data(), d_uoff, sizeof(uint64_t) * (U + 1), hipMemcpyDeviceToHost, h->stream));
   if (best_cost) HIPCHK(h, hipMemcpyAsync(best_cost, d_best, sizeof(double) * U, hipMemcpyDeviceToHost, h->stream));
   HIPCHK(h, hipStreamSynchronize(h->stream));
-  if (h->timing) {
-    hipEventRecord(h->ev[SCRF_N_PHASES][1], h->stream);
-    hipEventSynchronize(h->ev[SCRF_N_PHASES][1]);
-    hipEventElapsedTime(&h->ms[PH_ALL], h->ev[SCRF_N_PHASES][0], h->ev[SCRF_N_PHASES][1]);
-  }
+  call.stop();
   if (h->lp_off[U] != total) return fail(h, SCRF_ERR_INVALID, "scrf_lattice_prune_batch: arc count mismatch (internal)");
   memcpy(arc_off, h->lp_off.data(), sizeof(uint64_t) * (U + 1));
   h->lp_batch = b;
@@ -2908,7 +2861,7 @@ extern "C" int scrf_viterbi_batch(scrf_handle h, scrf_batch b, uint32_t* seg_lab
   HIPCHK(h, hipSetDevice(h->device));
   const ScrfLayout& l = h->lay;
   const bool frame_model = h->cfg.model_type == SCRF_STDFRAME;
-  if (h->timing) { memset(h->ms, 0, sizeof(h->ms)); memset(h->nlaunch, 0, sizeof(h->nlaunch)); h->ktimes.clear(); hipEventRecord(h->ev[SCRF_N_PHASES][0], h->stream); }
+  CallTimer call(h);
   const uint64_t NF = b->frame_off[b->U];
   if (NF > h->dec_cap_f) {
     hipFree(h->dec_lab); h->dec_lab = nullptr;
@@ -2939,46 +2892,26 @@ extern "C" int scrf_viterbi_batch(scrf_handle h, scrf_batch b, uint32_t* seg_lab
   ndf.fused = ndf.vitfast = true;
   const bool fast = h->fast_decode && b->fused_ok && !b->mixed && h->fuse_windows && !frame_model && l.L <= 0xffff;
   int rc = SCRF_OK;
-  if (nstate(h)) {
+  if (nstate(h) || stdseg(h)) {
+    // the chunk's scores in the scratch arena (chunks planned with the `post` sizing), path costs and back pointers per
+    // (row, label) in buffers of their own
+    const uint32_t n_lab = nstate(h) ? l.L : stdseg_La(h);
     HIPCHK(h, hipMemsetAsync(b->d_status, 0, sizeof(int) * b->U, h->stream));
-    for (uint32_t u0 = 0; u0 < b->U && rc == SCRF_OK;) {
-      const uint32_t u1 = nstate_plan_chunk(h, b, u0, true);
-      NstateBufs nb;
-      rc = nstate_run_chunk(h, b, u0, u1, false, nullptr, &nb);
+    for (uint32_t u0 = 0; u0 < b->U;) {
+      const uint32_t u1 = nstate(h) ? nstate_plan_chunk(h, b, u0, true) : stdseg_plan_chunk(h, b, u0, true);
+      SmallBufs sm;
+      rc = run_small_chunk(h, b, u0, u1, &sm);
       if (rc != SCRF_OK) break;
-      const uint64_t nfr = b->frame_off[u1] - b->frame_off[u0];
-      float* vc = nullptr;
-      uint16_t* bp = nullptr;
-      hipError_t e = hipMalloc((void**)&vc, sizeof(float) * nfr * l.L);
-      if (e == hipSuccess) e = hipMalloc((void**)&bp, sizeof(uint16_t) * nfr * l.L);
+      const uint64_t rows = nstate(h) ? b->frame_off[u1] - b->frame_off[u0] : b->seg_off[u1] - b->seg_off[u0];
+      DevBuf<float> vc;
+      DevBuf<uint16_t> bp;
+      hipError_t e = vc.alloc(rows * n_lab);
+      if (e == hipSuccess) e = bp.alloc(rows * n_lab);
       if (e == hipSuccess) {
-        launch_ns_viterbi(h->stream, l, b->view(), u0, u1 - u0, nb.S, nb.TD, nb.TO, nb.TE, vc, bp, d_lab, d_n, d_cost);
+        if (nstate(h)) launch_ns_viterbi(h->stream, l, b->view(), u0, u1 - u0, sm.ns.S, sm.ns.TD, sm.ns.TO, sm.ns.TE, vc.p, bp.p, d_lab, d_n, d_cost);
+        else launch_stdseg_viterbi(h->stream, l, n_lab, b->view(), u0, u1 - u0, sm.sg.S, sm.sg.MX, vc.p, bp.p, d_lab, d_n, d_cost);
         e = hipStreamSynchronize(h->stream);
       }
-      hipFree(vc); hipFree(bp);
-      if (e != hipSuccess) { rc = fail(h, SCRF_ERR_HIP, "scrf_viterbi_batch: %s", hipGetErrorString(e)); break; }
-      u0 = u1;
-    }
-  }
-  if (stdseg(h)) {
-    const uint32_t La = stdseg_La(h);
-    HIPCHK(h, hipMemsetAsync(b->d_status, 0, sizeof(int) * b->U, h->stream));
-    for (uint32_t u0 = 0; u0 < b->U && rc == SCRF_OK;) {
-      // the chunk's scores in the scratch arena, path costs and back pointers behind them
-      uint32_t u1 = stdseg_plan_chunk(h, b, u0, true);   // `post` sizing leaves room for the two decode arrays
-      StdsegBufs sb;
-      rc = stdseg_run_chunk(h, b, u0, u1, false, nullptr, &sb);
-      if (rc != SCRF_OK) break;
-      const uint64_t nseg = b->seg_off[u1] - b->seg_off[u0];
-      float* vc = nullptr;
-      uint16_t* bp = nullptr;
-      hipError_t e = hipMalloc((void**)&vc, sizeof(float) * nseg * La);
-      if (e == hipSuccess) e = hipMalloc((void**)&bp, sizeof(uint16_t) * nseg * La);
-      if (e == hipSuccess) {
-        launch_stdseg_viterbi(h->stream, h->lay, La, b->view(), u0, u1 - u0, sb.S, sb.MX, vc, bp, d_lab, d_n, d_cost);
-        e = hipStreamSynchronize(h->stream);
-      }
-      hipFree(vc); hipFree(bp);
       if (e != hipSuccess) { rc = fail(h, SCRF_ERR_HIP, "scrf_viterbi_batch: %s", hipGetErrorString(e)); break; }
       u0 = u1;
     }
@@ -2990,11 +2923,7 @@ extern "C" int scrf_viterbi_batch(scrf_handle h, scrf_batch b, uint32_t* seg_lab
       ChunkBufs cb;
       rc = carve(h, b, u0, u1, ndf, &cb);
       if (rc != SCRF_OK) break;
-      if (!h->m0_valid) {  // transition scores carry only the bias: one L x L matrix for every frame
-        launch_scores_exact(cb.st, nullptr, l.F, nullptr, 1, h->d_lambda, l, 1, l.L * l.L, h->d_m0);
-        launch_exp_m(cb.st, h->d_m0, l.L, 1, h->d_e0, h->d_et0, h->d_msh0);
-        h->m0_valid = true;
-      }
+      ensure_m0(h, cb.st);
       rc = run_scores(h, b, u0, u1, cb);
       if (rc != SCRF_OK) break;
       uint32_t n_fix = 0;
@@ -3042,11 +2971,7 @@ extern "C" int scrf_viterbi_batch(scrf_handle h, scrf_batch b, uint32_t* seg_lab
     else if (best_cost) memcpy(best_cost, h->dec_hcost, sizeof(float) * b->U);
   }
   if (rc != SCRF_OK) return rc;
-  if (h->timing) {
-    hipEventRecord(h->ev[SCRF_N_PHASES][1], h->stream);
-    hipEventSynchronize(h->ev[SCRF_N_PHASES][1]);
-    hipEventElapsedTime(&h->ms[PH_ALL], h->ev[SCRF_N_PHASES][0], h->ev[SCRF_N_PHASES][1]);
-  }
+  call.stop();
   uint64_t pos = 0;
   for (uint32_t u = 0; u < b->U; u++) {
     lab_off[u] = pos;
@@ -3060,13 +2985,11 @@ extern "C" int scrf_viterbi_batch(scrf_handle h, scrf_batch b, uint32_t* seg_lab
 
 extern "C" int scrf_batch_is_fused(scrf_handle h, scrf_batch b, int* fused) {
   if (!h || !b || !fused) return SCRF_ERR_INVALID;
-  *fused = b->fused_ok && h->fuse_windows ? 1 : 0;
-  // 3: hybrid (materialised dense statistics, sampled blocks through the per-frame projections)
-  if (!*fused && b->hybrid_ok && h->hybrid && h->fuse_windows && h->cfg.train_precision >= SCRF_PREC_FAST && h->cfg.train_precision != SCRF_PREC_FAST32 &&
-      h->lin_dp && wave_path(h, true)) *fused = 3;
-  // 2: training runs with the linear window average (SCRF_PREC_FASTLIN on a shape its kernels take)
-  if (*fused && h->cfg.train_precision == SCRF_PREC_FASTLIN && h->lin_dp && wave_path(h, true) &&
-      fused_la_supported(h->lay, b->recipe[0].in_width)) *fused = 2;
+  const BatchForm f = batch_form(h, b);
+  // 1 for a fusable batch at every precision (decode fuses at SCRF_PREC_EXACT too); 3: hybrid; 2: training runs with the
+  // linear window average
+  *fused = f.fusable ? 1 : f.hybrid ? 3 : 0;
+  if (*fused && f.la) *fused = 2;
   return SCRF_OK;
 }
 
