@@ -21,19 +21,78 @@ def nstate_segment_labels(rng, L, K, T, D):
     return out
 
 
+# input families (None: U[0, 1), the values every older test runs on): name -> nominal max |x|
+FAMILIES = {"signed": 8.0, "ranged": 64.0, "offset": 9.0, "tied": 2.0}
+TIED_VALUES = (-1.0, -0.5, 0.5, 1.0, 2.0)
+
+
+def family_frames(rng, family, Ts, in_w):
+    """float32 frames of one batch under an input family, finite and without a negative zero:
+    signed  N(0, 2^2): sign changes inside every window
+    ranged  N(0, 1) * 4^((u mod 4) - 1): scales 1/4, 1, 4 and 16 side by side in one batch
+    offset  8 + U[0, 1): a large common part (cancellation in differences of sums)
+    tied    values of TIED_VALUES, whole frames repeated in runs of 1 .. 3: exact ties in every running extremum"""
+    out = []
+    for u, T in enumerate(Ts):
+        if family == "signed":
+            x = rng.normal(0.0, 2.0, (T, in_w))
+        elif family == "ranged":
+            x = rng.normal(0.0, 1.0, (T, in_w)) * 4.0 ** ((u % 4) - 1)
+        elif family == "offset":
+            x = 8.0 + rng.random_sample((T, in_w))
+        elif family == "tied":
+            x = rng.choice(TIED_VALUES, (T, in_w))
+            t = 0
+            while t < T:
+                n = int(rng.randint(1, 4))
+                x[t:t + n] = x[t]
+                t += n
+        else:
+            raise ValueError("unknown input family %r" % (family,))
+        out.append(x.astype(np.float32) + np.float32(0.0))   # (-0.0) + 0.0 = +0.0
+    return out
+
+
+def tie_twin_labels(lam, lay, L, K=1):
+    """phone 1 becomes a twin of phone 0 (K = 1: label 1 of label 0): every weight indexed by one of its labels equals the
+    weight indexed the same way by the label of phone 0 -- the state block, and every transition block with it as previous
+    or as current label -- and the state bias of both is raised by 2, so that best paths run through them: any best
+    path through either then has a twin of equal cost."""
+    nsf, ntf = lay.num_state_funcs, lay.num_trans_funcs
+    if L < 2 * K:
+        return
+    twin = lambda l: l - K if K <= l < 2 * K else l
+    for l in range(K, 2 * K):
+        lam[lay.state_idx[l]:lay.state_idx[l] + nsf] = lam[lay.state_idx[l - K]:lay.state_idx[l - K] + nsf]
+    for p in range(L):
+        for c in range(L):
+            i, j = int(lay.trans_idx[p * L + c]), int(lay.trans_idx[twin(p) * L + twin(c)])
+            if i != j and i != 0xffffffff and j != 0xffffffff:
+                lam[i:i + ntf] = lam[j:j + ntf]
+    if lay.cfg.use_state_bias:
+        for l in range(2 * K):
+            lam[lay.state_idx[l] + nsf - 1] += 2.0
+
+
 class Case:
     """L labels, max duration D, raw frame width in_w, utterance lengths Ts.
     trans_ctx=None: `stdstate` map (bias-only transitions); trans_ctx=c: `stdtrans` map whose
     transition features are a second stream of boundary context (c frames each side), like the
-    TIMIT demo's ftr2 stream (demo/segmental-timit-demo.cfg.in:21-24)."""
+    TIMIT demo's ftr2 stream (demo/segmental-timit-demo.cfg.in:21-24).
+    family: one of FAMILIES instead of frames in [0, 1) (family_frames); lam_scale then defaults to
+    3 / (nominal max |x| * sqrt(F)), which keeps scores to a few nats, and `tied` also ties two labels (tie_twin_labels)."""
 
-    def __init__(self, L, D, in_w, Ts, trans_ctx=None, seed=0, lam_scale=0.3, frame_model=False,
+    def __init__(self, L, D, in_w, Ts, trans_ctx=None, seed=0, lam_scale=None, frame_model=False,
                  scratch_bytes=0, precision=0, l1_norm=False, model_type=None, trans_share=None,
-                 num_states=1, conform_labels=True, exact_avg=False):
+                 num_states=1, conform_labels=True, exact_avg=False, family=None):
         self.L, self.D, self.in_w, self.Ts = L, D, in_w, list(Ts)
         self.trans_ctx = trans_ctx
+        self.family = family
         rng = np.random.RandomState(seed)
-        self.frames = [rng.random_sample((T, in_w)).astype(np.float32) for T in Ts]
+        if family is None:
+            self.frames = [rng.random_sample((T, in_w)).astype(np.float32) for T in Ts]
+        else:
+            self.frames = family_frames(rng, family, Ts, in_w)
         if exact_avg:
             # frame values m * lcm(1..D) / 2^k, m in 0..4: every running float sum over <= D frames and its quotient by
             # the length is exact in float, so the reference's float window average IS the exact mean (D <= 10)
@@ -77,7 +136,11 @@ class Case:
         self.ocfg = orc.config(**kw)
         self.olay = orc.Layout(self.ocfg)
         self.gcfg = scrf_amd.make_config(scratch_bytes=scratch_bytes, precision=precision, **kw)
+        if lam_scale is None:
+            lam_scale = 0.3 if family is None else 3.0 / (FAMILIES[family] * np.sqrt(self.F))
         self.lam = rng.normal(0, lam_scale, self.olay.lambda_len)
+        if family == "tied":
+            tie_twin_labels(self.lam, self.olay, self.ocfg.num_labs, max(1, num_states))
 
     def windows(self, u):
         """oracle window vectors of utterance u: [N_seg, F]"""

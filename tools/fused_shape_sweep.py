@@ -3,7 +3,9 @@ the materialised-window kernels (SCRF_FUSE=0) and, for small cases, against the 
 against the EXACT decode.  usage: python tools/fused_shape_sweep.py [n_shapes] [seed]
 SWEEP_PREC=3 runs the fused side under FASTLIN (bounds 1e-6 / 1e-8: its window average is the exact mean);
 SWEEP_LONG=1 appends a 260-frame utterance to every case (launches of few utterances then walk the posterior pass in
-segments: k_post_z's split form)."""
+segments: k_post_z's split form).
+SWEEP_FAMILY=signed|ranged|offset|tied draws the frames from that input family of tests/cases.py instead of U[0, 1), with
+the weights scaled to the data (the family's own lam_scale)."""
 import os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "asr-craft_amd", "python")); sys.path.insert(0, os.path.join(ROOT, "tests"))
@@ -14,6 +16,7 @@ from cases import Case
 n = int(sys.argv[1]) if len(sys.argv) > 1 else 40
 PREC = int(os.environ.get("SWEEP_PREC", "1"))
 LONG = os.environ.get("SWEEP_LONG", "0") == "1"
+FAMILY = os.environ.get("SWEEP_FAMILY") or None
 TOL_G, TOL_Z, TOL_O = (1e-9, 1e-11, 1e-8) if PREC == 1 else (1e-6, 1e-8, 1e-6)
 rng = np.random.RandomState(int(sys.argv[2]) if len(sys.argv) > 2 else 1)
 bad = 0
@@ -59,6 +62,8 @@ for i in range(n):
     Ts = [int(x) for x in rng.choice([1, 2, D - 1, D, D + 1, 2 * D + 3, 57, 130], size=int(rng.randint(1, 6)))]
     Ts = [max(1, t) for t in Ts] + ([260] if LONG else [])
     kw = dict(L=L, D=D, in_w=W, Ts=Ts, seed=1000 + i, lam_scale=0.2)
+    if FAMILY:
+        kw.update(family=FAMILY, lam_scale=None)
     try:
         ok = one(kw, D, W, L, Ts)
     except Exception as e:

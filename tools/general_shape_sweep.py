@@ -1,7 +1,9 @@
 """Random shapes through every training / decode path (GPU box): stdstate and stdtrans maps (context
 stream), EXACT / FAST / FAST32, tiny scratch budgets (many chunks), L up to 300 (multi-wavefront and
 generic recursions), D up to 45, wide streams.  Each case against the oracle (gradient, Zx, numerator;
-Viterbi labels and cost on one utterance).  usage: python tools/general_shape_sweep.py [n] [seed]"""
+Viterbi labels and cost on one utterance).  usage: python tools/general_shape_sweep.py [n] [seed]
+SWEEP_FAMILY=signed|ranged|offset|tied draws the frames from that input family of tests/cases.py instead of U[0, 1), with
+the weights scaled to the data (the family's own lam_scale)."""
 import os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "asr-craft_amd", "python")); sys.path.insert(0, os.path.join(ROOT, "tests"))
@@ -11,6 +13,7 @@ from cases import Case
 
 n = int(sys.argv[1]) if len(sys.argv) > 1 else 40
 rng = np.random.RandomState(int(sys.argv[2]) if len(sys.argv) > 2 else 1)
+FAMILY = os.environ.get("SWEEP_FAMILY") or None
 TOL = {0: (1e-10, 1e-12), 1: (1e-9, 1e-11), 2: (5e-5, 1e-5)}   # gradient (relative to its max), Zx and numerator; contract 1e-4
 
 
@@ -60,6 +63,8 @@ for i in range(n):
         Ts = [max(1, int(x)) for x in rng.choice([1, 2, 3, 9, 40], size=nu)]
     kw = dict(L=L, D=D, in_w=W, Ts=Ts, seed=2000 + i, lam_scale=0.05, trans_ctx=(int(ctx) if ctx > 0 else (0 if frame else None)),
               frame_model=bool(frame))
+    if FAMILY:
+        kw.update(family=FAMILY, lam_scale=None)
     tag = ("frame " if frame else "") + "D=%d W=%d L=%d ctx=%s prec=%d scratch=%d Ts=%s" % (D, W, L, kw["trans_ctx"], prec, scratch, Ts)
     try:
         ok, msg = one(kw, prec, scratch)
