@@ -1933,11 +1933,29 @@ __global__ __launch_bounds__(FE_NT, 2) void k_expf_fused(ScrfFusedArgs fa, ScrfL
 // Outputs: slab[block][o][(3 - G0) W] and dslab[block][o][D + bias].
 #define FW_NT 512
 #define FW_DSL 5        // duration slots: producer threads 0..239 = (ol = ptid % 48, ds = ptid / 48)
+#ifndef FW_DMA_NT
+#define FW_DMA_NT 1     // cache policy of the R tile's LDS-DMA loads: 1 = nt (R is read once, as on the register path)
+#endif
+#if FW_DMA_NT
+#define FW_DMA_POL " nt"
+#else
+#define FW_DMA_POL ""
+#endif
+// One 16-byte LDS-DMA load per lane: memory at sbase + voff -> LDS at lds + 16 lane (lds wave-uniform, in m0).  Written
+// as an instruction rather than through __builtin_amdgcn_global_load_lds: with the builtin the compiler drains
+// vmcnt(0) at the next use of every ordinary load while a DMA is pending -- the window scans' 25 loads, which it
+// otherwise consumes one by one behind counted waits, then sit behind one full wait, and a second one precedes their
+// issue.  The caller owns the wait: s_waitcnt vmcnt(0) before the barrier that hands the image to its readers.
+__device__ __forceinline__ void fw_dma16(uint32_t voff, const void* sbase, uint32_t lds) {
+  uint32_t keep;
+  asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2" FW_DMA_POL "\n\ts_mov_b32 m0, %0"
+               : "=&s"(keep) : "v"(voff), "s"(sbase), "s"(lds) : "memory");
+}
 // ROWS = window rows per tile (76, or 100 where the two image pairs still fit 160 KB: fewer tiles, fewer barriers and
 // producer round trips per row); NKS = ceil(rows used / 4).
 // (register cap 208 for the narrow forms: two such wavefronts per SIMD leave 96 registers per lane, which is what lets
 // the narrow k_ztf of the side stream -- 64 registers -- be resident on the same SIMD)
-template <int NT, int DMAX, int NKS, int G0, int ROWS>
+template <int NT, int DMAX, int NKS, int G0, int ROWS, int DMA>
 __device__ __forceinline__ void expf_fused_ws_body(const ScrfFusedArgs& fa, const ScrfLayout& lay, const double* __restrict__ R,
                                                    uint32_t n_out, uint64_t n_tiles, uint32_t n_ct,
                                                    double* __restrict__ slab, double* __restrict__ dslab) {
@@ -1946,7 +1964,8 @@ __device__ __forceinline__ void expf_fused_ws_body(const ScrfFusedArgs& fa, cons
   constexpr uint32_t xs = (NT == 4 ? 5 : NT <= 7 ? 9 : 13) * 16;
   constexpr uint32_t XB = (ROWS + 1) * xs;   // floats per column image (row ROWS: dump row)
   constexpr uint32_t RB = ROWS * FE_RS;
-  constexpr int NRP = (ROWS * 48 + 255) / 256;   // R elements per producer thread      // doubles per R image
+  constexpr int NRP = (ROWS * 48 + 255) / 256;   // R elements per producer thread (register path)
+  constexpr int NDQ = (ROWS * 24 + 255) / 256;   // 16-byte chunks of the R image per producer thread (DMA path)
   float* Xs0 = (float*)fsm;                     // [2][XB]
   double* Rs0 = (double*)(Xs0 + 2 * XB);        // [2][RB]
   const uint32_t tid = threadIdx.x, lane = tid & 63;
@@ -1983,6 +2002,7 @@ __device__ __forceinline__ void expf_fused_ws_body(const ScrfFusedArgs& fa, cons
   for (int q = 0; q < NDA; q++) da[q] = 0.0;
   const uint32_t dol = ptid % 48, dsl = ptid / 48;
   uint32_t ct0 = 0, cnfr = 0, cr0 = 0;     // frames and first row of the tile whose images the consumers hold
+  uint32_t pnr0 = 0, pnr1 = 0;             // DMA: rows the tile staged last into image 0 / 1 had
   auto dur_sums = [&](uint32_t buf) {
     if (ptid >= 48 * FW_DSL || blockIdx.z != 0) return;
     const double* Rs = Rs0 + buf * RB + dol;
@@ -2014,7 +2034,37 @@ __device__ __forceinline__ void expf_fused_ws_body(const ScrfFusedArgs& fa, cons
       asm volatile("" : "+v"(ti));   // a vector load: a scalar one would wait with the LDS traffic below
       dn = fa.tiles[ti];
     }
-    double rp[NRP];
+    double rp[DMA ? 1 : NRP];
+    if (DMA) {
+      // The R tile goes from memory to the image without passing through registers: 16-byte chunk c = ptid + 256 q of
+      // the image is (row c / 24, output pair c % 24), and the 64 chunks of a wavefront's q-th load are 1 KB of the image
+      // in lane order -- the form an LDS-DMA load writes (wave-uniform base + 16 lane).  The source address is the
+      // lane's own, so any n_out works as long as the pairs are 16-byte aligned (n_out even; the launcher checks).
+      // The DMA writes rows [0, nrows) x outputs [0, n_out - o0) only: the columns past n_out keep the zeros of the
+      // kernel's start, and the rows the image's previous tile had beyond this one's are zeroed here with ordinary
+      // stores.  Nothing else in this phase touches the image (the scans write the column image, the duration sums
+      // read the other pair), so the loads need no wait before the one at the end of the build.
+      const uint32_t prev = buf ? pnr1 : pnr0;
+      if (buf) pnr1 = ft.nrows; else pnr0 = ft.nrows;
+      if (ft.nrows < prev) {
+#pragma unroll
+        for (int q = 0; q < NDQ; q++) {
+          const uint32_t c = ptid + 256 * q, row = c / 24;
+          if (row >= ft.nrows && row < prev) *(v2f64*)(Rs + 2 * c) = (v2f64){0.0, 0.0};
+        }
+      }
+      const double* Rt = R + ft.row0 * n_out + o0;                // uniform base, 32-bit lane offset
+      const uint32_t rowb = n_out * 8u, npr = (n_out - o0 + 1) >> 1;
+      // the wavefront's 1 KB piece of chunks [256 q, 256 q + 256)
+      const uint32_t Rw = __builtin_amdgcn_readfirstlane((uint32_t)(uintptr_t)(__attribute__((address_space(3))) void*)Rs + (ptid & ~63u) * 16u);
+#pragma unroll
+      for (int q = 0; q < NDQ; q++) {
+        const uint32_t c = ptid + 256 * q, row = c / 24, pr = c - row * 24;
+        if (FU_ABL != 5 && row < ft.nrows && pr < npr) fw_dma16(row * rowb + pr * 16u, Rt, Rw + q * 4096u);
+      }
+      // the duration sums of the tile the consumers hold run under the loads just requested
+      if (sum_buf < 2) dur_sums(sum_buf);
+    } else {
 #pragma unroll
     for (int q = 0; q < NRP; q++) {
       const uint32_t e = ptid + 256 * q, row = e / 48, ol = e % 48;
@@ -2024,6 +2074,7 @@ __device__ __forceinline__ void expf_fused_ws_body(const ScrfFusedArgs& fa, cons
     }
     // the duration sums of the tile the consumers hold run under the loads just requested
     if (sum_buf < 2) dur_sums(sum_buf);
+    }
     // avg | max | min: task = (statistic, frame, column), values straight from the raw frames in memory.  A thread
     // takes tasks ptid and ptid + 256 together: both tasks' loads are in flight at once (one memory round trip per
     // tile instead of two).  (Interleaving the two scan chains by hand, so that the wave always has a second
@@ -2102,10 +2153,15 @@ __device__ __forceinline__ void expf_fused_ws_body(const ScrfFusedArgs& fa, cons
         }
       }
     }
+    if (DMA) {
+      // the DMAs have landed before the tile's barrier: the consumers read the image one phase later
+      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    } else {
 #pragma unroll
-    for (int q = 0; q < NRP; q++) {
-      const uint32_t e = ptid + 256 * q, row = e / 48, ol = e % 48;
-      if (row < ROWS) Rs[row * FE_RS + ol] = rp[q];
+      for (int q = 0; q < NRP; q++) {
+        const uint32_t e = ptid + 256 * q, row = e / 48, ol = e % 48;
+        if (row < ROWS) Rs[row * FE_RS + ol] = rp[q];
+      }
     }
     return ft;
   };
@@ -2183,20 +2239,20 @@ __device__ __forceinline__ void expf_fused_ws_body(const ScrfFusedArgs& fa, cons
   }
 }
 
-template <int NT, int DMAX, int NKS, int G0, int ROWS>
+template <int NT, int DMAX, int NKS, int G0, int ROWS, int DMA>
 __global__ __launch_bounds__(FW_NT, 2) void k_expf_fused_ws(ScrfFusedArgs fa, ScrfLayout lay, const double* __restrict__ R, uint32_t n_out,
                                                             uint64_t n_tiles, uint32_t n_ct, double* __restrict__ slab,
                                                             double* __restrict__ dslab) {
-  expf_fused_ws_body<NT, DMAX, NKS, G0, ROWS>(fa, lay, R, n_out, n_tiles, n_ct, slab, dslab);
+  expf_fused_ws_body<NT, DMAX, NKS, G0, ROWS, DMA>(fa, lay, R, n_out, n_tiles, n_ct, slab, dslab);
 }
 // the same with 208 registers per wavefront (the attribute wants a literal, hence the second entry point): two such
 // wavefronts per SIMD leave 96 registers per lane, which lets the narrow k_ztf of the side stream (64) be resident on
 // the same SIMD while this kernel owns the CU
-template <int NT, int DMAX, int NKS, int G0, int ROWS>
+template <int NT, int DMAX, int NKS, int G0, int ROWS, int DMA>
 __global__ __launch_bounds__(FW_NT) __attribute__((amdgpu_num_vgpr(208))) void k_expf_fused_ws_n(
     ScrfFusedArgs fa, ScrfLayout lay, const double* __restrict__ R, uint32_t n_out, uint64_t n_tiles, uint32_t n_ct,
     double* __restrict__ slab, double* __restrict__ dslab) {
-  expf_fused_ws_body<NT, DMAX, NKS, G0, ROWS>(fa, lay, R, n_out, n_tiles, n_ct, slab, dslab);
+  expf_fused_ws_body<NT, DMAX, NKS, G0, ROWS, DMA>(fa, lay, R, n_out, n_tiles, n_ct, slab, dslab);
 }
 
 // column tiles needed, and the row stride of the kernel instantiation that serves them (NCT * 16)
@@ -2252,10 +2308,20 @@ static bool fused_expf_ws_fits(uint32_t W, int g0, int zb) {
   return n_ct <= 13 && fused_expf_ws_smem_rows(W, g0, zb, FE_ROWS) <= 160 * 1024;
 }
 static int fused_expf_ws_zb(uint32_t W, int g0) { return !fused_expf_ws_fits(W, g0, 0) && fused_expf_ws_fits(W, g0, 1) ? 1 : 0; }
+// The R tiles go to LDS by DMA (16-byte pieces) when every output pair of R is 16-byte aligned: an even row length
+// (and an aligned base, checked at the launch); odd L keeps the register path.  SCRF_EXPF_DMA=0 forces the register
+// path (A/B measurements, tests).
+static bool fused_expf_dma(uint32_t L) {
+  static const bool on = !(getenv("SCRF_EXPF_DMA") && atoi(getenv("SCRF_EXPF_DMA")) == 0);
+  return on && !(L & 1);
+}
 static uint32_t fused_expf_ws_rows(uint32_t W, int g0) {
-  // 100-row tiles take 232 registers per wavefront, 76-row tiles 212: only the latter leaves room on a SIMD for the
-  // side stream's narrow k_ztf (64), and with that overlap the 76-row form is the faster step (29.22 against 29.46 ms;
-  // without the side stream 29.54 against 29.43).  So: tall tiles only when the side stream is off.
+  // Tall tiles only when the side stream is off, or on request (SCRF_EXPF_BIG=1).  On the register path 100-row tiles
+  // take 245 registers and cannot share a SIMD with the side stream's narrow k_ztf (29.22 against 29.46 ms for the
+  // 76-row form with that overlap; without the side stream 29.54 against 29.43).  On the DMA path both heights fit
+  // beside k_ztf (178 / 184 registers) and the tall form is the faster kernel (5.8 against 6.3 ms), but a 100-row tile
+  // list deals other rows to each workgroup's slab, so the counts come out in another summation order (2e-15 relative
+  // on the weights after five steps): the default keeps the order the 76-row list gives.
   static const bool side = !(getenv("SCRF_SIDE") && atoi(getenv("SCRF_SIDE")) == 0);
   static const bool big = getenv("SCRF_EXPF_BIG") ? atoi(getenv("SCRF_EXPF_BIG")) != 0 : !side;
   uint32_t n_ct;
@@ -2307,19 +2373,25 @@ uint32_t fused_expf_blocks(const ScrfLayout& lay, uint32_t W, int f32, uint64_t 
   return (uint32_t)(n_tiles < cap ? n_tiles : cap);
 }
 
-template <int NT, int DMAX, int NKS, int G0, int ROWS>
-static void launch_expf_ws_t(hipStream_t st, const ScrfFusedArgs& fa, const ScrfLayout& lay, const double* R, uint64_t n_tiles,
+template <int NT, int DMAX, int NKS, int G0, int ROWS, int DMA>
+static void launch_expf_ws_d(hipStream_t st, const ScrfFusedArgs& fa, const ScrfLayout& lay, const double* R, uint64_t n_tiles,
                              uint32_t n_ct, double* slab, double* dslab) {
   const int zb = fused_expf_ws_zb(fa.W, G0);
   dim3 grid(fused_expf_blocks(lay, fa.W, 0, n_tiles, G0), (lay.L + 47) / 48, zb ? 3 - G0 : 1);
   const size_t smw = fused_expf_ws_smem_rows(fa.W, G0, zb, ROWS);
   if (NT <= 4) {   // the narrow forms leave room for the side stream's kernels
-    hipFuncSetAttribute((const void*)k_expf_fused_ws_n<NT, DMAX, NKS, G0, ROWS>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smw);
-    hipLaunchKernelGGL((k_expf_fused_ws_n<NT, DMAX, NKS, G0, ROWS>), grid, dim3(FW_NT), smw, st, fa, lay, R, lay.L, n_tiles, n_ct, slab, dslab);
+    hipFuncSetAttribute((const void*)k_expf_fused_ws_n<NT, DMAX, NKS, G0, ROWS, DMA>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smw);
+    hipLaunchKernelGGL((k_expf_fused_ws_n<NT, DMAX, NKS, G0, ROWS, DMA>), grid, dim3(FW_NT), smw, st, fa, lay, R, lay.L, n_tiles, n_ct, slab, dslab);
     return;
   }
-  hipFuncSetAttribute((const void*)k_expf_fused_ws<NT, DMAX, NKS, G0, ROWS>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smw);
-  hipLaunchKernelGGL((k_expf_fused_ws<NT, DMAX, NKS, G0, ROWS>), grid, dim3(FW_NT), smw, st, fa, lay, R, lay.L, n_tiles, n_ct, slab, dslab);
+  hipFuncSetAttribute((const void*)k_expf_fused_ws<NT, DMAX, NKS, G0, ROWS, DMA>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smw);
+  hipLaunchKernelGGL((k_expf_fused_ws<NT, DMAX, NKS, G0, ROWS, DMA>), grid, dim3(FW_NT), smw, st, fa, lay, R, lay.L, n_tiles, n_ct, slab, dslab);
+}
+template <int NT, int DMAX, int NKS, int G0, int ROWS>
+static void launch_expf_ws_t(hipStream_t st, const ScrfFusedArgs& fa, const ScrfLayout& lay, const double* R, uint64_t n_tiles,
+                             uint32_t n_ct, double* slab, double* dslab) {
+  if (fused_expf_dma(lay.L) && ((uintptr_t)R & 15) == 0) launch_expf_ws_d<NT, DMAX, NKS, G0, ROWS, 1>(st, fa, lay, R, n_tiles, n_ct, slab, dslab);
+  else launch_expf_ws_d<NT, DMAX, NKS, G0, ROWS, 0>(st, fa, lay, R, n_tiles, n_ct, slab, dslab);
 }
 
 template <int NT, int DMAX, int F32, int NKS>
