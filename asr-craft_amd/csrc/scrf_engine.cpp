@@ -180,6 +180,14 @@ struct scrf_engine_s {
   scrf_batch lp_batch = nullptr;   // the batch of the valid result, or nullptr
   std::vector<uint64_t> lp_off;    // [U + 1] host image of the offsets
   uint64_t n_lp_calls = 0, n_lp_chunks = 0;
+  // scrf_align_batch: the transcripts of the call on the device (phones | phone_off, back-pointer offsets),
+  // kept across calls; al_bp_off is the host image chunk_layout sizes a chunk's back pointers with
+  bool align_wave = true;   // SCRF_ALIGN_WAVE=0: every chunk through the workgroup kernel (same results)
+  uint32_t* al_ph = nullptr;
+  uint64_t* al_off = nullptr;
+  uint64_t al_cap_ph = 0, al_cap_u = 0;
+  std::vector<uint64_t> al_bp_off;
+  uint64_t n_al_calls = 0, n_al_chunks = 0, n_al_wave = 0, n_al_group = 0;   // calls; searches launched, and by which kernel
   std::string err;
   // per-kernel HIP-event times of the last timed call (scrf_kernel_timing)
   struct KTime { std::string name; double ms; uint32_t n; };
@@ -373,6 +381,7 @@ extern "C" int scrf_create(const scrf_config* cfg, scrf_handle* out) {
   if (const char* e = getenv("SCRF_LINDP")) h->lin_dp = atoi(e) != 0;
   if (const char* e = getenv("SCRF_POSTOCC_SPLIT")) h->post_split = atoi(e) != 0;
   if (const char* e = getenv("SCRF_FAST_DECODE")) h->fast_decode = atoi(e) != 0;
+  if (const char* e = getenv("SCRF_ALIGN_WAVE")) h->align_wave = atoi(e) != 0;
   if (const char* e = getenv("SCRF_BATCH_POOL")) { h->pool_on = atoi(e) != 0; h->pool_up = atoi(e) != 2; }
   if (const char* e = getenv("SCRF_HYBRID")) { h->hybrid = atoi(e) != 0; h->hybrid_first = atoi(e) == 2; }
   if (const char* e = getenv("SCRF_DECODE_BOUND_SCALE")) h->decode_bound_factor = std::max(1.0, atof(e));   // widening only: < 1 would void the bound
@@ -467,6 +476,7 @@ extern "C" int scrf_destroy(scrf_handle h) {
   if (h->ev_fork) hipEventDestroy(h->ev_fork);
   if (h->ev_join) hipEventDestroy(h->ev_join);
   hipFree(h->dec_lab); hipFree(h->dec_n); hipFree(h->dec_cost);
+  hipFree(h->al_ph); hipFree(h->al_off);
   hipFree(h->post_buf);
   hipFree(h->lp_arcs); hipFree(h->lp_meta);
   if (h->dec_hlab) hipHostFree(h->dec_hlab);
@@ -1095,12 +1105,14 @@ struct ChunkBufs {
   ScrfLatBufs lat = {nullptr, nullptr, nullptr, nullptr, nullptr};   // lattice beam: distances of the chunk's states
   uint32_t* lat_counts = nullptr;   // [nodes of the chunk] kept arcs per node
   uint64_t* lat_node_off = nullptr; // [nodes + 1]
+  uint16_t* al_bp = nullptr;        // forced alignment: sum of T * K back pointers over the chunk's transcripts that fit
   bool lamT_ready = false;   // sparse maps: h->d_lamT already re-laid for this call (scrf_fb_batch: once, before the lanes fork)
 };
 
 // ponly (scrf_posteriors_batch): the recursion of the training path without anything that needs labels or feeds the
 // gradient -- the linear-domain vectors (or alpha_dur / beta) and the per-frame state mass, no count buffers
-struct Need { bool fb, post, beta, vit; bool fused = false; bool vitfast = false; bool la = false; bool hybrid = false; bool ponly = false; bool plog = false; bool lat = false; };
+struct Need { bool fb, post, beta, vit; bool fused = false; bool vitfast = false; bool la = false; bool hybrid = false; bool ponly = false; bool plog = false; bool lat = false; bool align = false; };
+// align (scrf_align_batch): the back pointers of the chunk's (frame, transcript position) cells
 // lat (scrf_lattice_prune_batch): four distance arrays over the chunk's frames and the node counts / offsets
 // plog: ponly through the log-domain recursion (SCRF_PREC_EXACT)
 static bool need_lin(const Need& nd) { return nd.post || (nd.ponly && !nd.plog); }
@@ -1288,6 +1300,7 @@ static void chunk_layout(scrf_handle h, scrf_batch b, uint32_t u0, uint32_t u1, 
     cb->lat_counts = a.take<uint32_t>(nfr + nutt);
     cb->lat_node_off = a.take<uint64_t>(nfr + nutt + 1);
   }
+  if (nd.align) cb->al_bp = a.take<uint16_t>(h->al_bp_off[u1] - h->al_bp_off[u0]);
 }
 
 // (*tmp takes the walk's pointers, which a measurement does not use: the planner passes the same one for every candidate)
@@ -2855,13 +2868,63 @@ extern "C" int scrf_lattice_prune_stats(scrf_handle h, uint64_t* n_calls, uint64
   return SCRF_OK;
 }
 
-extern "C" int scrf_viterbi_batch(scrf_handle h, scrf_batch b, uint32_t* seg_labels, uint64_t max_labels,
-                                  uint64_t* lab_off, float* best_cost) {
-  if (!h || !b || !seg_labels || !lab_off) return SCRF_ERR_INVALID;
-  HIPCHK(h, hipSetDevice(h->device));
+// The chunk loop of the decode entry points of the one-state models (scrf_viterbi_batch, scrf_align_batch); only the search
+// differs.  Fast decode: the fused score kernel writes the float arc weights (cb.Wn) and lists the entries whose
+// rounding it cannot guarantee; those are recomputed in reference order.  A chunk whose list
+// overflows (pathological cancellation) goes through the EXACT path (cb.S) instead.
+// search(cb, u0, u1, fast) launches the search of chunk [u0, u1) on the engine stream.
+template <class Search>
+static int decode_chunks(scrf_handle h, scrf_batch b, const Need& nd, Search&& search) {
   const ScrfLayout& l = h->lay;
   const bool frame_model = h->cfg.model_type == SCRF_STDFRAME;
-  CallTimer call(h);
+  Need ndf = nd;
+  ndf.fused = ndf.vitfast = true;
+  const bool fast = h->fast_decode && b->fused_ok && !b->mixed && h->fuse_windows && !frame_model && l.L <= 0xffff;
+  int rc = SCRF_OK;
+  for (uint32_t u0 = 0; u0 < b->U && rc == SCRF_OK;) {
+    uint32_t u_end = u0;
+    if (fast) {
+      const uint32_t u1 = plan_chunk(h, b, u0, ndf);
+      ChunkBufs cb;
+      rc = carve(h, b, u0, u1, ndf, &cb);
+      if (rc != SCRF_OK) break;
+      ensure_m0(h, cb.st);
+      rc = run_scores(h, b, u0, u1, cb);
+      if (rc != SCRF_OK) break;
+      uint32_t n_fix = 0;
+      HIPCHK(h, hipMemcpyAsync(&n_fix, cb.fix_cnt, sizeof(uint32_t), hipMemcpyDeviceToHost, h->stream));
+      HIPCHK(h, hipStreamSynchronize(h->stream));
+      h->n_decode_fix += n_fix;
+      if (n_fix <= cb.fix_cap) {
+        PhaseTimer tm(h, PH_VIT);
+        launch_decode_fixup(h->stream, b->d_frames[0], b->recipe[0].in_width, b->view(), u0, u1, h->d_lambda, l, cb.fix_cnt,
+                            cb.fix_list, std::min(n_fix, cb.fix_cap), cb.Wn);
+        search(cb, u0, u1, true);
+        tm.stop(2);
+        u0 = u1;
+        continue;
+      }
+      h->n_decode_fallback++;
+      u_end = u1;  // this range again, through the EXACT path
+    }
+    do {
+      const uint32_t u1 = std::min(fast ? u_end : b->U, plan_chunk(h, b, u0, nd));
+      ChunkBufs cb;
+      rc = carve(h, b, u0, u1, nd, &cb);
+      if (rc != SCRF_OK) break;
+      rc = run_scores(h, b, u0, u1, cb);
+      if (rc != SCRF_OK) break;
+      PhaseTimer tm(h, PH_VIT);
+      search(cb, u0, u1, false);
+      tm.stop(1);
+      u0 = u1;
+    } while (fast && u0 < u_end && rc == SCRF_OK);
+  }
+  return rc;
+}
+
+// the result buffers of the decode entry points (dec_*) hold this batch
+static int decode_result_room(scrf_handle h, scrf_batch b) {
   const uint64_t NF = b->frame_off[b->U];
   if (NF > h->dec_cap_f) {
     hipFree(h->dec_lab); h->dec_lab = nullptr;
@@ -2882,16 +2945,43 @@ extern "C" int scrf_viterbi_batch(scrf_handle h, scrf_batch b, uint32_t* seg_lab
     HIPCHK(h, hipHostMalloc((void**)&h->dec_hcost, sizeof(float) * b->U, hipHostMallocDefault));
     h->dec_cap_u = b->U;
   }
+  return SCRF_OK;
+}
+
+// labels, counts and costs of the whole batch to the caller, through the pinned images; closes the timed region
+static int decode_result_fetch(scrf_handle h, scrf_batch b, const char* fn, CallTimer& call, uint32_t* seg_labels, uint64_t max_labels,
+                               uint64_t* lab_off, float* best_cost) {
+  const uint64_t NF = b->frame_off[b->U];
+  const uint32_t *lab = h->dec_hlab, *cnt = h->dec_hn;
+  hipError_t e = hipMemcpyAsync(h->dec_hlab, h->dec_lab, sizeof(uint32_t) * NF, hipMemcpyDeviceToHost, h->stream);
+  if (e == hipSuccess) e = hipMemcpyAsync(h->dec_hn, h->dec_n, sizeof(uint32_t) * b->U, hipMemcpyDeviceToHost, h->stream);
+  if (e == hipSuccess && best_cost) e = hipMemcpyAsync(h->dec_hcost, h->dec_cost, sizeof(float) * b->U, hipMemcpyDeviceToHost, h->stream);
+  if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
+  if (e != hipSuccess) return fail(h, SCRF_ERR_HIP, "%s: %s", fn, hipGetErrorString(e));
+  if (best_cost) memcpy(best_cost, h->dec_hcost, sizeof(float) * b->U);
+  call.stop();
+  uint64_t pos = 0;
+  for (uint32_t u = 0; u < b->U; u++) {
+    lab_off[u] = pos;
+    if (pos + cnt[u] > max_labels) return fail(h, SCRF_ERR_INVALID, "%s: seg_labels capacity %llu too small", fn, (unsigned long long)max_labels);
+    memcpy(seg_labels + pos, &lab[b->frame_off[u]], sizeof(uint32_t) * cnt[u]);
+    pos += cnt[u];
+  }
+  lab_off[b->U] = pos;
+  return SCRF_OK;
+}
+
+extern "C" int scrf_viterbi_batch(scrf_handle h, scrf_batch b, uint32_t* seg_labels, uint64_t max_labels,
+                                  uint64_t* lab_off, float* best_cost) {
+  if (!h || !b || !seg_labels || !lab_off) return SCRF_ERR_INVALID;
+  HIPCHK(h, hipSetDevice(h->device));
+  const ScrfLayout& l = h->lay;
+  const bool frame_model = h->cfg.model_type == SCRF_STDFRAME;
+  CallTimer call(h);
+  int rc = decode_result_room(h, b);
+  if (rc != SCRF_OK) return rc;
   uint32_t *d_lab = h->dec_lab, *d_n = h->dec_n;
   float* d_cost = h->dec_cost;
-  Need nd{false, false, false, true};
-  // fast decode: the fused score kernel writes the float arc weights and lists the entries whose
-  // rounding it cannot guarantee; those are recomputed in reference order.  A chunk whose list
-  // overflows (pathological cancellation) goes through the EXACT path instead.
-  Need ndf = nd;
-  ndf.fused = ndf.vitfast = true;
-  const bool fast = h->fast_decode && b->fused_ok && !b->mixed && h->fuse_windows && !frame_model && l.L <= 0xffff;
-  int rc = SCRF_OK;
   if (nstate(h) || stdseg(h)) {
     // the chunk's scores in the scratch arena (chunks planned with the `post` sizing), path costs and back pointers per
     // (row, label) in buffers of their own
@@ -2916,70 +3006,111 @@ extern "C" int scrf_viterbi_batch(scrf_handle h, scrf_batch b, uint32_t* seg_lab
       u0 = u1;
     }
   }
-  for (uint32_t u0 = 0; u0 < b->U && rc == SCRF_OK && !stdseg(h) && !nstate(h);) {
-    uint32_t u_end = u0;
-    if (fast) {
-      const uint32_t u1 = plan_chunk(h, b, u0, ndf);
-      ChunkBufs cb;
-      rc = carve(h, b, u0, u1, ndf, &cb);
-      if (rc != SCRF_OK) break;
-      ensure_m0(h, cb.st);
-      rc = run_scores(h, b, u0, u1, cb);
-      if (rc != SCRF_OK) break;
-      uint32_t n_fix = 0;
-      HIPCHK(h, hipMemcpyAsync(&n_fix, cb.fix_cnt, sizeof(uint32_t), hipMemcpyDeviceToHost, h->stream));
-      HIPCHK(h, hipStreamSynchronize(h->stream));
-      h->n_decode_fix += n_fix;
-      if (n_fix <= cb.fix_cap) {
-        PhaseTimer tm(h, PH_VIT);
-        launch_decode_fixup(h->stream, b->d_frames[0], b->recipe[0].in_width, b->view(), u0, u1, h->d_lambda, l, cb.fix_cnt,
-                            cb.fix_list, std::min(n_fix, cb.fix_cap), cb.Wn);
-        if (viterbi_fast_supported(l))
-          launch_viterbi_fast(h->stream, l, b->view(), u0, u1 - u0, cb.Wn, cb.M, cb.bp_b, cb.bp_e, d_lab, d_n, d_cost);
-        else
-          launch_viterbi(h->stream, l, b->view(), u0, u1 - u0, nullptr, cb.M, cb.m_per_frame, 0, cb.bp_b, cb.bp_e, d_lab, d_n,
-                         d_cost, cb.Wn);
-        tm.stop(2);
-        u0 = u1;
-        continue;
-      }
-      h->n_decode_fallback++;
-      u_end = u1;  // this range again, through the EXACT path
-    }
-    do {
-      const uint32_t u1 = std::min(fast ? u_end : b->U, plan_chunk(h, b, u0, nd));
-      ChunkBufs cb;
-      rc = carve(h, b, u0, u1, nd, &cb);
-      if (rc != SCRF_OK) break;
-      rc = run_scores(h, b, u0, u1, cb);
-      if (rc != SCRF_OK) break;
-      PhaseTimer tm(h, PH_VIT);
-      if (segtrans(h)) launch_viterbi_segtrans(h->stream, l, b->view(), u0, u1 - u0, cb.S, cb.M, cb.bp_b, cb.bp_e, d_lab, d_n, d_cost);
+  else
+    rc = decode_chunks(h, b, Need{false, false, false, true}, [&](const ChunkBufs& cb, uint32_t u0, uint32_t u1, bool fast) {
+      if (fast && viterbi_fast_supported(l))
+        launch_viterbi_fast(h->stream, l, b->view(), u0, u1 - u0, cb.Wn, cb.M, cb.bp_b, cb.bp_e, d_lab, d_n, d_cost);
+      else if (fast)
+        launch_viterbi(h->stream, l, b->view(), u0, u1 - u0, nullptr, cb.M, cb.m_per_frame, 0, cb.bp_b, cb.bp_e, d_lab, d_n,
+                       d_cost, cb.Wn);
+      else if (segtrans(h)) launch_viterbi_segtrans(h->stream, l, b->view(), u0, u1 - u0, cb.S, cb.M, cb.bp_b, cb.bp_e, d_lab, d_n, d_cost);
       else launch_viterbi(h->stream, l, b->view(), u0, u1 - u0, cb.S, cb.M, cb.m_per_frame, frame_model, cb.bp_b, cb.bp_e,
                           d_lab, d_n, d_cost);
-      tm.stop(1);
-      u0 = u1;
-    } while (fast && u0 < u_end && rc == SCRF_OK);
-  }
-  const uint32_t *lab = h->dec_hlab, *cnt = h->dec_hn;
-  if (rc == SCRF_OK) {
-    hipError_t e = hipMemcpyAsync(h->dec_hlab, d_lab, sizeof(uint32_t) * NF, hipMemcpyDeviceToHost, h->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(h->dec_hn, d_n, sizeof(uint32_t) * b->U, hipMemcpyDeviceToHost, h->stream);
-    if (e == hipSuccess && best_cost) e = hipMemcpyAsync(h->dec_hcost, d_cost, sizeof(float) * b->U, hipMemcpyDeviceToHost, h->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
-    if (e != hipSuccess) rc = fail(h, SCRF_ERR_HIP, "scrf_viterbi_batch: %s", hipGetErrorString(e));
-    else if (best_cost) memcpy(best_cost, h->dec_hcost, sizeof(float) * b->U);
-  }
+    });
   if (rc != SCRF_OK) return rc;
-  call.stop();
-  uint64_t pos = 0;
-  for (uint32_t u = 0; u < b->U; u++) {
-    lab_off[u] = pos;
-    if (pos + cnt[u] > max_labels) return fail(h, SCRF_ERR_INVALID, "scrf_viterbi_batch: seg_labels capacity %llu too small", (unsigned long long)max_labels);
-    memcpy(seg_labels + pos, &lab[b->frame_off[u]], sizeof(uint32_t) * cnt[u]);
-    pos += cnt[u];
+  return decode_result_fetch(h, b, "scrf_viterbi_batch", call, seg_labels, max_labels, lab_off, best_cost);
+}
+
+// ---------------------------------------------------------------------------------------------
+// batched forced alignment: scrf_viterbi_batch's chunk loop and score stage, a constrained search
+// ---------------------------------------------------------------------------------------------
+extern "C" int scrf_align_batch(scrf_handle h, scrf_batch b, const uint32_t* phones, const uint64_t* phone_off, int mode,
+                                uint32_t* seg_labels, uint64_t max_labels, uint64_t* lab_off, float* cost) {
+  if (!h || !b || !phone_off || !seg_labels || !lab_off) return SCRF_ERR_INVALID;
+  if (h->cfg.model_type == SCRF_STDSEG || h->cfg.model_type == SCRF_STDSEG_NO_DUR)
+    return fail(h, SCRF_ERR_INVALID, "scrf_align_batch: forced alignment is not built for the \"%s\" CRF model; use \"stdframe\", "
+                "\"stdseg_no_dur_no_transftr\" or \"stdseg_no_dur_no_segtransftr\"", model_type_name(h->cfg.model_type));
+  if (h->cfg.num_states > 1)
+    return fail(h, SCRF_ERR_INVALID, "scrf_align_batch: forced alignment is built for crf_states = 1 only (this \"%s\" model has crf_states = %u)",
+                model_type_name(h->cfg.model_type), h->cfg.num_states);
+  if (mode != SCRF_ALIGN_ONE && mode != SCRF_ALIGN_RUNS)
+    return fail(h, SCRF_ERR_INVALID, "scrf_align_batch: unknown mode %d (SCRF_ALIGN_ONE = 0, SCRF_ALIGN_RUNS = 1)", mode);
+  const ScrfLayout& l = h->lay;
+  if (l.D > 0x7fff)
+    return fail(h, SCRF_ERR_INVALID, "scrf_align_batch: maximum duration %u does not fit the 15 duration bits of a back pointer (at most %u)", l.D, 0x7fffu);
+  const uint32_t U = b->U;
+  const uint64_t NP = phone_off[U];
+  if (phone_off[0] != 0 || (NP && !phones)) return fail(h, SCRF_ERR_INVALID, "scrf_align_batch: phone_off must start at 0 and phones must be given");
+  // back-pointer cells before each utterance (the chunk planner sizes a chunk with them), the longest transcript the
+  // workgroup kernel may meet
+  const bool wave_on = h->align_wave && align_wave_supported(l);
+  h->al_bp_off.assign(U + 1, 0);
+  for (uint32_t u = 0; u < U; u++) {
+    if (phone_off[u + 1] < phone_off[u]) return fail(h, SCRF_ERR_INVALID, "scrf_align_batch: phone_off decreases at utterance %u", u);
+    const uint64_t K = phone_off[u + 1] - phone_off[u];
+    for (uint64_t k = phone_off[u]; k < phone_off[u + 1]; k++)
+      if (phones[k] >= l.L)
+        return fail(h, SCRF_ERR_INVALID, "scrf_align_batch: phone %u at position %llu of utterance %u's transcript (the model has %u)",
+                    phones[k], (unsigned long long)(k - phone_off[u]), u, l.L);
+    const bool fits = scrf_align_feasible(b->T[u], K, l.D, mode);
+    if (fits && (K > 64 || !wave_on) && align_group_smem_bytes(l, K) > 160 * 1024)
+      return fail(h, SCRF_ERR_INVALID, "scrf_align_batch: utterance %u's transcript of %llu phones needs (%u + 2) x %llu x 4 = %zu bytes of LDS, "
+                  "a workgroup has %d", u, (unsigned long long)K, l.D, (unsigned long long)K, align_group_smem_bytes(l, K), 160 * 1024);
+    h->al_bp_off[u + 1] = h->al_bp_off[u] + (fits ? (uint64_t)b->T[u] * K : 0);
   }
-  lab_off[b->U] = pos;
+  HIPCHK(h, hipSetDevice(h->device));
+  const bool frame_model = h->cfg.model_type == SCRF_STDFRAME;
+  CallTimer call(h);
+  int rc = decode_result_room(h, b);
+  if (rc != SCRF_OK) return rc;
+  // the transcripts and the two offset arrays, uploaded once per call into buffers kept across calls
+  if (NP > h->al_cap_ph) {
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    hipFree(h->al_ph); h->al_ph = nullptr; h->al_cap_ph = 0;
+    HIPCHK(h, hipMalloc((void**)&h->al_ph, sizeof(uint32_t) * NP));
+    h->al_cap_ph = NP;
+  }
+  if (U + 1 > h->al_cap_u) {
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    hipFree(h->al_off); h->al_off = nullptr; h->al_cap_u = 0;
+    HIPCHK(h, hipMalloc((void**)&h->al_off, sizeof(uint64_t) * 2 * (U + 1)));
+    h->al_cap_u = U + 1;
+  }
+  if (NP) HIPCHK(h, hipMemcpyAsync(h->al_ph, phones, sizeof(uint32_t) * NP, hipMemcpyHostToDevice, h->stream));
+  HIPCHK(h, hipMemcpyAsync(h->al_off, phone_off, sizeof(uint64_t) * (U + 1), hipMemcpyHostToDevice, h->stream));
+  HIPCHK(h, hipMemcpyAsync(h->al_off + (U + 1), h->al_bp_off.data(), sizeof(uint64_t) * (U + 1), hipMemcpyHostToDevice, h->stream));
+  HIPCHK(h, hipStreamSynchronize(h->stream));   // the host arrays are the caller's (and pageable)
+  h->n_al_calls++;
+  Need nd{false, false, false, false};
+  nd.align = true;
+  rc = decode_chunks(h, b, nd, [&](const ChunkBufs& cb, uint32_t u0, uint32_t u1, bool fast) {
+    const ScrfAlignArgs aa{h->al_ph, h->al_off, h->al_off + (U + 1), cb.al_bp, mode};
+    uint64_t k_max = 0;   // over the transcripts that fit
+    for (uint32_t u = u0; u < u1; u++)
+      if (h->al_bp_off[u + 1] > h->al_bp_off[u]) k_max = std::max(k_max, phone_off[u + 1] - phone_off[u]);
+    const double* S = fast ? nullptr : cb.S;
+    const float* Wn = fast ? cb.Wn : nullptr;
+    h->n_al_chunks++;
+    if (wave_on && k_max <= 64) {
+      h->n_al_wave++;
+      KT_RUN("k_align_wave", h->stream, launch_align_wave(h->stream, l, b->view(), u0, u1 - u0, S, Wn, cb.M, cb.m_per_frame, frame_model, aa,
+                                                          h->dec_lab, h->dec_n, h->dec_cost));
+    } else {
+      h->n_al_group++;
+      KT_RUN("k_align_group", h->stream, launch_align_group(h->stream, l, b->view(), u0, u1 - u0, (uint32_t)k_max, S, Wn, cb.M, cb.m_per_frame,
+                                                            frame_model, aa, h->dec_lab, h->dec_n, h->dec_cost));
+    }
+  });
+  if (rc != SCRF_OK) return rc;
+  return decode_result_fetch(h, b, "scrf_align_batch", call, seg_labels, max_labels, lab_off, cost);
+}
+
+extern "C" int scrf_align_stats(scrf_handle h, uint64_t* n_calls, uint64_t* n_chunks, uint64_t* n_wave, uint64_t* n_group) {
+  if (!h) return SCRF_ERR_INVALID;
+  if (n_calls) *n_calls = h->n_al_calls;
+  if (n_chunks) *n_chunks = h->n_al_chunks;
+  if (n_wave) *n_wave = h->n_al_wave;
+  if (n_group) *n_group = h->n_al_group;
   return SCRF_OK;
 }
 

@@ -290,4 +290,27 @@ void launch_lat_emit(hipStream_t st, const ScrfLayout& lay, ScrfBatchView bv, ui
                      const double* S, const double* M, int m_per_frame, int frame_model, const ScrfLatBufs& lb, double beam,
                      const uint64_t* node_off, uint64_t base, uint64_t cap, scrf_arc* out);
 
+// ---- forced alignment (scrf_align.hip)
+struct ScrfAlignArgs {
+  const uint32_t* phones;      // transcripts of the batch, back to back
+  const uint64_t* phone_off;   // [U + 1]
+  const uint64_t* bp_off;      // [U + 1] back-pointer cells before each utterance: T * K of every transcript that fits
+  uint16_t* bp;                // the chunk's cells; utterance u's start at bp_off[u] - bp_off[u0]
+  int mode;                    // scrf_align_mode
+};
+// does a transcript of K phones fit an utterance of T frames?  (host: sizes the back pointers; device: the same decision)
+__host__ __device__ inline bool scrf_align_feasible(uint32_t T, uint64_t K, uint32_t D, int mode) {
+  if (T == 0 || K == 0 || K > T) return false;
+  return mode != SCRF_ALIGN_ONE || K * D >= T;
+}
+int align_wave_supported(const ScrfLayout& lay);
+// S (fp64 scores) or Wn (their float arc weights, segment model only): exactly one is given
+void launch_align_wave(hipStream_t st, const ScrfLayout& lay, ScrfBatchView bv, uint32_t u0, uint32_t n_utts, const double* S,
+                       const float* Wn, const double* M, int m_per_frame, int frame_model, const ScrfAlignArgs& aa,
+                       uint32_t* out_labels, uint32_t* out_n, float* out_cost);
+size_t align_group_smem_bytes(const ScrfLayout& lay, uint64_t K);
+void launch_align_group(hipStream_t st, const ScrfLayout& lay, ScrfBatchView bv, uint32_t u0, uint32_t n_utts, uint32_t k_max,
+                        const double* S, const float* Wn, const double* M, int m_per_frame, int frame_model,
+                        const ScrfAlignArgs& aa, uint32_t* out_labels, uint32_t* out_n, float* out_cost);
+
 #endif  // SCRF_KERNELS_H_

@@ -25,7 +25,7 @@
 //   (with crf_posterior_log=1 only: the exponential of a log-partition of hundreds of nats is not a number a file can hold)
 //   the unnormalised form, log posterior + Zx.  Refused together with an LM, a dictionary, a phone FST,
 //   crf_align_mlffile, crf_output_mlffile or crf_lat_outdir.
-//   crf_output_conffile=PATH, on the best-paths-only branch (no crf_lat_outdir, no MLF, not align): beside the label
+//   crf_output_conffile=PATH, on the best-paths-only branch (no crf_lat_outdir, no MLF, not align unless crf_align_unit=phone): beside the label
 //   file, `sent seg first_frame last_frame label posterior` per segment of the best path (label = phone, posterior = the
 //   segment's posterior gamma).  The label file itself does not change.
 // A third one (beam-pruned lattices):
@@ -36,6 +36,14 @@
 //   with its LM / dictionary / phone FST / crf_align_mlffile chain) consumes the pruned machine unchanged; the label file
 //   holds the same best paths.  Ends with `Lattice beam B: kept K of N arcs`.  Refused with crf_decode_mode=align (a
 //   transcript's path may be pruned away), crf_decode_mode=posteriors, or when nothing would consume a lattice.
+// A fourth one (batched forced alignment on phones):
+//   crf_decode_mode=align crf_align_unit=phone: the transcript of an utterance is the phones of hardtarget_file's labels in
+//   their order (label % L), and the alignment runs on the device in batches of crf_bunch_size utterances.
+//   crf_align_repeat=1 (default): equal neighbours collapse and every phone takes one or more segments; crf_align_repeat=0:
+//   exactly one segment per listed phone.  Writes the label file in the usual formats; crf_output_conffile adds the posterior
+//   of every aligned segment.  A transcript that does not fit gets the align mode's warning and an empty entry.
+//   crf_align_unit=label (default) is the host path on phone-duration labels, unchanged.  Refused outside align mode and
+//   together with crf_lat_outdir / crf_output_mlffile (no lattice is built).
 #include "cli_common.h"
 
 #include <math.h>
@@ -88,8 +96,19 @@ int main(int argc, char** argv) {
   } else if (a.has("crf_output_posteriorfile")) { std::cerr << "crf_output_posteriorfile needs crf_decode_mode=posteriors" << std::endl; return 1; }
   const std::string pfmt = a.str("crf_output_posterior_format", "ascii");
   if (pfmt != "ascii" && pfmt != "pfile") { std::cerr << "crf_output_posterior_format=" << pfmt << " (ascii|pfile)" << std::endl; return 1; }
+  const std::string align_unit = a.str("crf_align_unit", "label");
+  if (align_unit != "label" && align_unit != "phone") { std::cerr << "crf_align_unit=" << align_unit << " (label|phone)" << std::endl; return 1; }
+  const bool align_phone = align_unit == "phone";
+  if (align_phone && !align_mode) { std::cerr << "crf_align_unit=phone needs crf_decode_mode=align (this is crf_decode_mode=" << mode << ")" << std::endl; return 1; }
+  if (align_phone && (a.has("crf_lat_outdir") || a.has("crf_output_mlffile"))) {
+    std::cerr << "crf_align_unit=phone aligns on the device and builds no lattice: not with crf_lat_outdir or crf_output_mlffile" << std::endl;
+    return 1;
+  }
+  if (a.has("crf_align_repeat") && !align_phone) { std::cerr << "crf_align_repeat needs crf_decode_mode=align crf_align_unit=phone" << std::endl; return 1; }
+  const long align_repeat = a.num("crf_align_repeat", 1);
+  if (align_repeat != 0 && align_repeat != 1) { std::cerr << "crf_align_repeat=" << align_repeat << " (1|0)" << std::endl; return 1; }
   const bool want_conf = a.has("crf_output_conffile");
-  if (want_conf && (post_mode || align_mode || a.has("crf_lat_outdir") || a.has("crf_output_mlffile"))) {
+  if (want_conf && (post_mode || (align_mode && !align_phone) || a.has("crf_lat_outdir") || a.has("crf_output_mlffile"))) {
     std::cerr << "crf_output_conffile goes with the best paths of the label file only: not with crf_decode_mode=" << mode
               << ", crf_lat_outdir or crf_output_mlffile" << std::endl;
     return 1;
@@ -326,7 +345,44 @@ int main(int argc, char** argv) {
     for (const scrf_arc& c : fst.arcs) lf << c.src << " " << c.dst << " " << c.ilabel << " " << c.olabel << " " << c.w << "\n";
     lf << fst.final_state << "\n";
   };
-  if (have_beam) {
+  // crf_output_conffile: `sent seg first_frame last_frame phone posterior` per segment of the paths about to be emitted
+  std::ofstream conf;
+  if (want_conf) {
+    conf.open(a.str("crf_output_conffile").c_str());
+    if (!conf.is_open()) { std::cerr << "ERROR: Failed opening file: " << a.str("crf_output_conffile") << std::endl; return -1; }
+    conf.precision(17);
+  }
+  auto write_conf = [&](const std::vector<std::vector<uint32_t> >& labs, const std::vector<std::vector<double> >& sp) {
+    for (size_t i = 0; i < labs.size(); i++) {
+      uint32_t frame = 0;
+      for (size_t k = 0; k < labs[i].size(); k++) {
+        const uint32_t dur = labs[i][k] / m.L + 1;
+        conf << u + i << " " << k << " " << frame << " " << frame + dur - 1 << " " << labs[i][k] % m.L << " " << sp[i][k] << "\n";
+        frame += dur;
+      }
+    }
+  };
+  if (align_phone) {
+    // forced alignment on phones, whole device batches of utterances (crf_bunch_size of them, default 256)
+    const size_t bunch = (size_t)std::max(1L, a.num("crf_bunch_size", 256));
+    bool at_end = strm.nextseg() == QN_SEGID_BAD;
+    while (!at_end) {
+      try {
+        std::vector<std::vector<uint32_t> > labs;
+        std::vector<float> costs;
+        std::vector<std::vector<double> > sp;
+        crf_amd_alignments(&strm, &crf, bunch, align_repeat ? SCRF_ALIGN_RUNS : SCRF_ALIGN_ONE, &labs, &costs, want_conf ? &sp : nullptr, &at_end);
+        if (want_conf) write_conf(labs, sp);
+        for (const auto& l : labs) {
+          if (l.empty()) std::cerr << "WARNING: the labels of sentence " << sents[u] << " do not fit its lattice" << std::endl;
+          emit(l);
+        }
+      } catch (std::exception& e) {
+        std::cerr << "Exception: " << e.what() << std::endl;
+        return -1;
+      }
+    }
+  } else if (have_beam) {
     // pruned lattices, whole device batches of utterances (crf_bunch_size of them, default 256)
     const size_t bunch = (size_t)std::max(1L, a.num("crf_bunch_size", 256));
     crf_amd::ArcListFst id;   // the label file's best path: ShortestPath over the pruned machine alone
@@ -365,12 +421,6 @@ int main(int argc, char** argv) {
   } else if (!a.has("crf_lat_outdir") && !want_mlf && !align_mode) {
     // best paths only: whole device batches of utterances (crf_bunch_size of them, default 256)
     const size_t bunch = (size_t)std::max(1L, a.num("crf_bunch_size", 256));
-    std::ofstream conf;
-    if (want_conf) {
-      conf.open(a.str("crf_output_conffile").c_str());
-      if (!conf.is_open()) { std::cerr << "ERROR: Failed opening file: " << a.str("crf_output_conffile") << std::endl; return -1; }
-      conf.precision(17);
-    }
     bool at_end = strm.nextseg() == QN_SEGID_BAD;
     while (!at_end) {
       try {
@@ -380,14 +430,7 @@ int main(int argc, char** argv) {
           // the same best paths (scrf_viterbi_batch on the same batch) with the posterior of each of their segments
           std::vector<std::vector<double> > sp;
           crf_amd_posteriors(&strm, &crf, bunch, nullptr, nullptr, nullptr, &labs, &costs, &sp, &at_end);
-          for (size_t i = 0; i < labs.size(); i++) {
-            uint32_t frame = 0;
-            for (size_t k = 0; k < labs[i].size(); k++) {
-              const uint32_t dur = labs[i][k] / m.L + 1;
-              conf << u + i << " " << k << " " << frame << " " << frame + dur - 1 << " " << labs[i][k] % m.L << " " << sp[i][k] << "\n";
-              frame += dur;
-            }
-          }
+          write_conf(labs, sp);
         } else
         crf_amd_best_paths(&strm, &crf, bunch, &labs, &costs, &at_end);
         for (const auto& l : labs) emit(l);

@@ -734,6 +734,7 @@ crf_amd::StreamBatch::StreamBatch(CRF_FeatureStream* ftr_strm, CRF_Model* crf, s
   g.b = nullptr;
 }
 crf_amd::StreamBatch::~StreamBatch() { if (b) scrf_batch_destroy(e->h, b); }
+const uint32_t* crf_amd::StreamBatch::labels(size_t u) const { return held->utts.at(u).u.labels; }
 
 // ------------------------------------------------------------------------------------------
 // CRF_GradBuilder

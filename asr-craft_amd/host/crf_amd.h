@@ -304,6 +304,8 @@ class StreamBatch {
   std::vector<uint32_t> T;   // frames per utterance
   size_t frames = 0;
   bool at_end = false;
+  // the node labels of utterance u as the batch holds them ([T[u]], CRF_LAB_BAD where a node has none), or nullptr
+  const uint32_t* labels(size_t u) const;
 
  private:
   struct Held;
@@ -641,6 +643,17 @@ size_t crf_amd_posteriors(CRF_FeatureStream* ftr_strm, CRF_Model* crf, size_t ma
 size_t crf_amd_pruned_lattices(CRF_FeatureStream* ftr_strm, CRF_Model* crf, size_t max_utts, double beam,
                                std::vector<crf_amd::ArcListFst>* lats, std::vector<double>* best, uint64_t* n_full_arcs,
                                bool* at_end);
+
+// Forced alignment on phones (scrf_align_batch) of the stream's CURRENT utterance and up to max_utts - 1
+// following ones in one device batch, in the style of crf_amd_best_paths (the stream is advanced with nextseg(); *at_end is
+// set when it ran out).  The transcript of an utterance is read from its node labels: label % nActualLabs of every labelled
+// node in order (CRF_LAB_BAD nodes skipped); with mode SCRF_ALIGN_RUNS consecutive equal phones are collapsed.  labels[u] =
+// the aligned segments as crf_amd_best_paths returns them (empty when the transcript does not fit, cost +inf); seg_post
+// (may be NULL) = the posterior of every aligned segment, from scrf_posteriors_batch on the same batch under the model's
+// training precision.  A model the engine refuses throws the engine's message.
+size_t crf_amd_alignments(CRF_FeatureStream* ftr_strm, CRF_Model* crf, size_t max_utts, int mode,
+                          std::vector<std::vector<uint32_t> >* labels, std::vector<float>* costs,
+                          std::vector<std::vector<double> >* seg_post, bool* at_end);
 
 // lattice builders: same call as the reference's templates; the arcs come from the engine in
 // AddArc order and are replayed into the caller's FST object

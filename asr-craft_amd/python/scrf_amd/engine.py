@@ -10,6 +10,7 @@ LAB_BAD = 0xFFFFFFFF
 STDFRAME, STDSEG, STDSEG_NO_DUR, STDSEG_NO_DUR_NO_TRANSFTR, STDSEG_NO_DUR_NO_SEGTRANSFTR = range(5)
 STDSTATE, STDTRANS, STDSPARSE, STDSPARSETRANS = 0, 1, 2, 3
 PREC_EXACT, PREC_FAST, PREC_FAST32, PREC_FASTLIN = 0, 1, 2, 3
+ALIGN_ONE, ALIGN_RUNS = 0, 1   # scrf_align_mode
 ABI_VERSION = 1
 MAX_STREAMS = 3
 N_PHASES = 10
@@ -424,6 +425,34 @@ class Engine:
         cost = np.empty(batch.n, dtype=np.float32)
         self._chk(self.lib.scrf_viterbi_batch(self.h, batch.handle, _p(labs), C.c_uint64(cap), _p(off), _p(cost)))
         return RaggedLabels(labs, off), cost
+
+    def align_batch(self, batch, transcripts, mode=ALIGN_RUNS):
+        """Forced alignment of every utterance against its phone transcript (scrf_align_batch).  transcripts: per utterance a
+        sequence of phones < L, or a RaggedLabels.  mode ALIGN_ONE: exactly one segment per phone; ALIGN_RUNS: one or more
+        consecutive segments per phone.  Returns (RaggedLabels, costs) in viterbi_batch's format; an utterance whose
+        transcript does not fit gets no labels and cost inf."""
+        U = batch.n
+        if len(transcripts) != U:
+            raise ValueError("align_batch: %d transcripts for a batch of %d utterances" % (len(transcripts), U))
+        if isinstance(transcripts, RaggedLabels):
+            ph = np.ascontiguousarray(transcripts.flat[:int(transcripts.off[U])], dtype=np.uint32)
+            poff = np.ascontiguousarray(transcripts.off, dtype=np.uint64)
+        else:
+            poff = np.zeros(U + 1, dtype=np.uint64)
+            poff[1:] = np.cumsum([len(t) for t in transcripts])
+            ph = np.ascontiguousarray(np.concatenate([np.asarray(t, dtype=np.uint32) for t in transcripts]) if U else [], dtype=np.uint32)
+        cap = batch.n_frames
+        labs = np.empty(cap, dtype=np.uint32); off = np.empty(U + 1, dtype=np.uint64)
+        cost = np.empty(U, dtype=np.float32)
+        self._chk(self.lib.scrf_align_batch(self.h, batch.handle, _p(ph), _p(poff), C.c_int(int(mode)), _p(labs), C.c_uint64(cap),
+                                            _p(off), _p(cost)))
+        return RaggedLabels(labs, off), cost
+
+    def align_stats(self):
+        """(scrf_align_batch calls, searches launched -- one per chunk --, those by the wavefront kernel, by the workgroup kernel) since create"""
+        v = [C.c_uint64() for _ in range(4)]
+        self._chk(self.lib.scrf_align_stats(self.h, *[C.byref(x) for x in v]))
+        return tuple(x.value for x in v)
 
     def batch_is_fused(self, batch):
         f = C.c_int()

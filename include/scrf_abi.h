@@ -337,6 +337,46 @@ int scrf_lattice_pruned_arcs(scrf_handle h, scrf_batch b, uint32_t u0, uint32_t 
 /* calls and chunks run since scrf_create (lets a test know that a batch really went through several chunks) */
 int scrf_lattice_prune_stats(scrf_handle h, uint64_t* n_calls, uint64_t* n_chunks);
 
+/* ---- forced alignment ----------------------------------------------------------------------------- */
+/* replaces: buildLattice + the label acceptor + composeShortestPath of CRFFstDecode crf_decode_mode=align
+ * (CRFFstDecode/src/Main.cpp, decoders/CRF_LatticeBuilder.h:172-184), for every utterance of the batch and on phones.
+ * The transcript of utterance u is the phone sequence q_0 .. q_{K-1} = phones[phone_off[u] .. phone_off[u+1]), every q_k < num_labs
+ * (phones only, no durations).  The hypotheses are the paths of the lattice exactly as scrf_lattice_arcs(..., norm = 0, ...)
+ * defines it, with its float weights, restricted by `mode`:
+ *   SCRF_ALIGN_ONE   exactly K segments, segment k carries phone q_k;
+ *   SCRF_ALIGN_RUNS  every q_k is realised by one or more consecutive segments that carry phone q_k (the reference's label
+ *                    acceptor: one state per run, entered by lab:lab, with a self loop).  For the frame model this is what
+ *                    crf_decode_mode=align computes.
+ * The cost of a path is the left-to-right float sum scrf_viterbi_batch forms.  Segmental model:
+ *   end(t,0)      <- 0.0f + w_seg(t, d = t+1, q_0)                       for t < lab_max_dur
+ *   boundary(t,k) <- end(t-1,k-1) + w_boundary(M_t, q_{k-1}, q_k)         "advance", k >= 1
+ *                 <- end(t-1,k)   + w_boundary(M_t, q_k, q_k)             "stay", SCRF_ALIGN_RUNS only
+ *   end(t,k)      <- boundary(t-d+1,k) + w_seg(t, d, q_k)
+ *   final         <- end(T-1,K-1) + (-0.0f), then + 0.0f
+ * frame model: state(0,0) = 0.0f + w_seg(0,1,q_0); state(t,k) <- state(t-1,k') + w_frame(M_t, S, t, q_k', q_k) with k' = k-1
+ * (advance) or, in SCRF_ALIGN_RUNS, k' = k (stay); final weight 0.0f.  Float addition is monotone, so the minimum over the
+ * paths is defined bit for bit whatever the evaluation order.  The path returned is fixed by strict improvement with the
+ * candidates in this order -- boundary: advance, then stay; end: the start arc, then t' ascending (d descending).
+ * seg_labels / lab_off / cost are in scrf_viterbi_batch's format (label l + num_labs * (d-1), one label per frame for the
+ * frame model), so they can go into scrf_posteriors_batch as segment queries.  The batch needs no labels.
+ * A transcript that does not fit (K = 0 with T > 0, K > T, SCRF_ALIGN_ONE with K * lab_max_dur < T) is not an error: that
+ * utterance gets 0 labels and cost +inf, as a T = 0 utterance does in scrf_viterbi_batch.  q_k >= num_labs or an unknown mode
+ * is SCRF_ERR_INVALID, checked before any launch.
+ * Arc weights as in scrf_viterbi_batch (the fast-decode path where that call takes it, bit-identical); chunks under
+ * scratch_bytes, which the back pointers (2 bytes per frame x transcript position) are part of.  Two kernels: one wavefront
+ * per utterance for chunks whose transcripts have at most 64 phones, one workgroup per utterance otherwise (any K <= T, as
+ * long as (lab_max_dur + 2) * K * 4 bytes fit a workgroup's LDS: SCRF_ERR_INVALID beyond); SCRF_ALIGN_WAVE=0 at scrf_create
+ * forces the second.  Same bytes either way.
+ * Models: SCRF_STDFRAME, SCRF_STDSEG_NO_DUR_NO_TRANSFTR, SCRF_STDSEG_NO_DUR_NO_SEGTRANSFTR with num_states == 1 (dense and
+ * sparse maps, batches of frames or of windows); SCRF_STDSEG, SCRF_STDSEG_NO_DUR and num_states > 1 are refused
+ * (SCRF_ERR_INVALID), and so is lab_max_dur > 32767 (a back pointer keeps the duration in 15 bits). */
+enum scrf_align_mode { SCRF_ALIGN_ONE = 0, SCRF_ALIGN_RUNS = 1 };
+int scrf_align_batch(scrf_handle h, scrf_batch b, const uint32_t* phones, const uint64_t* phone_off /* [n_utts+1] */,
+                     int mode, uint32_t* seg_labels, uint64_t max_labels, uint64_t* lab_off, float* cost /* or NULL */);
+/* since scrf_create: calls; searches launched (one per chunk; a fast-decode chunk whose fix-up list overflows is searched
+ * through the EXACT path instead, once per sub-chunk it is re-planned into); of these, by the wavefront / by the workgroup kernel */
+int scrf_align_stats(scrf_handle h, uint64_t* n_calls, uint64_t* n_chunks, uint64_t* n_wave, uint64_t* n_group);
+
 /* ---- minibatch reduce + optimizer ------------------------------------------------------------ */
 /* replaces the join/sum/average of CRF_Minibatch_GradAccumulator::accumulateGradient
  * (trainers/accumulators/CRF_Minibatch_GradAccumulator.cpp:277-312): all-reduce (sum) of the
@@ -394,7 +434,7 @@ int scrf_sgd_step(scrf_handle h, double lr_or_eta, int use_adagrad, double eps);
  * kernel (the three that dominate a step). */
 #define SCRF_N_PHASES 10
 int scrf_last_timing(scrf_handle h, float* ms, uint32_t* n_launch);
-/* HIP-event time of every kernel of the last timed scrf_fb_batch / scrf_posteriors_batch / scrf_viterbi_batch / scrf_lattice_prune_batch, one line per kernel
+/* HIP-event time of every kernel of the last timed scrf_fb_batch / scrf_posteriors_batch / scrf_viterbi_batch / scrf_lattice_prune_batch / scrf_align_batch, one line per kernel
  * name: "name\tmilliseconds\tlaunches\n" (events recorded on the stream the kernel is launched on) */
 int scrf_kernel_timing(scrf_handle h, char* buf, size_t cap);
 int scrf_enable_timing(scrf_handle h, int on);
