@@ -15,6 +15,8 @@
 //   computeAlpha :123-245, computeAlphaPlusTrans :1077-1108, computeBeta :395-466, computeExpF :616-949.
 #include "scrf_dp_common.h"
 
+#define DP_DBL_MIN 2.2250738585072014e-308   // the smallest normal double
+
 // E = exp(M - max(M)), its transpose, and the shift; one workgroup per L x L matrix
 __global__ void k_exp_m(const double* __restrict__ M, uint32_t L, double* __restrict__ E,
                         double* __restrict__ ET, double* __restrict__ mshift) {
@@ -159,7 +161,9 @@ __global__ __launch_bounds__(DP_WPB * 64, 3) void k_dp_wave(
       } else {
         usum = matvec_bcast(a, Es, L, lc);
       }
-      if (!(usum > 0.0 && usum < INFINITY)) err = 1;
+      // below DBL_MIN: flushed, or a sum of subnormal entries of E (more than 708 nats below the matrix maximum) that
+      // carry a few bits only -- the workgroup kernel redoes the batch
+      if (!(usum >= DP_DBL_MIN && usum < INFINITY)) err = 1;
       const double apt = amax + sh + log(usum);
       ring[rpos * L + lc] = apt;  // idle lanes rewrite lane L-1's value with the same number
       double v[DMAX];
@@ -259,7 +263,7 @@ __global__ __launch_bounds__(DP_WPB * 64, 3) void k_dp_wave(
       } else {
         w = matvec_bcast(b, Es, L, lc);
       }
-      if (!(w > 0.0 && w < INFINITY)) err = 1;
+      if (!(w >= DP_DBL_MIN && w < INFINITY)) err = 1;
       const double beta = smax + sh + log(w);
       ring[tpos * L + lc] = beta;
       if (act) { sdu[(size_t)t * L + lane] = sd; beu[(size_t)t * L + lane] = beta; }

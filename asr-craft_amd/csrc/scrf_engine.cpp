@@ -149,6 +149,7 @@ struct scrf_engine_s {
   double* d_sl_tab = nullptr;   // STDSEG, bias-only transitions: E, E^T (nLabs^2 each) and max M (scrf_stdseg_lin.hip)
   bool frame_mass = false;   // posterior-mass self-checks with the frame model's bounds (scrf_set_frame_mass_check)
   bool lin_dp = true;
+  bool stdseg_lin = true;    // SCRF_STDSEG_LIN=0: STDSEG trains on the reference-order kernels under every precision
   bool post_split = true;    // SCRF_POSTOCC_SPLIT=0: k_post_occ walks every utterance in one piece (same results)
   uint64_t n_post_split = 0, n_post_whole = 0;   // k_post_occ launches in frame segments / in one piece (scrf_posterior_stats)
   // the workgroup-per-utterance log-domain recursion (k_fb: column-wise max-shifted log-sum-exp, the
@@ -379,6 +380,7 @@ extern "C" int scrf_create(const scrf_config* cfg, scrf_handle* out) {
   if (const char* e = getenv("SCRF_FUSE_MIXED")) h->fuse_mixed = atoi(e) != 0;
   if (const char* e = getenv("SCRF_COMM_OVERLAP")) h->comm_overlap_on = atoi(e) != 0;
   if (const char* e = getenv("SCRF_LINDP")) h->lin_dp = atoi(e) != 0;
+  if (const char* e = getenv("SCRF_STDSEG_LIN")) h->stdseg_lin = atoi(e) != 0;
   if (const char* e = getenv("SCRF_POSTOCC_SPLIT")) h->post_split = atoi(e) != 0;
   if (const char* e = getenv("SCRF_FAST_DECODE")) h->fast_decode = atoi(e) != 0;
   if (const char* e = getenv("SCRF_ALIGN_WAVE")) h->align_wave = atoi(e) != 0;
@@ -1765,10 +1767,10 @@ static size_t stdseg_chunk_size(scrf_handle h, scrf_batch b, uint32_t u0, uint32
   stdseg_layout(h, b, u0, u1, post, m, &sb);
   return m.off;
 }
-// ---- STDSEG, bias-only transitions, FAST precisions, training path: scrf_stdseg_lin.hip
+// ---- STDSEG, bias-only transitions, FAST precisions, training path: scrf_stdseg_lin.hip (not during a log-domain redo,
+// force_fb: that one runs k_stdseg_fb, the reference's order)
 static bool stdseg_lin(scrf_handle h) {
-  static const bool on = !(getenv("SCRF_STDSEG_LIN") && atoi(getenv("SCRF_STDSEG_LIN")) == 0);
-  return on && h->cfg.train_precision != SCRF_PREC_EXACT && h->lay.use_sf && stdseg_lin_supported(h->lay, stdseg_La(h));
+  return h->stdseg_lin && !h->force_fb && h->cfg.train_precision != SCRF_PREC_EXACT && h->lay.use_sf && stdseg_lin_supported(h->lay, stdseg_La(h));
 }
 static uint64_t sl_rows_per_chunk(uint64_t nfr) {   // K-chunks of the count contractions: <= 256 of them, multiples of 32 frames
   uint64_t rpc = ((nfr + 255) / 256 + 31) & ~31ull;
@@ -2225,13 +2227,15 @@ static int fb_run(scrf_handle h, scrf_batch b, int latch[2], bool* used_lin) {
 
 // One pass over a batch and, where it raised NUMERIC on the wavefront kernels, a second one.  The wavefront recursions take
 // their transition step on exp(M - max M) (and the linear-domain one flushes what lies ~700 nats below a frame's maximum);
-// where that empties a whole vector or breaks a posterior-mass check, the batch is redone with the workgroup kernel, a
-// column-wise max-shifted log-sum-exp like the reference's LogMath.  Nothing of the first pass survives: its staged
-// gradient was dropped, its outputs are overwritten.
+// where that empties a vector, leaves a transition sum below DBL_MIN or breaks a posterior-mass check, the batch is redone
+// with the workgroup kernel, a column-wise max-shifted log-sum-exp like the reference's LogMath.  Nothing of the first pass
+// survives: its staged gradient was dropped, its outputs are overwritten.  STDSEG and the n-state frame model have pipelines
+// of their own: of those only STDSEG's linear-domain path (k_sl_fb, any number of full labels) has a log-domain second pass.
+static bool first_pass_was_linear(scrf_handle h) { return stdseg(h) || nstate(h) ? stdseg(h) && stdseg_lin(h) : wave_path(h, true); }
 template <class Pass>
 static int run_with_redo(scrf_handle h, const int latch[2], Pass pass) {
   int rc = pass();
-  if (rc != SCRF_OK || latch[0] != SCRF_ERR_NUMERIC || !wave_path(h, true)) return rc;
+  if (rc != SCRF_OK || latch[0] != SCRF_ERR_NUMERIC || !first_pass_was_linear(h)) return rc;
   h->n_lin_fallback++;
   h->force_fb = true;
   rc = pass();

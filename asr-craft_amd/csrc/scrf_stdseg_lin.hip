@@ -24,6 +24,7 @@ typedef double v4f64 __attribute__((ext_vector_type(4)));
 
 #define SL_NT 512          // threads of the recursion workgroup: one per full label (nLabs <= 512)
 #define SL_LOG0 (-1e300)
+#define SL_DBL_MIN 2.2250738585072014e-308   // the smallest normal double
 
 // ------------------------------------------------------------------------------------------
 // tables: M[p][c] = lambda[trans_idx(p, c)] * tbv (the bias is the only transition function), mmax = max M,
@@ -140,6 +141,9 @@ __global__ __launch_bounds__(SL_NT) void k_sl_fb(ScrfLayout lay, uint32_t La, Sc
           }
           for (; p < pavail; p++) acc0 = fma(rp[p], Ec[(size_t)p * NL], acc0);
           const double acc = acc0 + acc1;
+          // a sum below DBL_MIN is flushed, or built from subnormal entries of E that carry a few bits only (transition
+          // scores more than 708 nats below the table's maximum): the log-domain kernels decide
+          if (!(acc >= SL_DBL_MIN)) err = SCRF_ERR_NUMERIC;
           lg = acc > 0.0 ? (s + mmax) + (gring[slot] + log(acc)) : SL_LOG0;
         } else {
           lg = s;   // the utterance-initial segment (dur == t + 1): computeFirstAlpha :189-198
@@ -194,6 +198,7 @@ __global__ __launch_bounds__(SL_NT) void k_sl_fb(ScrfLayout lay, uint32_t La, Sc
           }
           for (; q < nv; q++) acc0 = fma(vec[q], Ep[(size_t)q * NL], acc0);
           const double acc = acc0 + acc1;
+          if (!(acc >= SL_DBL_MIN)) err = SCRF_ERR_NUMERIC;
           be = acc > 0.0 ? mmax + (red[SL_NT / 64] + log(acc)) : SL_LOG0;
         }
       }

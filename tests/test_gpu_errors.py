@@ -11,6 +11,7 @@ import pytest
 import orc
 import scrf_amd
 from cases import Case
+from spread_ladder import wide_spread_case      # heavy_out at 1500 nats on L = 4, D = 3
 
 pytestmark = pytest.mark.gpu
 
@@ -60,22 +61,6 @@ def test_the_lowest_failing_utterance_is_the_one_reported(prec):
             eng.fb_batch(bad, want_scalars=False)
         assert ei.value.code == 5 and "utterance 123" in str(ei.value)
     bad.close(); eng.close()
-
-
-def wide_spread_case(prec, fused=True):
-    """Weights under which the scaled linear-domain recursion must give up where the reference's log-domain
-    recursion succeeds: the state bias of label 0 is +1000 (every frame's posterior mass sits on label 0
-    to 1000 nats) and every transition OUT of label 0 costs 1500 nats, so the whole transition row of the
-    only label that carries mass lies more than 700 nats below the matrix maximum."""
-    c = Case(L=4, D=3, in_w=3, Ts=[6, 9, 5], seed=17, precision=prec, lam_scale=0.1)
-    lay = c.olay
-    nsf = lay.num_state_funcs
-    lam = c.lam.copy()
-    lam[lay.state_idx[0] + nsf - 1] = 1000.0           # state bias of label 0
-    for n in range(c.L):                               # transitions 0 -> n
-        lam[lay.trans_idx[0 * c.L + n]] = -1500.0
-    c.lam = lam
-    return c
 
 
 @pytest.mark.parametrize("prec", [0, 1])

@@ -13,6 +13,7 @@ import post_ref
 import scrf_amd
 from cases import Case
 from post_ref import CASES
+from spread_ladder import wide_spread_case      # heavy_out at 1500 nats on L = 4, D = 3
 
 pytestmark = pytest.mark.gpu
 
@@ -275,20 +276,6 @@ def test_chunking_is_invisible_and_the_log_domain_agrees(monkeypatch):
         print("log domain vs linear domain, %s: %.3e" % (k, d))
         assert d <= 1e-10
     b.close(); eng.close()
-
-
-def wide_spread_case(prec):
-    """tests/test_gpu_errors.py (copied): weights under which the wavefront recursions must give up where the reference's
-    log-domain recursion succeeds -- the state bias of label 0 is +1000 and every transition OUT of label 0 costs 1500 nats"""
-    c = Case(L=4, D=3, in_w=3, Ts=[6, 9, 5], seed=17, precision=prec, lam_scale=0.1)
-    lay = c.olay
-    nsf = lay.num_state_funcs
-    lam = c.lam.copy()
-    lam[lay.state_idx[0] + nsf - 1] = 1000.0
-    for n in range(c.L):
-        lam[lay.trans_idx[0 * c.L + n]] = -1500.0
-    c.lam = lam
-    return c
 
 
 @pytest.mark.parametrize("prec", [EXACT, FAST])

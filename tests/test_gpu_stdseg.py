@@ -108,6 +108,11 @@ def test_bias_only_transitions_linear_domain_path(ci, prec, tol, monkeypatch):
         np.testing.assert_allclose(numer, n0, rtol=1e-11, atol=1e-11)
         np.testing.assert_allclose(zx, z0, rtol=1e-11)
         assert np.abs(eng.get_grad() - g).max() <= 1e-9 * max(1.0, np.abs(g).max())
+        # the knob is read when the engine is created: this engine ran the reference-order kernels
+        eng.enable_timing(True); eng.zero_grad(); eng.fb_batch(b)
+        names = [k[0] for k in eng.kernel_timing()]
+        eng.enable_timing(False)
+        assert "k_stdseg_fb" in names and "k_sl_fb" not in names
         b.close(); eng.close()
 
 
