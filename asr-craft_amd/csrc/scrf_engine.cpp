@@ -1470,6 +1470,8 @@ static int run_scores(scrf_handle h, scrf_batch b, uint32_t u0, uint32_t u1, Chu
       launch_tile_tables(cb.st, l.D, fa.TB, (cb.la && !cb.Wn) ? 1 : 0, h->d_rtab);
       static const bool rtab_on = !(getenv("SCRF_RTAB") && atoi(getenv("SCRF_RTAB")) == 0);   // A/B knob
       if (rtab_on) fa.rtab = h->d_rtab;
+      static const bool dma_on = !(getenv("SCRF_SCORES_DMA") && atoi(getenv("SCRF_SCORES_DMA")) == 0);   // A/B knob
+      fa.dma = dma_on ? 1 : 0;
     }
     // per-frame projections of the five sampled blocks, then the dense part + gather
     if (pframe_supported(W0)) {

@@ -214,6 +214,39 @@ __device__ __forceinline__ void fu_scan_ext_full(const float (&v)[DMAX], float* 
   }
 }
 
+// One LDS-DMA load of BYTES (16 or 4) per lane: memory at sbase + voff -> LDS at lds + BYTES * lane (lds wave-uniform, in
+// m0; the source address is the lane's own, so a load is also a gather of rows).  NT: cache policy nt (data read once).
+// Written as an instruction rather than through __builtin_amdgcn_global_load_lds: with the builtin the compiler drains
+// vmcnt(0) at the next use of every ordinary load while a DMA is pending -- the window scans' 25 loads, which it
+// otherwise consumes one by one behind counted waits, then sit behind one full wait, and a second one precedes their
+// issue.  The caller owns the wait: s_waitcnt vmcnt(0) before the barrier that hands the image to its readers.
+#define FU_DMA_ASM(OP, POL)                                                                                       \
+  asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\t" OP " %1, %2" POL "\n\ts_mov_b32 m0, %0"      \
+               : "=&s"(keep) : "v"(voff), "s"(sbase), "s"(lds) : "memory")
+template <int BYTES, int NT>
+__device__ __forceinline__ void fu_dma(uint32_t voff, const void* sbase, uint32_t lds) {
+  static_assert(BYTES == 16 || BYTES == 4, "LDS-DMA widths in use");
+  uint32_t keep;
+  if constexpr (BYTES == 16 && NT) FU_DMA_ASM("global_load_lds_dwordx4", " nt");
+  else if constexpr (BYTES == 16) FU_DMA_ASM("global_load_lds_dwordx4", "");
+  else if constexpr (NT) FU_DMA_ASM("global_load_lds_dword", " nt");
+  else FU_DMA_ASM("global_load_lds_dword", "");
+}
+#undef FU_DMA_ASM
+// the issuing wavefront's wait for its DMAs (and every other load it has in flight)
+__device__ __forceinline__ void fu_dma_wait() { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); }
+// wave-uniform LDS byte address of a pointer into the workgroup's dynamic LDS
+__device__ __forceinline__ uint32_t fu_lds_addr(const void* p) {
+  return __builtin_amdgcn_readfirstlane((uint32_t)(uintptr_t)(__attribute__((address_space(3))) void*)p);
+}
+// Linear copy by 16-byte LDS-DMA loads: chunks [0, n16) of src -> dst, 1 KB pieces dealt to the NW wavefronts in turn.
+template <int NW>
+__device__ __forceinline__ void fu_dma_copy16(uint32_t wave, uint32_t lane, const void* src, void* dst, uint32_t n16) {
+  const uint32_t base = fu_lds_addr(dst);
+  for (uint32_t j = wave; j * 64u < n16; j += NW)
+    if (j * 64u + lane < n16) fu_dma<16, 0>((j * 64u + lane) * 16u, src, base + j * 1024u);
+}
+
 // ------------------------------------------------------------------------------------------
 // k_scores_fused: S[row][o] = dense(avg|max|min) + sum_k P[b+s_k(d)][k][o] + lambda_dur[d][o] + bias.
 // Workgroup (512 threads) = the windows of TB = 256/D whole frames (<= 256 rows); wave w owns rows
@@ -283,7 +316,7 @@ __host__ __device__ inline uint32_t fu_p_rows(uint32_t D, uint32_t TB) {
 __host__ __device__ inline uint32_t fu_p_rows_la(uint32_t D, uint32_t TB) { return fu_p_rows(D, TB) + TB + D; }
 #define FU_NPQ_LA 15
 
-template <int DMAX, int F32, int DEC, int LA>
+template <int DMAX, int F32, int DEC, int LA, int DMA>
 __global__ __launch_bounds__(FU_NT, 4) void k_scores_fused(ScrfFusedArgs fa, ScrfLayout lay,
                                                            const double* __restrict__ lambda,
                                                            const double* __restrict__ P, uint32_t n_out,
@@ -300,7 +333,10 @@ __global__ __launch_bounds__(FU_NT, 4) void k_scores_fused(ScrfFusedArgs fa, Scr
   float* fr = (float*)(Wg + FU_GC * FU_WS);                             // [nfmax][W]
   double* Pl = (double*)fsm;                                            // [fu_p_rows][FU_DS]: 48 used
   size_t opn = sizeof(float) * (FU_ROWS + 1) * FU_XS + sizeof(double) * FU_GC * FU_WS + sizeof(float) * nfmax * W;
-  const uint32_t nprmax = fu_p_rows_la(D, fa.TB);   // the tile size is planned for the larger (LA) image
+  // (fu_sample_step is float arithmetic: what comes out of it is wave-uniform but sits in vector registers unless told
+  // otherwise.  The DMA form tells: the LDS-DMA destinations are scalar operands, and the register budget is the tighter.)
+  auto uni = [](uint32_t x) { return DMA ? (uint32_t)__builtin_amdgcn_readfirstlane(x) : x; };
+  const uint32_t nprmax = uni(fu_p_rows_la(D, fa.TB));   // the tile size is planned for the larger (LA) image
   const size_t pb = sizeof(double) * nprmax * FU_DS;
   if (pb > opn) opn = pb;
   // outside the union (staged with the raw frames, read by the epilogue):
@@ -309,11 +345,15 @@ __global__ __launch_bounds__(FU_NT, 4) void k_scores_fused(ScrfFusedArgs fa, Scr
   // duration, the frame inside the tile, and the output whose score is the labelled window's (0xffff: none)
   uint4* recs = (uint4*)(Dt + D * FU_DS);                               // [FU_ROWS]
   uint16_t* rbase = (uint16_t*)(recs + FU_ROWS);                        // [TB] first row of each frame
-  uint16_t* rowmap = rbase + ((fa.TB + 3) & ~3u);                       // [fu_p_rows] P image row -> 5 * (frame - f0) + k
+  // (recs | rbase | rowmap are laid out as k_tile_tables lays them out in memory, in whole 16-byte chunks: a steady-state
+  // tile takes them by one linear LDS-DMA copy; fused_scores_smem_tb sizes them the same way.  The copy brings the
+  // table's padding and the records past TB * D along as they are in memory: nobody reads those.)
+  uint16_t* rowmap = rbase + ((fa.TB + 7) & ~7u);                       // [fu_p_rows] P image row -> 5 * (frame - f0) + k
 #if FU_EXPTAB
-  double* etab = (double*)(rowmap + ((nprmax + 3) & ~3u));              // [256] 2^(j/256) (exp epilogue only)
+  double* etab = (double*)(rowmap + ((nprmax + 7) & ~7u));              // [256] 2^(j/256) (exp epilogue only)
 #endif
-  const uint32_t tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+  const uint32_t tid = threadIdx.x, lane = tid & 63;
+  const uint32_t wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const uint32_t li = lane & 15, lk = lane >> 4;
   const uint32_t o0 = blockIdx.y * 48;
   // the tiles of an utterance are neighbours in the tile list and gather the same P rows and raw frames: with one
@@ -344,13 +384,25 @@ __global__ __launch_bounds__(FU_NT, 4) void k_scores_fused(ScrfFusedArgs fa, Scr
     const uint32_t ty = ci / cpg, c0 = (ci % cpg) * FU_GC;
     const uint32_t nc = min((uint32_t)FU_GC, W - c0);
     const uint32_t woff = (5 + ty) * W + c0;
+    // (DMA form: the four element offsets are worked out again at every call -- a dozen instructions -- instead of living
+    // in registers across the chunk loop, where they were the kernel's spills)
+    uint32_t wt = tid;
+    if (DMA) asm volatile("" : "+v"(wt));
 #pragma unroll
     for (int q = 0; q < 4; q++) {
-      const uint32_t e = tid + FU_NT * q, ol = e / FU_GC, c = e % FU_GC;
+      const uint32_t e = wt + FU_NT * q, ol = e / FU_GC, c = e % FU_GC;
       wp[q] = (e < 48 * FU_GC && o0 + ol < n_out && c < nc) ? lambda[lay.state_idx(o0 + ol) + woff + c] : 0.0;
     }
   };
   FU_SETPRIO(1);
+  // DMA (the launcher: fa.dma with both tables present): what does not depend on the tile -- the duration table of this output block and the steady-state tile's
+  // records, row bases and rowmap -- leaves for LDS by DMA now, in the round trip of the descriptor and the first lambda
+  // slice.  The regions lie outside the operand union; an edge tile overwrites the three tile tables after they landed.
+  constexpr bool dma = DMA != 0;
+  if (dma) {
+    fu_dma_copy16<FU_NT / 64>(wave, lane, fa.dtab + (size_t)blockIdx.y * D * FU_DS, Dt, D * (FU_DS / 2));
+    fu_dma_copy16<FU_NT / 64>(wave, lane, fa.rtab, recs, FU_ROWS + ((fa.TB + 7) >> 3) + ((nprmax + 7) >> 3));
+  }
   load_w(LA ? cpg : 0);   // LA: the dense groups are max and min only
 #if FU_PROF
   asm volatile("" :: "v"(ft.t0));   // the descriptor has arrived
@@ -362,7 +414,7 @@ __global__ __launch_bounds__(FU_NT, 4) void k_scores_fused(ScrfFusedArgs fa, Scr
   uint32_t prow0[5], pf0[5], nprows = 0;
 #pragma unroll
   for (int k = 0; k < 5; k++) {
-    const uint32_t reach = D - 1 - fu_sample_step(D, k);
+    const uint32_t reach = D - 1 - uni(fu_sample_step(D, k));
     pf0[k] = back > reach ? back - reach : 0;
     prow0[k] = nprows;
     nprows += nf - pf0[k];
@@ -370,6 +422,8 @@ __global__ __launch_bounds__(FU_NT, 4) void k_scores_fused(ScrfFusedArgs fa, Scr
   const uint32_t crow0 = nprows;          // LA: block 5 = the prefix sums C of frames t0 - D .. t0 + nfr - 1
   if (LA) nprows += ft.nfr + D;
   // stage raw frames f0 .. t0+nfr-1 and the duration weights (loads batched ahead of the LDS stores), decode rows
+  bool std_tile;
+  uint32_t lab_rel = 0xffffu;   // dma: the label slot of record tid
   {
     auto dur_w = [&](uint32_t i) {
       const uint32_t dd = i / 48, oo = i % 48;
@@ -384,14 +438,20 @@ __global__ __launch_bounds__(FU_NT, 4) void k_scores_fused(ScrfFusedArgs fa, Scr
     // fa.dtab (k_dur_table, once per launch): the [D][FU_DS] table of this output block, copied with coalesced loads --
     // built per tile it costs two loads per element from 48 different weight rows (lambda[state(o) + 8W + d] and the bias)
     const double* dtab = fa.dtab ? fa.dtab + (size_t)blockIdx.y * D * FU_DS : nullptr;
+    const float* src = fa.frames + (fa.frame_base + ft.fr0) * (uint64_t)W;
+    const uint32_t n = nf * W;
+    if (dma) {
+      // raw frames: rows of W floats, so the source is 4-byte aligned only -- 256-byte pieces, 4 bytes per lane
+      const uint32_t frb = fu_lds_addr(fr);
+      for (uint32_t j = wave; j * 64u < n; j += FU_NT / 64)
+        if (FU_ABL < 2 && j * 64u + lane < n) fu_dma<4, 0>((j * 64u + lane) * 4u, src, frb + j * 256u);
+    } else {
     double dtv[3];
 #pragma unroll
     for (int q = 0; q < 3; q++) {
       const uint32_t i = tid + FU_NT * q;
       dtv[q] = dtab ? (i < D * FU_DS ? dtab[i] : 0.0) : (i < D * 48 ? dur_w(i) : 0.0);
     }
-    const float* src = fa.frames + (fa.frame_base + ft.fr0) * (uint64_t)W;
-    const uint32_t n = nf * W;
     for (uint32_t i0 = 0; i0 < n; i0 += 4 * FU_NT) {
       float tmp[4];
 #pragma unroll
@@ -409,11 +469,21 @@ __global__ __launch_bounds__(FU_NT, 4) void k_scores_fused(ScrfFusedArgs fa, Scr
       for (uint32_t i = tid + 3 * FU_NT; i < D * 48; i += FU_NT) Dt[(i / 48) * FU_DS + i % 48] = dur_w(i);   // D > 32 only
       if (LA && tid < D) Dt[tid * FU_DS + 48] = 1.0 / (double)(tid + 1);
     }
-    FU_STAMP(6);   // frames and duration weights in LDS
+    }
+    FU_STAMP(6);   // frames and duration weights in LDS (dma: requested)
     // steady-state tiles (every frame has all D durations, TB frames) share their row records, row bases and rowmap:
     // copied from fa.rtab (k_tile_tables, once per launch), only the label slot is the tile's own
-    const bool std_tile = fa.rtab && ft.t0 >= D && ft.nfr == fa.TB;
-    if (std_tile) {
+    std_tile = (dma || fa.rtab) && ft.t0 >= D && ft.nfr == fa.TB;
+    if (dma && std_tile) {
+      // the tables are on their way; row tid of the tile is (frame tid / D, duration tid % D + 1), and its frame's label
+      // travels with the frames.  The record's label slot is patched once the records have landed (below).
+      if (labels && tid < ft.nfr * D) {
+        const uint32_t tl = fu_div(tid, fu_magic(D)), d = tid - tl * D + 1;
+        const uint32_t lab = labels[fa.frame_base + ft.fr0 + back + tl];
+        const uint32_t rel = lab - (d - 1) * n_out;
+        if (lab != SCRF_LAB_BAD && rel < n_out) lab_rel = rel;
+      }
+    } else if (std_tile) {
       const uint4* rg = (const uint4*)fa.rtab;
       const uint16_t* bg = (const uint16_t*)(rg + FU_ROWS);
       const uint16_t* mg = bg + ((fa.TB + 7) & ~7u);
@@ -430,6 +500,11 @@ __global__ __launch_bounds__(FU_NT, 4) void k_scores_fused(ScrfFusedArgs fa, Scr
       for (uint32_t tl = tid; tl < ft.nfr; tl += FU_NT) rbase[tl] = bg[tl];
       for (uint32_t r = tid; r < nprows; r += FU_NT) rowmap[r] = mg[r];
     } else {
+    // edge tile: its own tables replace the steady-state ones, once every wavefront's copies of those have landed
+    if (dma) {
+      fu_dma_wait();
+      __syncthreads();
+    }
     const uint32_t mD = fu_magic(D);
     for (uint32_t i = tid; i < ft.nfr * D; i += FU_NT) {
       const uint32_t tl = fu_div(i, mD), d = i - tl * D + 1;
@@ -484,7 +559,11 @@ __global__ __launch_bounds__(FU_NT, 4) void k_scores_fused(ScrfFusedArgs fa, Scr
       }
     }
   }
+  // DMA data is read after the issuing wavefronts' wait and a barrier the readers have passed
+  if (dma) fu_dma_wait();
   __syncthreads();
+  // (the records are next read in the epilogue, behind the barriers of the chunk loop)
+  if (lab_rel != 0xffffu) ((uint32_t*)recs)[4 * tid + 3] = lab_rel;
   FU_STAMP(0);   // stage
 
   v4f64 acc[F32 ? 1 : 2][F32 ? 1 : 3];
@@ -604,10 +683,25 @@ __global__ __launch_bounds__(FU_NT, 4) void k_scores_fused(ScrfFusedArgs fa, Scr
     __syncthreads();
     FU_STAMP(2);   // MFMA loops (+ barrier)
   }
-  // the P image over the dead operand images
+  // the P image over the dead operand images (the barrier that ended the last MFMA loop released them)
+  if (dma && std_tile && (n_out & 1) == 0 && o0 + 48 <= n_out) {
+    // by DMA: 16-byte chunk c of the image is (row c / 25, slot c % 25), the 64 chunks of a piece are 1 KB of the image in
+    // lane order, and each lane's source is its own row of P: rowmap[row] rows past frame fr0 - 1, 16 slot bytes into
+    // the output block (16-byte aligned: n_out is even).  Slot 24 is the row's padding, which nobody reads.  A full
+    // output block of a steady-state tile: every cell the epilogue gathers is one of these chunks, and no row is a zero
+    // row (t0 >= D).
+    const double* Pb = P + (ft.fr0 - 1) * NG * (uint64_t)n_out + o0;
+    const uint32_t plb = fu_lds_addr(Pl), nch = nprows * (FU_DS / 2), rowb = n_out * 8u;
+    for (uint32_t j = wave; j * 64u < nch; j += FU_NT / 64) {
+      const uint32_t c = j * 64u + lane, row = c / (FU_DS / 2), slot = c - row * (FU_DS / 2);
+      if (FU_ABL < 1 && c < nch && slot < 24) fu_dma<16, 0>(rowmap[row] * rowb + slot * 16u, Pb, plb + j * 1024u);
+    }
+    fu_dma_wait();
+  } else {
   for (uint32_t r0 = 0; r0 < nprows; r0 += 10 * NPQ) {   // one batch unless the tile is wider than the registers hold
     p_load(r0);
     p_store(r0);
+  }
   }
   __syncthreads();
   FU_STAMP(3);   // P staging
@@ -770,8 +864,13 @@ static size_t fused_scores_smem_tb(uint32_t W, uint32_t D, uint32_t TB) {
   const size_t pb = sizeof(double) * npr * FU_DS;
   if (pb > opn) opn = pb;
   opn = (opn + 15) & ~(size_t)15;
-  return opn + sizeof(double) * D * FU_DS + sizeof(uint4) * FU_ROWS + sizeof(uint16_t) * ((TB + 3) & ~3u) +
-         sizeof(uint16_t) * ((npr + 3) & ~3u) + (FU_EXPTAB ? sizeof(double) * FU_EXPT_N : 0) + 16;
+  // rbase and rowmap in whole 16-byte chunks (the kernel's layout = k_tile_tables' layout in memory).  The spare at the
+  // end shrinks by what that padding took over 4-entry padding (0, 8 or 16 of its 16 bytes), so the total -- and with it
+  // the tile plan -- is what it was before the tables were padded.
+  const size_t t4 = sizeof(uint16_t) * (((TB + 3) & ~3u) + ((npr + 3) & ~3u));
+  const size_t t8 = sizeof(uint16_t) * (((TB + 7) & ~7u) + ((npr + 7) & ~7u));
+  const size_t spare = 16 - (t8 - t4);
+  return opn + sizeof(double) * D * FU_DS + sizeof(uint4) * FU_ROWS + t8 + (FU_EXPTAB ? sizeof(double) * FU_EXPT_N : 0) + spare;
 }
 // frames per score tile: as many whole frames as give <= 256 rows and keep the workgroup's LDS
 // (the staged P rows grow with TB + D - 1) within 80 KB, i.e. two workgroups per CU; 0 = no fit
@@ -850,15 +949,23 @@ void launch_dur_table(hipStream_t st, const ScrfLayout& lay, uint32_t W, const d
   hipLaunchKernelGGL(k_dur_table, dim3((lay.L + 47) / 48), dim3(256), 0, st, lay, W, lambda, dtab);
 }
 
-template <int DMAX, int F32, int DEC, int LA>
-static void launch_scores_fused_t(hipStream_t st, const ScrfFusedArgs& fa, const ScrfLayout& lay, const double* lambda,
+template <int DMAX, int F32, int DEC, int LA, int DMA>
+static void launch_scores_fused_d(hipStream_t st, const ScrfFusedArgs& fa, const ScrfLayout& lay, const double* lambda,
                                   const double* P, uint64_t n_tiles, double* S, double* smax, double* s_true,
                                   const uint32_t* labels, const ScrfDecodeOut& dz) {
   const size_t sm = fused_scores_smem(fa.W, lay.D);
   dim3 grid((uint32_t)n_tiles, (lay.L + 47) / 48);
-  hipFuncSetAttribute((const void*)k_scores_fused<DMAX, F32, DEC, LA>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sm);
-  hipLaunchKernelGGL((k_scores_fused<DMAX, F32, DEC, LA>), grid, dim3(FU_NT), sm, st, fa, lay, lambda, P, lay.L, S, smax,
+  hipFuncSetAttribute((const void*)k_scores_fused<DMAX, F32, DEC, LA, DMA>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sm);
+  hipLaunchKernelGGL((k_scores_fused<DMAX, F32, DEC, LA, DMA>), grid, dim3(FU_NT), sm, st, fa, lay, lambda, P, lay.L, S, smax,
                      s_true, labels, dz);
+}
+// the LDS-DMA form copies both launch tables, so it needs both
+template <int DMAX, int F32, int DEC, int LA>
+static void launch_scores_fused_t(hipStream_t st, const ScrfFusedArgs& fa, const ScrfLayout& lay, const double* lambda,
+                                  const double* P, uint64_t n_tiles, double* S, double* smax, double* s_true,
+                                  const uint32_t* labels, const ScrfDecodeOut& dz) {
+  if (fa.dma && fa.dtab && fa.rtab) launch_scores_fused_d<DMAX, F32, DEC, LA, 1>(st, fa, lay, lambda, P, n_tiles, S, smax, s_true, labels, dz);
+  else launch_scores_fused_d<DMAX, F32, DEC, LA, 0>(st, fa, lay, lambda, P, n_tiles, S, smax, s_true, labels, dz);
 }
 
 // la (SCRF_PREC_FASTLIN, fp64 only): P carries 6 groups per frame, the sixth summed along the utterance (k_avg_prefix)
@@ -1936,21 +2043,8 @@ __global__ __launch_bounds__(FE_NT, 2) void k_expf_fused(ScrfFusedArgs fa, ScrfL
 #ifndef FW_DMA_NT
 #define FW_DMA_NT 1     // cache policy of the R tile's LDS-DMA loads: 1 = nt (R is read once, as on the register path)
 #endif
-#if FW_DMA_NT
-#define FW_DMA_POL " nt"
-#else
-#define FW_DMA_POL ""
-#endif
-// One 16-byte LDS-DMA load per lane: memory at sbase + voff -> LDS at lds + 16 lane (lds wave-uniform, in m0).  Written
-// as an instruction rather than through __builtin_amdgcn_global_load_lds: with the builtin the compiler drains
-// vmcnt(0) at the next use of every ordinary load while a DMA is pending -- the window scans' 25 loads, which it
-// otherwise consumes one by one behind counted waits, then sit behind one full wait, and a second one precedes their
-// issue.  The caller owns the wait: s_waitcnt vmcnt(0) before the barrier that hands the image to its readers.
-__device__ __forceinline__ void fw_dma16(uint32_t voff, const void* sbase, uint32_t lds) {
-  uint32_t keep;
-  asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2" FW_DMA_POL "\n\ts_mov_b32 m0, %0"
-               : "=&s"(keep) : "v"(voff), "s"(sbase), "s"(lds) : "memory");
-}
+// The R tile's loads: fu_dma above, 16 bytes per lane, cache policy FW_DMA_NT
+__device__ __forceinline__ void fw_dma16(uint32_t voff, const void* sbase, uint32_t lds) { fu_dma<16, FW_DMA_NT>(voff, sbase, lds); }
 // ROWS = window rows per tile (76, or 100 where the two image pairs still fit 160 KB: fewer tiles, fewer barriers and
 // producer round trips per row); NKS = ceil(rows used / 4).
 // (register cap 208 for the narrow forms: two such wavefronts per SIMD leave 96 registers per lane, which is what lets
