@@ -85,12 +85,11 @@ __global__ __launch_bounds__(256) void k_exp_m_tile(const double* __restrict__ M
   if (tid == 0) mshift[blockIdx.x] = mx;
 }
 
-void launch_exp_m(hipStream_t st, const double* M, uint32_t L, uint64_t n_mat, double* E, double* ET,
+void launch_exp_m(hipStream_t st, const ScrfKnobs& kn, const double* M, uint32_t L, uint64_t n_mat, double* E, double* ET,
                   double* mshift) {
   if (n_mat == 0) return;
-  static const bool tile_off = getenv("SCRF_EXPM_TILE") && atoi(getenv("SCRF_EXPM_TILE")) == 0;   // A/B knob
   const uint32_t ne = (L * L + 255) / 256;
-  if (L <= 64 && !tile_off) {
+  if (L <= 64 && kn.expm_tile) {
     if (ne <= 4) hipLaunchKernelGGL(k_exp_m_tile<4>, dim3((uint32_t)n_mat), dim3(256), 0, st, M, L, E, ET, mshift);
     else if (ne <= 9) hipLaunchKernelGGL(k_exp_m_tile<9>, dim3((uint32_t)n_mat), dim3(256), 0, st, M, L, E, ET, mshift);
     else hipLaunchKernelGGL(k_exp_m_tile<16>, dim3((uint32_t)n_mat), dim3(256), 0, st, M, L, E, ET, mshift);

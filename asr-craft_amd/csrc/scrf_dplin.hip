@@ -858,7 +858,7 @@ int dplin_mw_supported(const ScrfLayout& lay) { return lay.L > 64 && lay.L <= 25
 int dplin_supported(const ScrfLayout& lay) { return lay.L <= 64 && lay.D <= 40; }
 
 template <int DMAX>
-static void launch_dp_lin_mw_t(hipStream_t st, const ScrfLayout& lay, ScrfBatchView bv, uint32_t u0, uint32_t n_utts,
+static void launch_dp_lin_mw_t(hipStream_t st, const ScrfKnobs& kn, const ScrfLayout& lay, ScrfBatchView bv, uint32_t u0, uint32_t n_utts,
                                const double* ES, const double* smax, const double* E, const double* ET,
                                const double* mshift, int m_per_frame, const ScrfDpLin& o, double* zx, int* status) {
   const uint32_t nw = (lay.L + 63) / 64;
@@ -870,17 +870,15 @@ static void launch_dp_lin_mw_t(hipStream_t st, const ScrfLayout& lay, ScrfBatchV
                        ET, mshift, o.a, o.ga, o.p, o.gp, o.b, o.gb, o.sd, o.gsd, zx, status);                                         \
   } while (0)
   // the matrix column in registers (SCRF_DPLIN_EREG=0: from L2 every frame, as before round 4)
-  static const bool ereg = !(getenv("SCRF_DPLIN_EREG") && atoi(getenv("SCRF_DPLIN_EREG")) == 0);
   // Measured (ms per launch, from L2 -> in registers): L = 200, D = 25, 512 x 300 frames 17.6 -> 9.4 (LR = 208: 49 spilled
   // registers, still a gain); L = 96, D = 25, 1024 utterances 10.2 -> 6.5; L = 128, D = 10: 5.4 -> 4.3.  At DMAX = 40 the
   // duration step's 80 registers leave room for 128 rows only (L = 200 in full spills 141 registers and LOSES: 13.7 ->
   // 17.8): there 128 rows live in registers and the rest comes from L2 (TAIL).
-  static const bool tail_on = !(getenv("SCRF_DPLIN_TAIL") && atoi(getenv("SCRF_DPLIN_TAIL")) == 0);
-  if (m_per_frame || !ereg) { if (m_per_frame) MW_GO(1, 0, 0); else MW_GO(0, 0, 0); }
+  if (m_per_frame || !kn.dplin_ereg) { if (m_per_frame) MW_GO(1, 0, 0); else MW_GO(0, 0, 0); }
   else if (lay.L <= 128) MW_GO(0, 128, 0);
   else if (DMAX <= 25 && lay.L <= 192) MW_GO(0, 192, 0);
   else if (DMAX <= 25 && lay.L <= 208) MW_GO(0, 208, 0);
-  else if (DMAX > 25 && tail_on) MW_GO(0, 128, 1);
+  else if (DMAX > 25 && kn.dplin_tail) MW_GO(0, 128, 1);
   else MW_GO(0, 0, 0);
 #undef MW_GO
 }
@@ -906,14 +904,14 @@ static int dp_cu_count() {
   return n_cu;
 }
 
-void launch_dp_lin(hipStream_t st, const ScrfLayout& lay, ScrfBatchView bv, uint32_t u0, uint32_t n_utts,
+void launch_dp_lin(hipStream_t st, const ScrfKnobs& kn, const ScrfLayout& lay, ScrfBatchView bv, uint32_t u0, uint32_t n_utts,
                    const double* ES, const double* smax, const double* E, const double* ET, const double* mshift,
                    int m_per_frame, const ScrfDpLin& o, double* zx, int* status) {
   if (n_utts == 0) return;
   if (lay.L > 64) {
-    if (lay.D <= 10) launch_dp_lin_mw_t<10>(st, lay, bv, u0, n_utts, ES, smax, E, ET, mshift, m_per_frame, o, zx, status);
-    else if (lay.D <= 25) launch_dp_lin_mw_t<25>(st, lay, bv, u0, n_utts, ES, smax, E, ET, mshift, m_per_frame, o, zx, status);
-    else launch_dp_lin_mw_t<40>(st, lay, bv, u0, n_utts, ES, smax, E, ET, mshift, m_per_frame, o, zx, status);
+    if (lay.D <= 10) launch_dp_lin_mw_t<10>(st, kn, lay, bv, u0, n_utts, ES, smax, E, ET, mshift, m_per_frame, o, zx, status);
+    else if (lay.D <= 25) launch_dp_lin_mw_t<25>(st, kn, lay, bv, u0, n_utts, ES, smax, E, ET, mshift, m_per_frame, o, zx, status);
+    else launch_dp_lin_mw_t<40>(st, kn, lay, bv, u0, n_utts, ES, smax, E, ET, mshift, m_per_frame, o, zx, status);
     return;
   }
   // opt-in (SCRF_DPLIN_MV=1): parity-green, but measured no faster than one wavefront per sweep -- see the kernel's header
@@ -922,9 +920,7 @@ void launch_dp_lin(hipStream_t st, const ScrfLayout& lay, ScrfBatchView bv, uint
   // single-wavefront kernel's step is the latency of one wavefront fetching an L x L matrix, and four fetch it in
   // parallel (config 3, 256 utterances: 1.86 -> 1.03 ms).  With time-invariant transitions it measured no faster at any
   // batch size (64 .. 4096 utterances), so it stays opt-in there.
-  static const int mv_mode = getenv("SCRF_DPLIN_MV") ? (atoi(getenv("SCRF_DPLIN_MV")) != 0 ? 1 : 0) : -1;
-  static const int mv_sweeps = getenv("SCRF_DPLIN_MV_SWEEPS") ? atoi(getenv("SCRF_DPLIN_MV_SWEEPS")) : 3;
-  const bool use_mv = mv_mode == 1 || (mv_mode < 0 && m_per_frame && 2 * (uint64_t)n_utts <= (uint64_t)mv_sweeps * dp_cu_count());
+  const bool use_mv = kn.dplin_mv == 1 || (kn.dplin_mv < 0 && m_per_frame && 2 * (uint64_t)n_utts <= (uint64_t)kn.dplin_mv_sweeps * dp_cu_count());
   if (use_mv && lay.D >= 2) {
     // several wavefronts per sweep (k_dp_lin_mv): one workgroup of 4 per (utterance, direction)
     const size_t smv = sizeof(double) * ((((size_t)lay.D * lay.L + 1) & ~(size_t)1) + 4 * DPV_NW * 64);

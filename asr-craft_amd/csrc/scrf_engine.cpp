@@ -68,6 +68,7 @@ enum { SCRF_NCCL_DOUBLE = 8, SCRF_NCCL_SUM = 0 };  // ncclFloat64, ncclSum (rccl
 // ---------------------------------------------------------------------------------------------
 struct scrf_engine_s {
   scrf_config cfg;
+  ScrfKnobs kn;   // the SCRF_* environment switches as scrf_create found them (scrf_knobs.h, DESIGN.md "Knobs")
   ScrfLayout lay;
   // K states per label on a segmental model (nodes/CRF_StdSegNStateNode_WithoutDurLab_WithoutSegTransFtr.cpp): the
   // kernels run the dense one-state layout `lay` with the bias of every transition the topology lacks pinned at
@@ -123,45 +124,30 @@ struct scrf_engine_s {
   hipEvent_t pool_ev[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
   uint64_t pool_epoch = 0, pool_done = 0;         // destroy calls so far / epochs known to be finished
   size_t pool_bytes = 0;                          // bytes sitting in pool_free
-  bool pool_on = true;
-  bool pool_up = true;     // uploads on their own stream (SCRF_BATCH_POOL=2: on the engine stream)
   char* scratch2 = nullptr;
   size_t scratch2_cap = 0;
   double* d_grad2 = nullptr;
   double* d_sums2 = nullptr;
   hipEvent_t ev_fork = nullptr, ev_join = nullptr;
-  int n_lanes = 1;  // SCRF_LANES=2: alternate chunks on two streams (worth ~3 % at config 2; off by default)
-  bool fuse_windows = true;
   // all-reduce / compute overlap (scrf_fb_batch_allreduce): inside the fused call the transition
   // contraction runs first and the all-reduce of the transition weights (98.7 % of the TIMIT-demo gradient) is issued on
   // the second stream as soon as they are committed, under the state contraction
   bool overlap_comm = false;  // set for the duration of a scrf_fb_batch_allreduce call
   bool early_done = false;    // the transition block of this step has been all-reduced already
   uint64_t n_collectives = 0, n_overlapped = 0;   // scrf_comm_stats
-  bool comm_overlap_on = true;   // SCRF_COMM_OVERLAP=0: the fused call issues both blocks after the batch (same results)
   double* d_pack = nullptr;   // [L * nsf + 8]: the state weights of every label + the 8 scalars, one small message
-  bool fuse_mixed = true;     // SCRF_FUSE_MIXED=0: two-stream batches keep the general path for the state part too
-  bool dur_table = true;      // the score kernel copies its duration-weight table instead of building it per tile (SCRF_DTAB=0: off)
-  bool side_stream = true;    // k_ztf + transition counts on the second stream under k_expf_fused_ws (SCRF_SIDE=0: off)
   void* d_rtab = nullptr;       // k_tile_tables: row records / row bases / rowmap of a steady-state score tile
   size_t rtab_bytes = 0;
   double* d_dtab = nullptr;     // k_dur_table: duration weight + bias per output block, for the fused score kernel
   double* d_sl_tab = nullptr;   // STDSEG, bias-only transitions: E, E^T (nLabs^2 each) and max M (scrf_stdseg_lin.hip)
   bool frame_mass = false;   // posterior-mass self-checks with the frame model's bounds (scrf_set_frame_mass_check)
-  bool lin_dp = true;
-  bool stdseg_lin = true;    // SCRF_STDSEG_LIN=0: STDSEG trains on the reference-order kernels under every precision
-  bool post_split = true;    // SCRF_POSTOCC_SPLIT=0: k_post_occ walks every utterance in one piece (same results)
   uint64_t n_post_split = 0, n_post_whole = 0;   // k_post_occ launches in frame segments / in one piece (scrf_posterior_stats)
   // the workgroup-per-utterance log-domain recursion (k_fb: column-wise max-shifted log-sum-exp, the
   // reference's LogMath) instead of the wavefront kernels, whose transition step works on exp(M - max M):
   // set for the automatic redo of a batch / hook call that raised SCRF_ERR_NUMERIC there
   bool force_fb = false;
   // decode from the fused score kernel's float arc weights + reference-order fix-ups (bit-identical
-  // to the EXACT path by a rounding-error bound, ScrfDecodeOut); SCRF_FAST_DECODE=0 turns it off
-  bool hybrid = true;   // SCRF_HYBRID=0: the general path contracts all 8 W + D columns of X
-  bool hybrid_first = false;   // SCRF_HYBRID=2 (A/B runs): L > 64 takes the hybrid path even where the fused kernels fit
-  bool fast_decode = true;
-  double decode_bound_factor = 1.0;   // SCRF_DECODE_BOUND_SCALE (tests widen the screen with it)
+  // to the EXACT path by a rounding-error bound, ScrfDecodeOut; kn.fast_decode)
   double* d_w1 = nullptr;
   uint64_t n_decode_fix = 0, n_decode_fallback = 0;   // entries recomputed / chunks sent back to the EXACT path
   // result buffers of scrf_viterbi_batch, kept across calls (a hipMalloc / hipFree pair per call is a device-wide
@@ -183,7 +169,6 @@ struct scrf_engine_s {
   uint64_t n_lp_calls = 0, n_lp_chunks = 0;
   // scrf_align_batch: the transcripts of the call on the device (phones | phone_off, back-pointer offsets),
   // kept across calls; al_bp_off is the host image chunk_layout sizes a chunk's back pointers with
-  bool align_wave = true;   // SCRF_ALIGN_WAVE=0: every chunk through the workgroup kernel (same results)
   uint32_t* al_ph = nullptr;
   uint64_t* al_off = nullptr;
   uint64_t al_cap_ph = 0, al_cap_u = 0;
@@ -373,20 +358,7 @@ extern "C" int scrf_create(const scrf_config* cfg, scrf_handle* out) {
   }
   h->device = cfg->device_id;
   if (h->cfg.scratch_bytes == 0) h->cfg.scratch_bytes = 8ull << 30;
-  if (const char* e = getenv("SCRF_LANES")) h->n_lanes = atoi(e) > 1 ? 2 : 1;  // experiment knobs
-  if (const char* e = getenv("SCRF_FUSE")) h->fuse_windows = atoi(e) != 0;
-  if (const char* e = getenv("SCRF_SIDE")) h->side_stream = atoi(e) != 0;
-  if (const char* e = getenv("SCRF_DTAB")) h->dur_table = atoi(e) != 0;
-  if (const char* e = getenv("SCRF_FUSE_MIXED")) h->fuse_mixed = atoi(e) != 0;
-  if (const char* e = getenv("SCRF_COMM_OVERLAP")) h->comm_overlap_on = atoi(e) != 0;
-  if (const char* e = getenv("SCRF_LINDP")) h->lin_dp = atoi(e) != 0;
-  if (const char* e = getenv("SCRF_STDSEG_LIN")) h->stdseg_lin = atoi(e) != 0;
-  if (const char* e = getenv("SCRF_POSTOCC_SPLIT")) h->post_split = atoi(e) != 0;
-  if (const char* e = getenv("SCRF_FAST_DECODE")) h->fast_decode = atoi(e) != 0;
-  if (const char* e = getenv("SCRF_ALIGN_WAVE")) h->align_wave = atoi(e) != 0;
-  if (const char* e = getenv("SCRF_BATCH_POOL")) { h->pool_on = atoi(e) != 0; h->pool_up = atoi(e) != 2; }
-  if (const char* e = getenv("SCRF_HYBRID")) { h->hybrid = atoi(e) != 0; h->hybrid_first = atoi(e) == 2; }
-  if (const char* e = getenv("SCRF_DECODE_BOUND_SCALE")) h->decode_bound_factor = std::max(1.0, atof(e));   // widening only: < 1 would void the bound
+  h->kn = scrf_knobs_read(scrf_env);
   memset(h->ms, 0, sizeof(h->ms));
   memset(h->nlaunch, 0, sizeof(h->nlaunch));
 #define CRCHK(call)                                                                          \
@@ -688,7 +660,7 @@ static void pool_poll(scrf_handle h) {   // which destroy epochs have finished o
 }
 static int pool_alloc(scrf_handle h, size_t bytes, void** out) {
   *out = nullptr;
-  if (!h->pool_on) { HIPCHK(h, hipMalloc(out, bytes)); return SCRF_OK; }
+  if (!h->kn.pool_on()) { HIPCHK(h, hipMalloc(out, bytes)); return SCRF_OK; }
   const size_t cap = pool_class(bytes);
   pool_poll(h);
   for (size_t i = 0; i < h->pool_free.size(); i++) {
@@ -709,7 +681,7 @@ static int pool_alloc(scrf_handle h, size_t bytes, void** out) {
 static void pool_release(scrf_handle h, void* p) {   // inside a destroy call: the block carries the epoch being closed
   if (!p) return;
   auto it = h ? h->pool_cap.find(p) : decltype(h->pool_cap.find(p))();
-  if (!h || !h->pool_on || it == h->pool_cap.end()) { hipFree(p); return; }
+  if (!h || !h->kn.pool_on() || it == h->pool_cap.end()) { hipFree(p); return; }
   h->pool_free.push_back({p, it->second, h->pool_epoch + 1});
   h->pool_bytes += it->second;
   h->pool_cap.erase(it);
@@ -735,6 +707,7 @@ static void pool_close_epoch(scrf_handle h) {   // after the releases of one des
   }
 }
 
+static hipStream_t upload_stream(scrf_handle h) { return (h->kn.pool_on() && h->kn.pool_up()) ? h->up_stream : h->stream; }
 template <class Tp>
 static int upload(scrf_handle h, Tp** d, const Tp* src, size_t n) {
   *d = nullptr;
@@ -743,7 +716,7 @@ static int upload(scrf_handle h, Tp** d, const Tp* src, size_t n) {
   int rc = pool_alloc(h, sizeof(Tp) * n, &p);
   if (rc != SCRF_OK) return rc;
   *d = (Tp*)p;
-  if (src) HIPCHK(h, hipMemcpyAsync(*d, src, sizeof(Tp) * n, hipMemcpyHostToDevice, (h->pool_on && h->pool_up) ? h->up_stream : h->stream));
+  if (src) HIPCHK(h, hipMemcpyAsync(*d, src, sizeof(Tp) * n, hipMemcpyHostToDevice, upload_stream(h)));
   return SCRF_OK;
 }
 
@@ -758,7 +731,7 @@ extern "C" int scrf_batch_destroy(scrf_handle h, scrf_batch b) {
   if (!b) return SCRF_OK;
   if (h) hipSetDevice(h->device);
   if (h && h->lp_batch == b) h->lp_batch = nullptr;
-  if (h && !h->pool_on) hipStreamSynchronize(h->stream);
+  if (h && !h->kn.pool_on()) hipStreamSynchronize(h->stream);
   // (pool: no synchronisation here -- the blocks wait in the pool until the engine stream has passed this point)
 #define BFREE(p) pool_release(h, (void*)(p))
   BFREE(b->d_T); BFREE(b->d_frame_off); BFREE(b->d_seg_off); BFREE(b->d_arc_off);
@@ -767,7 +740,7 @@ extern "C" int scrf_batch_destroy(scrf_handle h, scrf_batch b) {
   BFREE(b->d_numer); BFREE(b->d_zx); BFREE(b->d_status);
   BFREE(b->d_tiles[0]); BFREE(b->d_tiles[1]); BFREE(b->d_tiles[2]);
 #undef BFREE
-  if (h && h->pool_on) pool_close_epoch(h);
+  if (h && h->kn.pool_on()) pool_close_epoch(h);
   delete b;
   return SCRF_OK;
 }
@@ -818,7 +791,7 @@ extern "C" int scrf_batch_create(scrf_handle h, const scrf_utt* utts, uint32_t n
   const uint64_t NF = b->frame_off[n], NS = b->seg_off[n];
   int rc;
 #define BCHK(x) do { rc = (x); if (rc != SCRF_OK) { scrf_batch_destroy(h, b); return rc; } } while (0)
-#define BSYNC() do { hipError_t e_ = hipStreamSynchronize((h->pool_on && h->pool_up) ? h->up_stream : h->stream); if (e_ != hipSuccess) { scrf_batch_destroy(h, b); return fail(h, SCRF_ERR_HIP, "scrf_batch_create: %s", hipGetErrorString(e_)); } } while (0)
+#define BSYNC() do { hipError_t e_ = hipStreamSynchronize(upload_stream(h)); if (e_ != hipSuccess) { scrf_batch_destroy(h, b); return fail(h, SCRF_ERR_HIP, "scrf_batch_create: %s", hipGetErrorString(e_)); } } while (0)
   BCHK(upload(h, &b->d_T, b->T.data(), n));
   BCHK(upload(h, &b->d_frame_off, b->frame_off.data(), n + 1));
   BCHK(upload(h, &b->d_seg_off, b->seg_off.data(), n + 1));
@@ -872,7 +845,7 @@ extern "C" int scrf_batch_create(scrf_handle h, const scrf_utt* utts, uint32_t n
     BCHK(upload<float>(h, &b->d_windows, nullptr, NS * lay.F + 64));  // tail pad: wide loads may over-read 12 B
     for (uint32_t u = 0; u < n; u++) {
       hipError_t e = hipMemcpyAsync(b->d_windows + b->seg_off[u] * lay.F, utts[u].windows,
-                                    sizeof(float) * (b->seg_off[u + 1] - b->seg_off[u]) * lay.F, hipMemcpyHostToDevice, (h->pool_on && h->pool_up) ? h->up_stream : h->stream);
+                                    sizeof(float) * (b->seg_off[u + 1] - b->seg_off[u]) * lay.F, hipMemcpyHostToDevice, upload_stream(h));
       if (e != hipSuccess) { scrf_batch_destroy(h, b); return fail(h, SCRF_ERR_HIP, "window upload failed: %s", hipGetErrorString(e)); }
     }
   } else {
@@ -890,7 +863,7 @@ extern "C" int scrf_batch_create(scrf_handle h, const scrf_utt* utts, uint32_t n
       BSYNC();
       for (uint32_t u = 0; u < n; u++) {
         hipError_t e = hipMemcpyAsync(b->d_frames[s] + so[u] * recipes[s].in_width, utts[u].frames[s],
-                                      sizeof(float) * (so[u + 1] - so[u]) * recipes[s].in_width, hipMemcpyHostToDevice, (h->pool_on && h->pool_up) ? h->up_stream : h->stream);
+                                      sizeof(float) * (so[u + 1] - so[u]) * recipes[s].in_width, hipMemcpyHostToDevice, upload_stream(h));
         if (e != hipSuccess) { scrf_batch_destroy(h, b); return fail(h, SCRF_ERR_HIP, "frame upload failed: %s", hipGetErrorString(e)); }
       }
     }
@@ -899,10 +872,10 @@ extern "C" int scrf_batch_create(scrf_handle h, const scrf_utt* utts, uint32_t n
   // the state feature range, no transition features
   const int f32_cfg = h->cfg.train_precision == SCRF_PREC_FAST32;
   const bool sparse_map = h->cfg.map_type >= SCRF_STDSPARSE;   // the general path only
-  const bool hybrid_first = !sparse_map && h->hybrid_first && lay.L > 64 && n_streams == 1 && !lay.use_tf;
+  const bool hybrid_first = !sparse_map && h->kn.hybrid_first() && lay.L > 64 && n_streams == 1 && !lay.use_tf;
   const bool seg_stream0 = !sparse_map && !hybrid_first && !by_windows && n_streams >= 1 && h->cfg.model_type != SCRF_STDSEG_NO_DUR && h->cfg.model_type != SCRF_STDSEG && lay.use_sf &&
                            recipes[0].extract_seg_ftr && !recipes[0].left_ctx && !recipes[0].right_ctx && lay.sfs == 0 &&
-                           lay.nsfe == 8 * recipes[0].in_width + lay.D && fused_supported(lay, recipes[0].in_width, f32_cfg);
+                           lay.nsfe == 8 * recipes[0].in_width + lay.D && fused_supported(h->kn, lay, recipes[0].in_width, f32_cfg);
   // "mixed" (round 4, BASELINE config 3's shape): the state features are exactly stream 0's segment-recipe window and the
   // transition features live in the other streams' columns -- the state part takes the fused kernels, the transition
   // part keeps the materialised first-row windows and the dense contractions
@@ -912,8 +885,8 @@ extern "C" int scrf_batch_create(scrf_handle h, const scrf_utt* utts, uint32_t n
   // counts through the per-frame sums Z (k_lin_z, Z^T F), exactly as on the fused path.
   b->hybrid_ok = !sparse_map && !by_windows && n_streams == 1 && h->cfg.model_type != SCRF_STDSEG_NO_DUR && h->cfg.model_type != SCRF_STDSEG && lay.use_sf &&
                  !lay.use_tf && recipes[0].extract_seg_ftr && !recipes[0].left_ctx && !recipes[0].right_ctx && lay.sfs == 0 && lay.D >= 2 &&
-                 lay.nsfe == 8 * recipes[0].in_width + lay.D && (hybrid_first || !fused_supported(lay, recipes[0].in_width, f32_cfg));
-  const bool mixed_ok = seg_stream0 && n_streams >= 2 && lay.use_tf && lay.tfs >= lay.nsfe && h->fuse_mixed;
+                 lay.nsfe == 8 * recipes[0].in_width + lay.D && (hybrid_first || !fused_supported(h->kn, lay, recipes[0].in_width, f32_cfg));
+  const bool mixed_ok = seg_stream0 && n_streams >= 2 && lay.use_tf && lay.tfs >= lay.nsfe && h->kn.fuse_mixed;
   if ((seg_stream0 && n_streams == 1 && !lay.use_tf && lay.nsfe == lay.F) || mixed_ok) {
     b->fused_ok = true;
     b->mixed = mixed_ok;
@@ -934,8 +907,8 @@ extern "C" int scrf_batch_create(scrf_handle h, const scrf_utt* utts, uint32_t n
     const uint32_t D = lay.D, TB = fused_scores_tb(recipes[0].in_width, D), TBE = fused_expf_frames(D);
     // a third list when the engine trains with the linear window average and its count kernel walks taller tiles
     uint32_t TBL = 0;
-    if (h->cfg.train_precision == SCRF_PREC_FASTLIN && fused_la_supported(lay, recipes[0].in_width)) {
-      const ScrfFusedExpfPlan plan = fused_expf_plan(lay, recipes[0].in_width, 0, 1);
+    if (h->cfg.train_precision == SCRF_PREC_FASTLIN && fused_la_supported(h->kn, lay, recipes[0].in_width)) {
+      const ScrfFusedExpfPlan plan = fused_expf_plan(h->kn, lay, recipes[0].in_width, 0, 1);
       if (plan.tile_list == 2) TBL = plan.frames;
     }
     for (int k = 0; k < (TBL ? 3 : 2); k++) {
@@ -1016,10 +989,9 @@ static uint32_t segtrans_chunks(uint64_t nseg, size_t LL, uint32_t ntf) {
 // of 256 workgroups: with the TIMIT demo's 240 tiles per chunk, 4 chunks are 3.75 rounds (the last one three quarters
 // full), 16 chunks are 15 whole rounds.  Smallest count from 4 up to 16 (at least 1024 rows each) whose last round is >= 97 %
 // full, else the fullest; SCRF_TRANS_CHUNKS overrides (A/B runs).
-static uint32_t transframe_chunks(uint64_t nfr, uint32_t n_out, uint32_t nfun, int f32) {
+static uint32_t transframe_chunks(const ScrfKnobs& kn, uint64_t nfr, uint32_t n_out, uint32_t nfun, int f32) {
   const uint32_t base = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(4, (nfr + 2047) / 2048));
-  static const int forced = getenv("SCRF_TRANS_CHUNKS") ? atoi(getenv("SCRF_TRANS_CHUNKS")) : 0;
-  if (forced > 0) return (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>((uint64_t)forced, std::max<uint64_t>(1, nfr / 64)));
+  if (kn.trans_chunks > 0) return (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>((uint64_t)kn.trans_chunks, std::max<uint64_t>(1, nfr / 64)));
   const uint32_t tiles = expf_mfma_wide_tiles(n_out, nfun, f32);
   if (tiles == 0 || base < 4) return base;
   const uint32_t cus = 256;
@@ -1102,7 +1074,7 @@ struct ChunkBufs {
   bool hybrid = false;       // materialised X, but the sampled blocks through P / Z (scrf_batch::hybrid_ok)
   bool la = false;           // SCRF_PREC_FASTLIN: linear window average (6 groups in P / Z, no avg group in the dense parts)
   double* slab_d = nullptr;  // duration + bias counts of the wave-specialised count kernel (behind slab_s)
-  int expf_tiles = 1;        // tile list the fused count kernel walks
+  ScrfFusedExpfPlan expf_plan = {0, 0, 0, 0, 0, 0, 1, 1};   // the fused count kernel's plan for this chunk (tile list, slab columns)
   ScrfSparseIndex spx[2];    // sparse maps: inverted index + bias slab of the state [0] / transition [1] counts
   ScrfLatBufs lat = {nullptr, nullptr, nullptr, nullptr, nullptr};   // lattice beam: distances of the chunk's states
   uint32_t* lat_counts = nullptr;   // [nodes of the chunk] kept arcs per node
@@ -1136,7 +1108,7 @@ static bool sparse(scrf_handle h) { return h->cfg.map_type >= SCRF_STDSPARSE; }
 
 static bool wave_path(scrf_handle h, bool post) {
   if (h->force_fb || segtrans(h)) return false;
-  return dp_wave_supported(h->lay) || (post && h->lin_dp && (dplin_mw_supported(h->lay) || dplin_supported(h->lay)));
+  return dp_wave_supported(h->lay) || (post && h->kn.lindp && (dplin_mw_supported(h->lay) || dplin_supported(h->lay)));
 }
 
 // fused path: the five sampled blocks as per-frame projections (outputs (k, label), k < 5), and
@@ -1208,7 +1180,7 @@ static void chunk_layout(scrf_handle h, scrf_batch b, uint32_t u0, uint32_t u1, 
   }
   if (nd.fb) {
     cb->wave = wave_path(h, need_lin(nd));
-    cb->lin = cb->wave && need_lin(nd) && h->lin_dp;
+    cb->lin = cb->wave && need_lin(nd) && h->kn.lindp;
     if (cb->lin) {
       cb->smax = a.take<double>(nseg);
       cb->s_true = a.take<double>(nfr);
@@ -1266,7 +1238,7 @@ static void chunk_layout(scrf_handle h, scrf_batch b, uint32_t u0, uint32_t u1, 
         cb->XI = a.take<double>(nfr * LL);
         cb->xrow_next = a.take<uint64_t>(nfr);
         if (!sparse(h)) {   // the sparse transition counts have their own slab (below)
-          cb->nch_t = transframe_chunks(nfr, (uint32_t)LL, scrf_spec_trans(l).nfun(), h->cfg.train_precision == SCRF_PREC_FAST32);
+          cb->nch_t = transframe_chunks(h->kn, nfr, (uint32_t)LL, scrf_spec_trans(l).nfun(), h->cfg.train_precision == SCRF_PREC_FAST32);
           cb->rpc_t = (nfr + cb->nch_t - 1) / cb->nch_t;
           cb->slab_t = a.take<double>((size_t)cb->nch_t * LL * l.ntf);
         }
@@ -1283,9 +1255,8 @@ static void chunk_layout(scrf_handle h, scrf_batch b, uint32_t u0, uint32_t u1, 
       cb->nch_s = (uint32_t)((nseg + cb->rpc_s - 1) / cb->rpc_s);
       if (!sparse(h)) cb->slab_s = a.take<double>((size_t)(nd.fused ? 512 : cb->nch_s) * l.L * l.nsf);
       if (nd.fused && cb->slab_s) {   // the fused count kernel's plan lives inside its 512 slabs: nothing of it is measured
-        const ScrfFusedExpfPlan plan = fused_expf_plan(l, b->recipe[0].in_width, h->cfg.train_precision == SCRF_PREC_FAST32, nd.la);
-        cb->expf_tiles = plan.tile_list;
-        cb->nch_s = fused_expf_blocks(l, b->recipe[0].in_width, h->cfg.train_precision == SCRF_PREC_FAST32,
+        const ScrfFusedExpfPlan& plan = cb->expf_plan = fused_expf_plan(h->kn, l, b->recipe[0].in_width, h->cfg.train_precision == SCRF_PREC_FAST32, nd.la);
+        cb->nch_s = fused_expf_blocks(h->kn, l, b->recipe[0].in_width, h->cfg.train_precision == SCRF_PREC_FAST32,
                                       b->tile_off[plan.tile_list][u1] - b->tile_off[plan.tile_list][u0], nd.la);
         // dense columns + durations + bias <= nsf: the duration slab fits behind the dense one
         cb->slab_d = cb->slab_s + (size_t)cb->nch_s * l.L * plan.ncol;
@@ -1437,7 +1408,7 @@ static bool ensure_m0(scrf_handle h, hipStream_t st) {
   if (h->m0_valid) return false;
   const ScrfLayout& l = h->lay;
   launch_scores_exact(st, nullptr, l.F, nullptr, 1, h->d_lambda, l, 1, l.L * l.L, h->d_m0);
-  launch_exp_m(st, h->d_m0, l.L, 1, h->d_e0, h->d_et0, h->d_msh0);
+  launch_exp_m(st, h->kn, h->d_m0, l.L, 1, h->d_e0, h->d_et0, h->d_msh0);
   h->m0_valid = true;
   return true;
 }
@@ -1458,7 +1429,7 @@ static int run_scores(scrf_handle h, scrf_batch b, uint32_t u0, uint32_t u1, Chu
     PhaseTimer tm(h, PH_SCORE, cb.st);
     const uint32_t W0 = b->recipe[0].in_width;
     ScrfFusedArgs fa = fused_args(h, b, u0, 0);
-    if (h->d_dtab && h->dur_table) {
+    if (h->d_dtab && h->kn.dtab) {
       launch_dur_table(cb.st, l, W0, h->d_lambda, h->d_dtab);
       fa.dtab = h->d_dtab;
       const size_t nb = fused_tile_table_bytes(l.D, fa.TB);
@@ -1468,17 +1439,15 @@ static int run_scores(scrf_handle h, scrf_batch b, uint32_t u0, uint32_t u1, Chu
         h->rtab_bytes = nb;
       }
       launch_tile_tables(cb.st, l.D, fa.TB, (cb.la && !cb.Wn) ? 1 : 0, h->d_rtab);
-      static const bool rtab_on = !(getenv("SCRF_RTAB") && atoi(getenv("SCRF_RTAB")) == 0);   // A/B knob
-      if (rtab_on) fa.rtab = h->d_rtab;
-      static const bool dma_on = !(getenv("SCRF_SCORES_DMA") && atoi(getenv("SCRF_SCORES_DMA")) == 0);   // A/B knob
-      fa.dma = dma_on ? 1 : 0;
+      if (h->kn.rtab) fa.rtab = h->d_rtab;
+      fa.dma = h->kn.scores_dma ? 1 : 0;
     }
     // per-frame projections of the five sampled blocks, then the dense part + gather
     if (pframe_supported(W0)) {
       KT_RUN("k_pframe", cb.st, launch_pframe(cb.st, b->d_frames[0] + b->frame_off[u0] * W0, W0, nfr, h->d_lambda, l, (cb.la ? 6 : 5) * l.L, cb.P));
       if (cb.la) KT_RUN("k_avg_prefix", cb.st, launch_avg_prefix(cb.st, bv, u0, u1 - u0, l.L, cb.P));
     } else {
-      KT_RUN("k_scores_mfma(samples)", cb.st, launch_scores_mfma(cb.st, b->d_frames[0] + b->frame_off[u0] * W0, W0, nullptr, nfr, h->d_lambda, l,
+      KT_RUN("k_scores_mfma(samples)", cb.st, launch_scores_mfma(cb.st, h->kn, b->d_frames[0] + b->frame_off[u0] * W0, W0, nullptr, nfr, h->d_lambda, l,
                          spec_samples(W0), (cb.la ? 6 : 5) * l.L, cb.P));
       if (cb.la) KT_RUN("k_avg_prefix", cb.st, launch_avg_prefix(cb.st, bv, u0, u1 - u0, l.L, cb.P));
     }
@@ -1493,7 +1462,7 @@ static int run_scores(scrf_handle h, scrf_batch b, uint32_t u0, uint32_t u1, Chu
       // separately rounded products added one by one; m <= 3 W + 8 roundings on any term's way through
       // the fused evaluation (MFMA accumulation of the 3W dense columns or a W-term P dot, gather and
       // epilogue adds).  1 % covers gamma's denominator and the rounding of the bound itself.
-      dz.bound_scale = h->decode_bound_factor * 1.01 * 0x1p-53 * (double)(l.nsfe + 1 + 3 * W0 + 8);
+      dz.bound_scale = h->kn.decode_bound_scale * 1.01 * 0x1p-53 * (double)(l.nsfe + 1 + 3 * W0 + 8);
       PhaseTimer tk(h, PH_K_SCORE, cb.st);
       KT_RUN("k_scores_fused(decode)", cb.st, launch_scores_fused_decode(cb.st, fa, l, h->d_lambda, cb.P, b->tile_off[0][u1] - b->tile_off[0][u0], dz));
       tk.stop(1);
@@ -1526,10 +1495,10 @@ static int run_scores(scrf_handle h, scrf_batch b, uint32_t u0, uint32_t u1, Chu
     // as per-frame projections added by row
     const uint32_t W0 = b->recipe[0].in_width;
     if (pframe_supported(W0)) KT_RUN("k_pframe", cb.st, launch_pframe(cb.st, b->d_frames[0] + b->frame_off[u0] * W0, W0, nfr, h->d_lambda, l, 5 * l.L, cb.P));
-    else KT_RUN("k_scores_mfma(samples)", cb.st, launch_scores_mfma(cb.st, b->d_frames[0] + b->frame_off[u0] * W0, W0, nullptr, nfr, h->d_lambda, l,
+    else KT_RUN("k_scores_mfma(samples)", cb.st, launch_scores_mfma(cb.st, h->kn, b->d_frames[0] + b->frame_off[u0] * W0, W0, nullptr, nfr, h->d_lambda, l,
                                                                      spec_samples(W0), 5 * l.L, cb.P, f32));
     PhaseTimer tk(h, PH_K_SCORE, cb.st);
-    KT_RUN("k_scores_mfma(state)", cb.st, launch_scores_mfma(cb.st, cb.X, hybrid_row_floats(l, W0), nullptr, nseg, h->d_lambda, l, spec_dense_x(l, W0), l.L, cb.S, f32));
+    KT_RUN("k_scores_mfma(state)", cb.st, launch_scores_mfma(cb.st, h->kn, cb.X, hybrid_row_floats(l, W0), nullptr, nseg, h->d_lambda, l, spec_dense_x(l, W0), l.L, cb.S, f32));
     // + the labelled windows' scores, the row maxima and exp(S - smax) for the linear-domain recursion (cb.lin)
     KT_RUN("k_add_p_exp", cb.st, launch_add_p_exp(cb.st, l, bv, b->d_frame_u, u0, nfr, cb.P, cb.S, cb.smax, cb.s_true));
     cb.es_ready = true;
@@ -1550,7 +1519,7 @@ static int run_scores(scrf_handle h, scrf_batch b, uint32_t u0, uint32_t u1, Chu
     }
   } else if (!cb.fused) {
     PhaseTimer tk(h, PH_K_SCORE, cb.st);
-    if (fast) KT_RUN("k_scores_mfma(state)", cb.st, launch_scores_mfma(cb.st, cb.X, l.F, nullptr, nseg, h->d_lambda, l, scrf_spec_state(l), l.L, cb.S, f32));
+    if (fast) KT_RUN("k_scores_mfma(state)", cb.st, launch_scores_mfma(cb.st, h->kn, cb.X, l.F, nullptr, nseg, h->d_lambda, l, scrf_spec_state(l), l.L, cb.S, f32));
     else KT_RUN("k_scores_exact(state)", cb.st, launch_scores_exact(cb.st, cb.X, l.F, nullptr, nseg, h->d_lambda, l, 0, l.L, cb.S));
     tk.stop(1);
   }
@@ -1559,13 +1528,13 @@ static int run_scores(scrf_handle h, scrf_batch b, uint32_t u0, uint32_t u1, Chu
   } else if (segtrans(h)) {
     // one transition matrix per window: the same contraction over every row of X; the rows of the
     // utterance-initial segments (no predecessor) are zeroed like the reference leaves them unused
-    if (fast) KT_RUN("k_scores_mfma(trans)", cb.st, launch_scores_mfma(cb.st, cb.X, l.F, nullptr, nseg, h->d_lambda, l, scrf_spec_trans(l), l.L * l.L, cb.M, f32));
+    if (fast) KT_RUN("k_scores_mfma(trans)", cb.st, launch_scores_mfma(cb.st, h->kn, cb.X, l.F, nullptr, nseg, h->d_lambda, l, scrf_spec_trans(l), l.L * l.L, cb.M, f32));
     else KT_RUN("k_scores_exact(trans)", cb.st, launch_scores_exact(cb.st, cb.X, l.F, nullptr, nseg, h->d_lambda, l, 1, l.L * l.L, cb.M));
     launch_zero_initial_rows(cb.st, bv, b->d_frame_u, u0, nfr, l.D, l.L, cb.M);
     nl += 2;
   } else if (l.use_tf) {
     launch_frame_rows(cb.st, bv, u0, u1, l.D, nfr, cb.xrow_cur, 0);
-    if (fast) KT_RUN("k_scores_mfma(trans)", cb.st, launch_scores_mfma(cb.st, cb.X, l.F, cb.xrow_cur, nfr, h->d_lambda, l, scrf_spec_trans(l), l.L * l.L, cb.M, f32));
+    if (fast) KT_RUN("k_scores_mfma(trans)", cb.st, launch_scores_mfma(cb.st, h->kn, cb.X, l.F, cb.xrow_cur, nfr, h->d_lambda, l, scrf_spec_trans(l), l.L * l.L, cb.M, f32));
     else KT_RUN("k_scores_exact(trans)", cb.st, launch_scores_exact(cb.st, cb.X, l.F, cb.xrow_cur, nfr, h->d_lambda, l, 1, l.L * l.L, cb.M));
     nl += 2;
   } else if (ensure_m0(h, cb.st)) nl += 2;
@@ -1588,7 +1557,7 @@ static int run_dp(scrf_handle h, scrf_batch b, uint32_t u0, uint32_t u1, ChunkBu
     if (fb_segtrans_smem_bytes(l, fb_block_threads(l)) > 160 * 1024)
       return fail(h, SCRF_ERR_INVALID, "labels x maximum duration = %u x %u is too large for the stdseg_no_dur recursion "
                   "(its three [D][L] rings must fit 160 KB of LDS)", l.L, l.D);
-    KT_RUN("k_fb_segtrans", cb.st, launch_fb_segtrans(cb.st, l, bv, u0, (uint32_t)nutt, b->d_prev_lab, cb.S, cb.M, cb.AD, cb.alpha, cb.beta,
+    KT_RUN("k_fb_segtrans", cb.st, launch_fb_segtrans(cb.st, h->kn, l, bv, u0, (uint32_t)nutt, b->d_prev_lab, cb.S, cb.M, cb.AD, cb.alpha, cb.beta,
                        post ? cb.XI : nullptr, b->d_numer, b->d_zx, b->d_status, post ? 1 : 0));
     nl = 1;
   } else if (!cb.wave) {
@@ -1600,7 +1569,7 @@ static int run_dp(scrf_handle h, scrf_batch b, uint32_t u0, uint32_t u1, ChunkBu
               post ? cb.xi_acc : nullptr, b->d_numer, b->d_zx, b->d_status, post ? 1 : 0, frame_model));
     nl = 1;
   } else {
-    if (cb.m_per_frame) { KT_RUN("k_exp_m", cb.st, launch_exp_m(cb.st, cb.M, l.L, nfr, cb.E, cb.ET, cb.msh)); nl++; }
+    if (cb.m_per_frame) { KT_RUN("k_exp_m", cb.st, launch_exp_m(cb.st, h->kn, cb.M, l.L, nfr, cb.E, cb.ET, cb.msh)); nl++; }
     if (cb.lin) {
       const uint64_t nseg = b->seg_off[u1] - b->seg_off[u0];
       if (!cb.es_ready) {
@@ -1610,7 +1579,7 @@ static int run_dp(scrf_handle h, scrf_batch b, uint32_t u0, uint32_t u1, ChunkBu
       }
       {
         PhaseTimer tk(h, PH_K_DP, cb.st);
-        KT_RUN(l.L > 64 ? "k_dp_lin_mw" : "k_dp_lin", cb.st, launch_dp_lin(cb.st, l, bv, u0, (uint32_t)nutt, cb.S, cb.smax, cb.E, cb.ET, cb.msh, cb.m_per_frame, cb.dl,
+        KT_RUN(l.L > 64 ? "k_dp_lin_mw" : "k_dp_lin", cb.st, launch_dp_lin(cb.st, h->kn, l, bv, u0, (uint32_t)nutt, cb.S, cb.smax, cb.E, cb.ET, cb.msh, cb.m_per_frame, cb.dl,
                       b->d_zx, b->d_status));
         tk.stop(1);
       }
@@ -1624,7 +1593,7 @@ static int run_dp(scrf_handle h, scrf_batch b, uint32_t u0, uint32_t u1, ChunkBu
         if (l.L > 64) HIPCHK(h, hipMemsetAsync(cb.mass_s, 0, sizeof(double) * nfr, cb.st));   // summed over the 64-output groups
         uint32_t t_max = 0;   // the longest utterance of the chunk: a launch of few utterances splits each into segments
         for (uint64_t u = u0; u < u1; u++) t_max = std::max(t_max, b->T[u]);
-        KT_RUN("k_post_z", cb.st, launch_post_z(cb.st, l, bv, u0, (uint32_t)nutt, b->d_next_lab, cb.s_true, cb.M, cb.m_per_frame, cb.S, cb.smax,
+        KT_RUN("k_post_z", cb.st, launch_post_z(cb.st, h->kn, l, bv, u0, (uint32_t)nutt, b->d_next_lab, cb.s_true, cb.M, cb.m_per_frame, cb.S, cb.smax,
                       cb.dl, b->d_zx, cb.numer_f, b->d_status, cb.Z, cb.mass_s, cb.la ? 1 : 0, t_max, nfr));
         cb.z_ready = true;
       } else {
@@ -1772,7 +1741,7 @@ static size_t stdseg_chunk_size(scrf_handle h, scrf_batch b, uint32_t u0, uint32
 // ---- STDSEG, bias-only transitions, FAST precisions, training path: scrf_stdseg_lin.hip (not during a log-domain redo,
 // force_fb: that one runs k_stdseg_fb, the reference's order)
 static bool stdseg_lin(scrf_handle h) {
-  return h->stdseg_lin && !h->force_fb && h->cfg.train_precision != SCRF_PREC_EXACT && h->lay.use_sf && stdseg_lin_supported(h->lay, stdseg_La(h));
+  return h->kn.stdseg_lin && !h->force_fb && h->cfg.train_precision != SCRF_PREC_EXACT && h->lay.use_sf && stdseg_lin_supported(h->lay, stdseg_La(h));
 }
 static uint64_t sl_rows_per_chunk(uint64_t nfr) {   // K-chunks of the count contractions: <= 256 of them, multiples of 32 frames
   uint64_t rpc = ((nfr + 255) / 256 + 31) & ~31ull;
@@ -1829,7 +1798,7 @@ static int stdseg_lin_run_chunk(scrf_handle h, scrf_batch b, uint32_t u0, uint32
     KernelTimer kt(h, "k_scores_mfma(state, per duration)", st);
     for (uint32_t d0 = 0; d0 < l.D; d0++) {
       const ScrfGemmSpec sp{0, l.sfs, l.nsfe, (uint32_t)l.use_sb, l.sbv, d0 * La * l.stride, 0};
-      launch_scores_mfma(st, sb.X, l.F, sb.xrow + (size_t)d0 * nfr, nfr, h->d_lambda, l, sp, La, sb.Sd + (size_t)d0 * nfr * La, f32);
+      launch_scores_mfma(st, h->kn, sb.X, l.F, sb.xrow + (size_t)d0 * nfr, nfr, h->d_lambda, l, sp, La, sb.Sd + (size_t)d0 * nfr * La, f32);
     }
     kt.stop(l.D);
   }
@@ -1840,7 +1809,7 @@ static int stdseg_lin_run_chunk(scrf_handle h, scrf_batch b, uint32_t u0, uint32
     KernelTimer kt(h, "k_expf_mfma(state, per duration)", st);
     for (uint32_t d0 = 0; d0 < l.D; d0++) {
       const ScrfGemmSpec sp{0, l.sfs, l.nsfe, (uint32_t)l.use_sb, l.sbv, d0 * La * l.stride, 0};
-      launch_expf_mfma(st, sb.Rd + (size_t)d0 * nfr * La, La, sb.X, l.F, sb.xrow + (size_t)d0 * nfr, nfr, l, sp, sb.rpc, sb.nch, sb.slab_s, f32);
+      launch_expf_mfma(st, h->kn, sb.Rd + (size_t)d0 * nfr * La, La, sb.X, l.F, sb.xrow + (size_t)d0 * nfr, nfr, l, sp, sb.rpc, sb.nch, sb.slab_s, f32);
       launch_reduce_slabs(st, sb.slab_s, sb.nch, La, l, sp, grad);
     }
     kt.stop(2 * l.D);
@@ -1962,10 +1931,10 @@ struct BatchForm { bool fusable, hybrid, la; };
 static BatchForm batch_form(scrf_handle h, scrf_batch b) {
   const uint32_t prec = h->cfg.train_precision;
   BatchForm f;
-  f.fusable = b->fused_ok && h->fuse_windows;
-  f.hybrid = !f.fusable && b->hybrid_ok && h->hybrid && h->fuse_windows && prec >= SCRF_PREC_FAST && prec != SCRF_PREC_FAST32 && h->lin_dp &&
+  f.fusable = b->fused_ok && h->kn.fuse;
+  f.hybrid = !f.fusable && b->hybrid_ok && h->kn.hybrid_on() && h->kn.fuse && prec >= SCRF_PREC_FAST && prec != SCRF_PREC_FAST32 && h->kn.lindp &&
              wave_path(h, true);
-  f.la = prec == SCRF_PREC_FASTLIN && h->lin_dp && wave_path(h, true) && fused_la_supported(h->lay, b->recipe[0].in_width);
+  f.la = prec == SCRF_PREC_FASTLIN && h->kn.lindp && wave_path(h, true) && fused_la_supported(h->kn, h->lay, b->recipe[0].in_width);
   return f;
 }
 static void set_batch_form(scrf_handle h, scrf_batch b, Need* nd) {
@@ -2014,7 +1983,7 @@ static int fb_run(scrf_handle h, scrf_batch b, int latch[2], bool* used_lin) {
   // plan the chunks first: each must fit the scratch budget; with two lanes a batch is cut into
   // at least four chunks so that both streams always have work
   std::vector<uint32_t> cuts(1, 0);
-  const bool two_lanes = h->n_lanes > 1 && !h->timing && b->U >= 64;
+  const bool two_lanes = h->kn.lanes > 1 && !h->timing && b->U >= 64;
   {
     const uint32_t cap = two_lanes ? (b->U + 3) / 4 : b->U;
     for (uint32_t u0 = 0; u0 < b->U;) {
@@ -2063,7 +2032,7 @@ static int fb_run(scrf_handle h, scrf_batch b, int latch[2], bool* used_lin) {
     // are committed and their all-reduce goes to the second stream, under the state contraction.  A NUMERIC failure of
     // the recursion is retried with the log-domain kernels by the caller: that has to be known BEFORE a collective is
     // issued (the peers issue theirs exactly once), so the host waits for the status here.
-    const bool ov = h->overlap_comm && h->comm_overlap_on && two_block_reduce(h) && !use2 && !h->timing && !sparse(h);
+    const bool ov = h->overlap_comm && h->kn.comm_overlap && two_block_reduce(h) && !use2 && !h->timing && !sparse(h);
     bool trans_done = false;   // the transition counts of this chunk are already in the staged gradient
     if (ov) {
       if (ci + 1 == n_chunks) {
@@ -2072,7 +2041,7 @@ static int fb_run(scrf_handle h, scrf_batch b, int latch[2], bool* used_lin) {
         if (latch[0] == SCRF_ERR_NUMERIC && wave_path(h, true)) return SCRF_OK;   // the caller reruns; nothing committed, nothing sent
       }
       launch_frame_rows(cb.st, bv, u0, u1, l.D, nfr, cb.xrow_next, 1);
-      if (fast) launch_expf_mfma(cb.st, cb.XI, l.L * l.L, cb.X, l.F, cb.xrow_next, nfr, l, scrf_spec_trans(l), cb.rpc_t, cb.nch_t, cb.slab_t, f32);
+      if (fast) launch_expf_mfma(cb.st, h->kn, cb.XI, l.L * l.L, cb.X, l.F, cb.xrow_next, nfr, l, scrf_spec_trans(l), cb.rpc_t, cb.nch_t, cb.slab_t, f32);
       else launch_expf_gemm(cb.st, cb.XI, l.L * l.L, cb.X, l.F, cb.xrow_next, nfr, l, 1, cb.rpc_t, cb.nch_t, cb.slab_t);
       launch_reduce_slabs(cb.st, cb.slab_t, cb.nch_t, l.L * l.L, l, scrf_spec_trans(l), cb.grad);
       if (ci + 1 == n_chunks) {
@@ -2088,19 +2057,21 @@ static int fb_run(scrf_handle h, scrf_batch b, int latch[2], bool* used_lin) {
       trans_done = true;   // the state part (fused or dense) follows below, under the transition block's all-reduce
     }
     bool side = false;   // part of the count work runs on the second stream (below)
+    uint32_t t_max = 0;   // longest utterance of the chunk (hybrid path: k_lin_z5's segments, here and at the reduction)
+    if (cb.hybrid) for (uint64_t u = u0; u < u1; u++) t_max = std::max(t_max, b->T[u]);
     {
       PhaseTimer tm(h, PH_EXPF, cb.st);
       uint32_t nl = 1;
       if (cb.fused) {
         const uint32_t W0 = b->recipe[0].in_width;
-        ScrfFusedArgs fa = fused_args(h, b, u0, cb.expf_tiles);
+        ScrfFusedArgs fa = fused_args(h, b, u0, cb.expf_plan.tile_list);
         // Side stream (round 4): the per-frame count contraction k_ztf, its reduction and the transition counts A^T B
         // need Z / the recursion's vectors, not R's contraction -- they run on the engine's second stream UNDER
         // k_expf_fused_ws, whose one workgroup per CU leaves 80 registers per SIMD lane and the wave slots for a narrow
         // k_ztf (one output tile per wavefront).  The two sides add into disjoint weights; the streams join before the
         // commit.  Off while kernels are timed one by one (scrf_enable_timing) and with SCRF_SIDE=0.
-        side = h->side_stream && !use2 && !h->timing && cb.z_ready && pframe_supported(W0) && !l.use_tf && !segtrans(h) && cb.wave &&
-               fused_expf_plan(l, W0, f32, cb.la ? 1 : 0).ws;
+        side = h->kn.side && !use2 && !h->timing && cb.z_ready && pframe_supported(W0) && !l.use_tf && !segtrans(h) && cb.wave &&
+               cb.expf_plan.ws;
         if (side) {
           HIPCHK(h, hipEventRecord(h->ev_fork, cb.st));
           HIPCHK(h, hipStreamWaitEvent(h->stream2, h->ev_fork, 0));
@@ -2111,15 +2082,14 @@ static int fb_run(scrf_handle h, scrf_batch b, int latch[2], bool* used_lin) {
         }
         {
           PhaseTimer tk(h, PH_K_EXPF, cb.st);
-          KT_RUN("k_expf_fused", cb.st, launch_expf_fused(cb.st, fa, l, cb.R, b->tile_off[cb.expf_tiles][u1] - b->tile_off[cb.expf_tiles][u0], cb.slab_s, cb.slab_d, f32, cb.la ? 1 : 0));
+          KT_RUN("k_expf_fused", cb.st, launch_expf_fused(cb.st, h->kn, fa, l, cb.R, b->tile_off[cb.expf_plan.tile_list][u1] - b->tile_off[cb.expf_plan.tile_list][u0], cb.slab_s, cb.slab_d, f32, cb.la ? 1 : 0));
           tk.stop(1);
         }
         if (!cb.z_ready) KT_RUN("k_lin_z", cb.st, launch_lin_z(cb.st, l, bv, u0, (uint32_t)nutt, cb.R, cb.Z));
-        if (side) {
-        } else if (pframe_supported(W0))
+        if (!side && pframe_supported(W0))   // (side: k_ztf ran on the second stream)
           KT_RUN("k_ztf", cb.st, launch_ztf(cb.st, cb.Z, (cb.la ? 6 : 5) * l.L, b->d_frames[0] + b->frame_off[u0] * W0, W0, nfr, cb.rpc_l, cb.nch_l, cb.slab_l));
-        else
-          KT_RUN("k_expf_mfma(samples)", cb.st, launch_expf_mfma(cb.st, cb.Z, (cb.la ? 6 : 5) * l.L, b->d_frames[0] + b->frame_off[u0] * W0, W0, nullptr, nfr, l,
+        else if (!side)
+          KT_RUN("k_expf_mfma(samples)", cb.st, launch_expf_mfma(cb.st, h->kn, cb.Z, (cb.la ? 6 : 5) * l.L, b->d_frames[0] + b->frame_off[u0] * W0, W0, nullptr, nfr, l,
                            spec_samples(W0), cb.rpc_l, cb.nch_l, cb.slab_l));
         nl += 2;
       } else if (cb.hybrid) {
@@ -2128,16 +2098,14 @@ static int fb_run(scrf_handle h, scrf_batch b, int latch[2], bool* used_lin) {
           PhaseTimer tk(h, PH_K_EXPF, cb.st);
           // [avg | max | min] only: the one-hot duration and bias counts are sums of R (k_lin_z5), and 3 W columns are one
           // 384-column tile of the count kernel where 3 W + D + 1 were two
-          KT_RUN("k_expf_mfma(state)", cb.st, launch_expf_mfma(cb.st, cb.R, l.L, cb.X, hybrid_row_floats(l, W0), nullptr, nseg, l, spec_stats_x(l, W0), cb.rpc_s, cb.nch_s, cb.slab_s, f32));
+          KT_RUN("k_expf_mfma(state)", cb.st, launch_expf_mfma(cb.st, h->kn, cb.R, l.L, cb.X, hybrid_row_floats(l, W0), nullptr, nseg, l, spec_stats_x(l, W0), cb.rpc_s, cb.nch_s, cb.slab_s, f32));
           tk.stop(1);
         }
-        uint32_t t_max = 0;
-        for (uint64_t u = u0; u < u1; u++) t_max = std::max(t_max, b->T[u]);
         KT_RUN("k_lin_z5", cb.st, launch_lin_z5(cb.st, l, bv, u0, (uint32_t)nutt, t_max, nfr, cb.R, cb.Z, cb.slab_d));
         if (pframe_supported(W0))
           KT_RUN("k_ztf", cb.st, launch_ztf(cb.st, cb.Z, 5 * l.L, b->d_frames[0] + b->frame_off[u0] * W0, W0, nfr, cb.rpc_l, cb.nch_l, cb.slab_l));
         else
-          KT_RUN("k_expf_mfma(samples)", cb.st, launch_expf_mfma(cb.st, cb.Z, 5 * l.L, b->d_frames[0] + b->frame_off[u0] * W0, W0, nullptr, nfr, l,
+          KT_RUN("k_expf_mfma(samples)", cb.st, launch_expf_mfma(cb.st, h->kn, cb.Z, 5 * l.L, b->d_frames[0] + b->frame_off[u0] * W0, W0, nullptr, nfr, l,
                            spec_samples(W0), cb.rpc_l, cb.nch_l, cb.slab_l));
         nl += 2;
       } else if (sparse(h)) {
@@ -2153,19 +2121,18 @@ static int fb_run(scrf_handle h, scrf_batch b, int latch[2], bool* used_lin) {
         }
       } else {
         PhaseTimer tk(h, PH_K_EXPF, cb.st);
-        if (fast) KT_RUN("k_expf_mfma(state)", cb.st, launch_expf_mfma(cb.st, cb.R, l.L, cb.X, l.F, nullptr, nseg, l, scrf_spec_state(l), cb.rpc_s, cb.nch_s, cb.slab_s, f32));
+        if (fast) KT_RUN("k_expf_mfma(state)", cb.st, launch_expf_mfma(cb.st, h->kn, cb.R, l.L, cb.X, l.F, nullptr, nseg, l, scrf_spec_state(l), cb.rpc_s, cb.nch_s, cb.slab_s, f32));
         else KT_RUN("k_expf_gemm(state)", cb.st, launch_expf_gemm(cb.st, cb.R, l.L, cb.X, l.F, nullptr, nseg, l, 0, cb.rpc_s, cb.nch_s, cb.slab_s));
         tk.stop(1);
       }
-      if (sparse(h)) {
-      } else if (segtrans(h)) {
+      if (!sparse(h) && segtrans(h)) {
         // transition counts of the segment's own window: XI2 rows are windows, no row map
-        if (fast) KT_RUN("k_expf_mfma(trans)", cb.st, launch_expf_mfma(cb.st, cb.XI, l.L * l.L, cb.X, l.F, nullptr, nseg, l, scrf_spec_trans(l), cb.rpc_t, cb.nch_t, cb.slab_t, f32));
+        if (fast) KT_RUN("k_expf_mfma(trans)", cb.st, launch_expf_mfma(cb.st, h->kn, cb.XI, l.L * l.L, cb.X, l.F, nullptr, nseg, l, scrf_spec_trans(l), cb.rpc_t, cb.nch_t, cb.slab_t, f32));
         else KT_RUN("k_expf_gemm(trans)", cb.st, launch_expf_gemm(cb.st, cb.XI, l.L * l.L, cb.X, l.F, nullptr, nseg, l, 1, cb.rpc_t, cb.nch_t, cb.slab_t));
         nl += 1;
-      } else if (l.use_tf && !trans_done) {
+      } else if (!sparse(h) && l.use_tf && !trans_done) {
         launch_frame_rows(cb.st, bv, u0, u1, l.D, nfr, cb.xrow_next, 1);
-        if (fast) KT_RUN("k_expf_mfma(trans)", cb.st, launch_expf_mfma(cb.st, cb.XI, l.L * l.L, cb.X, l.F, cb.xrow_next, nfr, l, scrf_spec_trans(l), cb.rpc_t, cb.nch_t, cb.slab_t, f32));
+        if (fast) KT_RUN("k_expf_mfma(trans)", cb.st, launch_expf_mfma(cb.st, h->kn, cb.XI, l.L * l.L, cb.X, l.F, cb.xrow_next, nfr, l, scrf_spec_trans(l), cb.rpc_t, cb.nch_t, cb.slab_t, f32));
         else KT_RUN("k_expf_gemm(trans)", cb.st, launch_expf_gemm(cb.st, cb.XI, l.L * l.L, cb.X, l.F, cb.xrow_next, nfr, l, 1, cb.rpc_t, cb.nch_t, cb.slab_t));
         nl += 2;
       }
@@ -2176,7 +2143,7 @@ static int fb_run(scrf_handle h, scrf_batch b, int latch[2], bool* used_lin) {
       KernelTimer kt(h, "reductions (k_reduce_slabs, k_atb, k_batch_sums)", cb.st);
       if (cb.fused) {
         const uint32_t W0 = b->recipe[0].in_width;
-        const ScrfFusedExpfPlan plan = fused_expf_plan(l, W0, f32, cb.la ? 1 : 0);
+        const ScrfFusedExpfPlan& plan = cb.expf_plan;
         if (plan.ndur) {
           // dense groups [avg |] max | min at columns (5 + g0) W ..; one-hot duration + bias counts from their own slab
           launch_reduce_slabs(cb.st, cb.slab_s, cb.nch_s, l.L, l, ScrfGemmSpec{0, 0, plan.ncol, 0, 0.0, (5 + plan.g0) * W0, 0}, cb.grad);
@@ -2185,8 +2152,6 @@ static int fb_run(scrf_handle h, scrf_batch b, int latch[2], bool* used_lin) {
         if (!side) launch_reduce_slabs(cb.st, cb.slab_l, cb.nch_l, (cb.la ? 6 : 5) * l.L, l, spec_samples(W0), cb.grad);
       } else if (cb.hybrid) {
         const uint32_t W0 = b->recipe[0].in_width;
-        uint32_t t_max = 0;
-        for (uint64_t u = u0; u < u1; u++) t_max = std::max(t_max, b->T[u]);
         int seg_len = 0;
         const uint32_t nblk_d = (uint32_t)nutt * lin_z5_segments((uint32_t)nutt, l.L, l.D, t_max, &seg_len);
         launch_reduce_slabs(cb.st, cb.slab_s, cb.nch_s, l.L, l, spec_stats_x(l, W0), cb.grad);
@@ -2326,7 +2291,7 @@ static int post_run(scrf_handle h, scrf_batch b, const PostOut& po, int latch[2]
       for (uint64_t u = u0; u < u1; u++) t_max = std::max(t_max, b->T[u]);
       uint32_t nz = 1;
       KT_RUN("k_post_occ", cb.st, nz = launch_post_occ(cb.st, l, bv, u0, (uint32_t)nutt, t_max, nfr, cb.S, cb.smax, cb.dl, b->d_zx, b->d_status, occ,
-                      cb.mass_part, cb.mass_s, h->post_split ? 1 : 0));
+                      cb.mass_part, cb.mass_s, h->kn.postocc_split ? 1 : 0));
       if (nz > 1) h->n_post_split++; else h->n_post_whole++;
       if (post_occ_groups(l) > 1) nl++;   // k_sum_groups
       KT_RUN("k_mass_check", cb.st, launch_mass_check(cb.st, bv, b->d_frame_u, u0, nfr, l.L, frame_model, 1, cb.dl.a, cb.dl.ga, cb.dl.b, cb.dl.gb,
@@ -2885,7 +2850,7 @@ static int decode_chunks(scrf_handle h, scrf_batch b, const Need& nd, Search&& s
   const bool frame_model = h->cfg.model_type == SCRF_STDFRAME;
   Need ndf = nd;
   ndf.fused = ndf.vitfast = true;
-  const bool fast = h->fast_decode && b->fused_ok && !b->mixed && h->fuse_windows && !frame_model && l.L <= 0xffff;
+  const bool fast = h->kn.fast_decode && b->fused_ok && !b->mixed && h->kn.fuse && !frame_model && l.L <= 0xffff;
   int rc = SCRF_OK;
   for (uint32_t u0 = 0; u0 < b->U && rc == SCRF_OK;) {
     uint32_t u_end = u0;
@@ -3015,7 +2980,7 @@ extern "C" int scrf_viterbi_batch(scrf_handle h, scrf_batch b, uint32_t* seg_lab
   else
     rc = decode_chunks(h, b, Need{false, false, false, true}, [&](const ChunkBufs& cb, uint32_t u0, uint32_t u1, bool fast) {
       if (fast && viterbi_fast_supported(l))
-        launch_viterbi_fast(h->stream, l, b->view(), u0, u1 - u0, cb.Wn, cb.M, cb.bp_b, cb.bp_e, d_lab, d_n, d_cost);
+        launch_viterbi_fast(h->stream, h->kn, l, b->view(), u0, u1 - u0, cb.Wn, cb.M, cb.bp_b, cb.bp_e, d_lab, d_n, d_cost);
       else if (fast)
         launch_viterbi(h->stream, l, b->view(), u0, u1 - u0, nullptr, cb.M, cb.m_per_frame, 0, cb.bp_b, cb.bp_e, d_lab, d_n,
                        d_cost, cb.Wn);
@@ -3049,7 +3014,7 @@ extern "C" int scrf_align_batch(scrf_handle h, scrf_batch b, const uint32_t* pho
   if (phone_off[0] != 0 || (NP && !phones)) return fail(h, SCRF_ERR_INVALID, "scrf_align_batch: phone_off must start at 0 and phones must be given");
   // back-pointer cells before each utterance (the chunk planner sizes a chunk with them), the longest transcript the
   // workgroup kernel may meet
-  const bool wave_on = h->align_wave && align_wave_supported(l);
+  const bool wave_on = h->kn.align_wave && align_wave_supported(l);
   h->al_bp_off.assign(U + 1, 0);
   for (uint32_t u = 0; u < U; u++) {
     if (phone_off[u + 1] < phone_off[u]) return fail(h, SCRF_ERR_INVALID, "scrf_align_batch: phone_off decreases at utterance %u", u);

@@ -1725,7 +1725,7 @@ __global__ __launch_bounds__(64, 2) void k_post_z(ScrfLayout lay, ScrfBatchView 
   if (__any(err != 0) && lane == 0) atomicMax(&status[u], err > 0 ? err : SCRF_ERR_NUMERIC);
 }
 
-void launch_post_z(hipStream_t st, const ScrfLayout& lay, ScrfBatchView bv, uint32_t u0, uint32_t n_utts,
+void launch_post_z(hipStream_t st, const ScrfKnobs& kn, const ScrfLayout& lay, ScrfBatchView bv, uint32_t u0, uint32_t n_utts,
                    const uint32_t* next_lab, const double* s_true, const double* M, int m_per_frame, double* ES,
                    const double* smax, const ScrfDpLin& o, const double* zx, double* numer_f, int* status, double* Z,
                    double* mass_s, int la, uint32_t t_max, uint64_t n_frames) {
@@ -1734,11 +1734,10 @@ void launch_post_z(hipStream_t st, const ScrfLayout& lay, ScrfBatchView bv, uint
   // few wavefronts (a small minibatch): several segments per utterance, about four wavefronts per CU in all (half the
   // kernel's occupancy), no segment shorter than 2 D frames (SCRF_POSTZ_SPLIT=0: never).  Config 3, 256 utterances:
   // 1.21 -> 0.50 ms; config 2's shape at 64 utterances: 1.90 -> 0.38 ms
-  static const bool split_ok = !(getenv("SCRF_POSTZ_SPLIT") && atoi(getenv("SCRF_POSTZ_SPLIT")) == 0);
   int seg_len = 0;
   uint32_t nz = 1;
   const uint64_t waves = (uint64_t)grid.x * grid.y;
-  if (split_ok && waves <= 2 * 256 && t_max >= 4 * lay.D) {
+  if (kn.postz_split && waves <= 2 * 256 && t_max >= 4 * lay.D) {
     const uint32_t want = (uint32_t)((4 * 256 + waves - 1) / waves);
     seg_len = (int)((t_max + want - 1) / want);
     if (seg_len < (int)(2 * lay.D)) seg_len = (int)(2 * lay.D);
@@ -2405,32 +2404,26 @@ static int fused_expf_ws_zb(uint32_t W, int g0) { return !fused_expf_ws_fits(W, 
 // The R tiles go to LDS by DMA (16-byte pieces) when every output pair of R is 16-byte aligned: an even row length
 // (and an aligned base, checked at the launch); odd L keeps the register path.  SCRF_EXPF_DMA=0 forces the register
 // path (A/B measurements, tests).
-static bool fused_expf_dma(uint32_t L) {
-  static const bool on = !(getenv("SCRF_EXPF_DMA") && atoi(getenv("SCRF_EXPF_DMA")) == 0);
-  return on && !(L & 1);
-}
-static uint32_t fused_expf_ws_rows(uint32_t W, int g0) {
+static bool fused_expf_dma(const ScrfKnobs& kn, uint32_t L) { return kn.expf_dma && !(L & 1); }
+static uint32_t fused_expf_ws_rows(const ScrfKnobs& kn, uint32_t W, int g0) {
   // Tall tiles only when the side stream is off, or on request (SCRF_EXPF_BIG=1).  On the register path 100-row tiles
   // take 245 registers and cannot share a SIMD with the side stream's narrow k_ztf (29.22 against 29.46 ms for the
   // 76-row form with that overlap; without the side stream 29.54 against 29.43).  On the DMA path both heights fit
   // beside k_ztf (178 / 184 registers) and the tall form is the faster kernel (5.8 against 6.3 ms), but a 100-row tile
   // list deals other rows to each workgroup's slab, so the counts come out in another summation order (2e-15 relative
   // on the weights after five steps): the default keeps the order the 76-row list gives.
-  static const bool side = !(getenv("SCRF_SIDE") && atoi(getenv("SCRF_SIDE")) == 0);
-  static const bool big = getenv("SCRF_EXPF_BIG") ? atoi(getenv("SCRF_EXPF_BIG")) != 0 : !side;
   uint32_t n_ct;
   fused_expf_ws_xs(W, g0, 0, &n_ct);
-  return (big && g0 == 1 && n_ct <= 5 && !fused_expf_ws_zb(W, g0) && fused_expf_ws_smem_rows(W, g0, 0, FW_ROWS_BIG) <= 160 * 1024) ? FW_ROWS_BIG : FE_ROWS;
+  return (kn.expf_big && g0 == 1 && n_ct <= 5 && !fused_expf_ws_zb(W, g0) && fused_expf_ws_smem_rows(W, g0, 0, FW_ROWS_BIG) <= 160 * 1024) ? FW_ROWS_BIG : FE_ROWS;
 }
-static bool fused_expf_ws(const ScrfLayout& lay, uint32_t W, int f32, int g0) {
-  static const bool on = !(getenv("SCRF_EXPF_WS") && atoi(getenv("SCRF_EXPF_WS")) == 0);
-  return on && !f32 && (fused_expf_ws_fits(W, g0, 0) || fused_expf_ws_fits(W, g0, 1));
+static bool fused_expf_ws(const ScrfKnobs& kn, const ScrfLayout& lay, uint32_t W, int f32, int g0) {
+  return kn.expf_ws && !f32 && (fused_expf_ws_fits(W, g0, 0) || fused_expf_ws_fits(W, g0, 1));
 }
 
 // f32: FAST32 runs the single-role count kernel only
-int fused_supported(const ScrfLayout& lay, uint32_t W, int f32) {
+int fused_supported(const ScrfKnobs& kn, const ScrfLayout& lay, uint32_t W, int f32) {
   if (lay.D < 2 || lay.D > 40 || W < 1) return 0;
-  if (!fused_expf_plain_fits(lay, W) && !fused_expf_ws(lay, W, f32, 0)) return 0;
+  if (!fused_expf_plain_fits(lay, W) && !fused_expf_ws(kn, lay, W, f32, 0)) return 0;
   // wide streams with many labels (config 5: W = 123, L = 200, D = 40) are served better by the general path: every
   // 48-output block of the fused kernels repeats the window scans, the D = 40 forms spill, k_post_z walks four label
   // groups (measured 253.6 ms fused against 206.4 ms materialised per 128 utterances).  The z-blocked count kernel is for
@@ -2445,33 +2438,32 @@ int fused_supported(const ScrfLayout& lay, uint32_t W, int f32) {
 // SCRF_PREC_FASTLIN needs the wave-specialised count kernel (the only one without the avg group); other shapes run the
 // FAST kernels (the reference's float average) under that precision.  (L > 64: k_post_z keeps one Z_avg ring per
 // 64-output group, which its LDS no longer holds two of per SIMD -- left to FAST.)
-int fused_la_supported(const ScrfLayout& lay, uint32_t W) {
-  return fused_supported(lay, W, 0) && lay.L <= 64 && fused_expf_ws(lay, W, 0, 1);
+int fused_la_supported(const ScrfKnobs& kn, const ScrfLayout& lay, uint32_t W) {
+  return fused_supported(kn, lay, W, 0) && lay.L <= 64 && fused_expf_ws(kn, lay, W, 0, 1);
 }
 // layout of the count slabs: {dense columns, first dense group, separate duration slab?}, the tile list and its height
-ScrfFusedExpfPlan fused_expf_plan(const ScrfLayout& lay, uint32_t W, int f32, int la) {
+ScrfFusedExpfPlan fused_expf_plan(const ScrfKnobs& kn, const ScrfLayout& lay, uint32_t W, int f32, int la) {
   ScrfFusedExpfPlan p;
-  p.ws = fused_expf_ws(lay, W, f32, la ? 1 : 0) ? 1 : 0;
+  p.ws = fused_expf_ws(kn, lay, W, f32, la ? 1 : 0) ? 1 : 0;
   p.g0 = (p.ws && la) ? 1 : 0;
   p.ncol = p.ws ? (3 - p.g0) * W : 3 * W + lay.D + (lay.use_sb ? 1 : 0);
   p.ndur = p.ws ? lay.D + (lay.use_sb ? 1 : 0) : 0;
-  p.rows = p.ws ? fused_expf_ws_rows(W, p.g0) : FE_ROWS;
+  p.rows = p.ws ? fused_expf_ws_rows(kn, W, p.g0) : FE_ROWS;
   p.tile_list = p.rows == FE_ROWS ? 1 : 2;
   p.frames = lay.D >= p.rows ? 1u : p.rows / lay.D;
   p.nz = (p.ws && fused_expf_ws_zb(W, p.g0)) ? (uint32_t)(3 - p.g0) : 1u;
   return p;
 }
-uint32_t fused_expf_blocks(const ScrfLayout& lay, uint32_t W, int f32, uint64_t n_tiles, int la) {
-  static const uint32_t nb = getenv("SCRF_EXPF_BLOCKS") ? (uint32_t)atoi(getenv("SCRF_EXPF_BLOCKS")) : 512u;  // experiment knob (<= 512)
-  const uint32_t cap = fused_expf_ws(lay, W, f32, la ? 1 : 0) ? std::min(nb, 256u) : nb;   // one workgroup per CU there
+uint32_t fused_expf_blocks(const ScrfKnobs& kn, const ScrfLayout& lay, uint32_t W, int f32, uint64_t n_tiles, int la) {
+  const uint32_t cap = fused_expf_ws(kn, lay, W, f32, la ? 1 : 0) ? std::min(kn.expf_blocks, 256u) : kn.expf_blocks;   // one workgroup per CU there
   return (uint32_t)(n_tiles < cap ? n_tiles : cap);
 }
 
 template <int NT, int DMAX, int NKS, int G0, int ROWS, int DMA>
-static void launch_expf_ws_d(hipStream_t st, const ScrfFusedArgs& fa, const ScrfLayout& lay, const double* R, uint64_t n_tiles,
+static void launch_expf_ws_d(hipStream_t st, const ScrfKnobs& kn, const ScrfFusedArgs& fa, const ScrfLayout& lay, const double* R, uint64_t n_tiles,
                              uint32_t n_ct, double* slab, double* dslab) {
   const int zb = fused_expf_ws_zb(fa.W, G0);
-  dim3 grid(fused_expf_blocks(lay, fa.W, 0, n_tiles, G0), (lay.L + 47) / 48, zb ? 3 - G0 : 1);
+  dim3 grid(fused_expf_blocks(kn, lay, fa.W, 0, n_tiles, G0), (lay.L + 47) / 48, zb ? 3 - G0 : 1);
   const size_t smw = fused_expf_ws_smem_rows(fa.W, G0, zb, ROWS);
   if (NT <= 4) {   // the narrow forms leave room for the side stream's kernels
     hipFuncSetAttribute((const void*)k_expf_fused_ws_n<NT, DMAX, NKS, G0, ROWS, DMA>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smw);
@@ -2482,23 +2474,23 @@ static void launch_expf_ws_d(hipStream_t st, const ScrfFusedArgs& fa, const Scrf
   hipLaunchKernelGGL((k_expf_fused_ws<NT, DMAX, NKS, G0, ROWS, DMA>), grid, dim3(FW_NT), smw, st, fa, lay, R, lay.L, n_tiles, n_ct, slab, dslab);
 }
 template <int NT, int DMAX, int NKS, int G0, int ROWS>
-static void launch_expf_ws_t(hipStream_t st, const ScrfFusedArgs& fa, const ScrfLayout& lay, const double* R, uint64_t n_tiles,
+static void launch_expf_ws_t(hipStream_t st, const ScrfKnobs& kn, const ScrfFusedArgs& fa, const ScrfLayout& lay, const double* R, uint64_t n_tiles,
                              uint32_t n_ct, double* slab, double* dslab) {
-  if (fused_expf_dma(lay.L) && ((uintptr_t)R & 15) == 0) launch_expf_ws_d<NT, DMAX, NKS, G0, ROWS, 1>(st, fa, lay, R, n_tiles, n_ct, slab, dslab);
-  else launch_expf_ws_d<NT, DMAX, NKS, G0, ROWS, 0>(st, fa, lay, R, n_tiles, n_ct, slab, dslab);
+  if (fused_expf_dma(kn, lay.L) && ((uintptr_t)R & 15) == 0) launch_expf_ws_d<NT, DMAX, NKS, G0, ROWS, 1>(st, kn, fa, lay, R, n_tiles, n_ct, slab, dslab);
+  else launch_expf_ws_d<NT, DMAX, NKS, G0, ROWS, 0>(st, kn, fa, lay, R, n_tiles, n_ct, slab, dslab);
 }
 
 template <int NT, int DMAX, int F32, int NKS>
-static void launch_expf_fused_t(hipStream_t st, const ScrfFusedArgs& fa, const ScrfLayout& lay, const double* R,
+static void launch_expf_fused_t(hipStream_t st, const ScrfKnobs& kn, const ScrfFusedArgs& fa, const ScrfLayout& lay, const double* R,
                                 uint64_t n_tiles, uint32_t n_ct, size_t sm, double* slab) {
-  dim3 grid(fused_expf_blocks(lay, fa.W, F32, n_tiles, 0), (lay.L + 47) / 48);
+  dim3 grid(fused_expf_blocks(kn, lay, fa.W, F32, n_tiles, 0), (lay.L + 47) / 48);
   hipFuncSetAttribute((const void*)k_expf_fused<NT, DMAX, F32, NKS>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sm);
   hipLaunchKernelGGL((k_expf_fused<NT, DMAX, F32, NKS>), grid, dim3(FE_NT), sm, st, fa, lay, R, lay.L, n_tiles, n_ct,
                      fused_expf_nfmax(lay.D), slab);
 }
 
 // slab: [fused_expf_blocks(n_tiles)][L][plan.ncol]; dslab (plan.ndur > 0): [blocks][L][D + bias]
-void launch_expf_fused(hipStream_t st, const ScrfFusedArgs& fa, const ScrfLayout& lay, const double* R,
+void launch_expf_fused(hipStream_t st, const ScrfKnobs& kn, const ScrfFusedArgs& fa, const ScrfLayout& lay, const double* R,
                        uint64_t n_tiles, double* slab, double* dslab, int f32, int la) {
   if (n_tiles == 0) return;
   const uint32_t nks = fused_expf_nks(lay.D);
@@ -2514,7 +2506,7 @@ void launch_expf_fused(hipStream_t st, const ScrfFusedArgs& fa, const ScrfLayout
       else FE_GO3(N, 40, 19);                                      \
     }                                                              \
   } while (0)
-  const ScrfFusedExpfPlan plan = fused_expf_plan(lay, fa.W, f32, la);
+  const ScrfFusedExpfPlan plan = fused_expf_plan(kn, lay, fa.W, f32, la);
   if (plan.ws) {
     uint32_t n_ct;
     fused_expf_ws_xs(fa.W, plan.g0, plan.nz > 1 ? 1 : 0, &n_ct);
@@ -2523,8 +2515,8 @@ void launch_expf_fused(hipStream_t st, const ScrfFusedArgs& fa, const ScrfLayout
       const uint32_t used = plan.frames * lay.D;
 #define FB_GO(DM)                                                                                                 \
   do {                                                                                                            \
-    if (used <= 84) launch_expf_ws_t<4, DM, 21, 1, FW_ROWS_BIG>(st, fa, lay, R, n_tiles, n_ct, slab, dslab);      \
-    else launch_expf_ws_t<4, DM, 25, 1, FW_ROWS_BIG>(st, fa, lay, R, n_tiles, n_ct, slab, dslab);                 \
+    if (used <= 84) launch_expf_ws_t<4, DM, 21, 1, FW_ROWS_BIG>(st, kn, fa, lay, R, n_tiles, n_ct, slab, dslab);  \
+    else launch_expf_ws_t<4, DM, 25, 1, FW_ROWS_BIG>(st, kn, fa, lay, R, n_tiles, n_ct, slab, dslab);             \
   } while (0)
       if (lay.D <= 12) FB_GO(12);
       else if (lay.D <= 25) FB_GO(25);
@@ -2534,8 +2526,8 @@ void launch_expf_fused(hipStream_t st, const ScrfFusedArgs& fa, const ScrfLayout
     }
 #define FE_GO3(N, DM, KS)                                                                                   \
   do {                                                                                                      \
-    if (plan.g0) launch_expf_ws_t<N, DM, KS, 1, FE_ROWS>(st, fa, lay, R, n_tiles, n_ct, slab, dslab);       \
-    else launch_expf_ws_t<N, DM, KS, 0, FE_ROWS>(st, fa, lay, R, n_tiles, n_ct, slab, dslab);               \
+    if (plan.g0) launch_expf_ws_t<N, DM, KS, 1, FE_ROWS>(st, kn, fa, lay, R, n_tiles, n_ct, slab, dslab);   \
+    else launch_expf_ws_t<N, DM, KS, 0, FE_ROWS>(st, kn, fa, lay, R, n_tiles, n_ct, slab, dslab);           \
   } while (0)
     // slots per consumer wavefront = ceil(3 n_ct / 4)
     if (n_ct <= 5) FE_GO(4);
@@ -2550,8 +2542,8 @@ void launch_expf_fused(hipStream_t st, const ScrfFusedArgs& fa, const ScrfLayout
   const size_t sm = fused_expf_smem(lay, fa.W);
 #define FE_GO3(N, DM, KS)                                                                             \
   do {                                                                                                \
-    if (f32) launch_expf_fused_t<N, DM, 1, KS>(st, fa, lay, R, n_tiles, n_ct, sm, slab);              \
-    else launch_expf_fused_t<N, DM, 0, KS>(st, fa, lay, R, n_tiles, n_ct, sm, slab);                  \
+    if (f32) launch_expf_fused_t<N, DM, 1, KS>(st, kn, fa, lay, R, n_tiles, n_ct, sm, slab);          \
+    else launch_expf_fused_t<N, DM, 0, KS>(st, kn, fa, lay, R, n_tiles, n_ct, sm, slab);              \
   } while (0)
   if (n_ct <= 5) FE_GO(4);
   else if (n_ct <= 9) FE_GO(7);

@@ -3,6 +3,7 @@
 #define SCRF_KERNELS_H_
 
 #include "scrf_common.h"
+#include "scrf_knobs.h"
 
 #include <vector>
 
@@ -41,7 +42,7 @@ void launch_add(hipStream_t st, double* y, const double* x, uint32_t n);
 size_t fb_segtrans_smem_bytes(const ScrfLayout& lay, int NT);
 void launch_zero_initial_rows(hipStream_t st, ScrfBatchView bv, const uint32_t* frame_u, uint32_t u0, uint64_t n_frames,
                               uint32_t D, uint32_t L, double* M2);
-void launch_fb_segtrans(hipStream_t st, const ScrfLayout& lay, ScrfBatchView bv, uint32_t u0, uint32_t n_utts,
+void launch_fb_segtrans(hipStream_t st, const ScrfKnobs& kn, const ScrfLayout& lay, ScrfBatchView bv, uint32_t u0, uint32_t n_utts,
                         const uint32_t* prev_lab, const double* S, const double* M2, double* AD, double* alpha_g,
                         double* beta_g, double* XI2, double* numer, double* zx, int* status, int write_post);
 
@@ -53,10 +54,10 @@ void launch_viterbi_segtrans(hipStream_t st, const ScrfLayout& lay, ScrfBatchVie
                              uint32_t* out_n, float* out_cost);
 
 // scrf_mfma.hip: fp64 MFMA contractions (FAST training precision)
-void launch_scores_mfma(hipStream_t st, const float* X, uint32_t F, const uint64_t* xrow, uint64_t n_rows,
+void launch_scores_mfma(hipStream_t st, const ScrfKnobs& kn, const float* X, uint32_t F, const uint64_t* xrow, uint64_t n_rows,
                         const double* lambda, const ScrfLayout& lay, const ScrfGemmSpec& sp, uint32_t n_out,
                         double* out, int f32 = 0);
-void launch_expf_mfma(hipStream_t st, const double* A, uint32_t n_out, const float* X, uint32_t F,
+void launch_expf_mfma(hipStream_t st, const ScrfKnobs& kn, const double* A, uint32_t n_out, const float* X, uint32_t F,
                       const uint64_t* xrow, uint64_t n_rows, const ScrfLayout& lay, const ScrfGemmSpec& sp,
                       uint64_t rows_per_chunk, uint32_t n_chunks, double* slab, int f32 = 0);
 // workgroups launch_expf_mfma starts per row chunk when it takes the 8-wavefront form (one workgroup per CU), else 0:
@@ -66,7 +67,7 @@ uint32_t expf_mfma_wide_tiles(uint32_t n_out, uint32_t nfun, int f32);
 // scrf_dp.hip: wavefront-per-utterance DP and the parallel posterior kernels
 int dp_wave_supported(const ScrfLayout& lay);
 int atb_supported(const ScrfLayout& lay);
-void launch_exp_m(hipStream_t st, const double* M, uint32_t L, uint64_t n_mat, double* E, double* ET,
+void launch_exp_m(hipStream_t st, const ScrfKnobs& kn, const double* M, uint32_t L, uint64_t n_mat, double* E, double* ET,
                   double* mshift);
 void launch_dp_wave(hipStream_t st, const ScrfLayout& lay, ScrfBatchView bv, uint32_t u0, uint32_t n_utts,
                     const double* S, const double* E, const double* ET, const double* mshift, int m_per_frame,
@@ -94,7 +95,7 @@ int dplin_supported(const ScrfLayout& lay);
 void launch_true_scores(hipStream_t st, const ScrfLayout& lay, ScrfBatchView bv, const uint32_t* frame_u, uint32_t u0,
                         uint64_t n_frames, const double* S, double* s_true);
 void launch_exp_rows(hipStream_t st, double* S, uint64_t n_rows, uint32_t L, double* smax);
-void launch_dp_lin(hipStream_t st, const ScrfLayout& lay, ScrfBatchView bv, uint32_t u0, uint32_t n_utts,
+void launch_dp_lin(hipStream_t st, const ScrfKnobs& kn, const ScrfLayout& lay, ScrfBatchView bv, uint32_t u0, uint32_t n_utts,
                    const double* ES, const double* smax, const double* E, const double* ET, const double* mshift,
                    int m_per_frame, const ScrfDpLin& o, double* zx, int* status);
 void launch_post_lin(hipStream_t st, const ScrfLayout& lay, ScrfBatchView bv, const uint32_t* frame_u, uint32_t u0,
@@ -138,17 +139,17 @@ void launch_gamma_log(hipStream_t st, const ScrfLayout& lay, uint32_t T, const d
 uint32_t fused_scores_tb(uint32_t W, uint32_t D);   // whole frames per score tile (0: shape not supported)
 #define SCRF_FUSED_ROWS_EXPF 76
 uint32_t fused_expf_frames(uint32_t D);            // whole frames per expected-count tile (<= 76 rows)
-int fused_supported(const ScrfLayout& lay, uint32_t W, int f32 = 0);
+int fused_supported(const ScrfKnobs& kn, const ScrfLayout& lay, uint32_t W, int f32 = 0);
 // SCRF_PREC_FASTLIN (`la`): the window average leaves both dense contractions (prefix sums of a sixth per-frame
 // projection / a sixth group of Z); shapes this returns 0 for run the FAST kernels under that precision
-int fused_la_supported(const ScrfLayout& lay, uint32_t W);
+int fused_la_supported(const ScrfKnobs& kn, const ScrfLayout& lay, uint32_t W);
 // slabs of the fused expected-count kernel: slab [blocks][L][ncol] (dense groups from g0: 0 avg, 1 max) and, when
 // ndur > 0, a separate duration slab [blocks][L][ndur] (one-hot duration counts + bias; wave-specialised kernel)
 // rows / frames: height of the row tiles the kernel walks (whole frames); tile_list: which of the batch's tile lists
 // describes them (1: <= 76 rows, 2: <= 100 rows, built only for batches of an SCRF_PREC_FASTLIN engine)
 struct ScrfFusedExpfPlan { int ws; int g0; uint32_t ncol; uint32_t ndur; uint32_t rows; uint32_t frames; int tile_list; uint32_t nz; };   // nz: workgroup columns of the launch (one dense statistic each when > 1)
-ScrfFusedExpfPlan fused_expf_plan(const ScrfLayout& lay, uint32_t W, int f32, int la);
-uint32_t fused_expf_blocks(const ScrfLayout& lay, uint32_t W, int f32, uint64_t n_tiles, int la);   // workgroups (= slabs) of launch_expf_fused, <= 512
+ScrfFusedExpfPlan fused_expf_plan(const ScrfKnobs& kn, const ScrfLayout& lay, uint32_t W, int f32, int la);
+uint32_t fused_expf_blocks(const ScrfKnobs& kn, const ScrfLayout& lay, uint32_t W, int f32, uint64_t n_tiles, int la);   // workgroups (= slabs) of launch_expf_fused, <= 512
 void launch_scores_fused(hipStream_t st, const ScrfFusedArgs& fa, const ScrfLayout& lay, const double* lambda,
                          const double* P, uint64_t n_tiles, double* S, int f32, double* smax = nullptr,
                          double* s_true = nullptr, const uint32_t* labels = nullptr, int la = 0);
@@ -159,7 +160,7 @@ void launch_dur_table(hipStream_t st, const ScrfLayout& lay, uint32_t W, const d
 void launch_avg_prefix(hipStream_t st, ScrfBatchView bv, uint32_t u0, uint32_t n_utts, uint32_t L, double* P);
 // k_viterbi on float arc weights with one wavefront per utterance (fast decode; L <= 64, constant M)
 int viterbi_fast_supported(const ScrfLayout& lay);
-void launch_viterbi_fast(hipStream_t st, const ScrfLayout& lay, ScrfBatchView bv, uint32_t u0, uint32_t n_utts, const float* Wn,
+void launch_viterbi_fast(hipStream_t st, const ScrfKnobs& kn, const ScrfLayout& lay, ScrfBatchView bv, uint32_t u0, uint32_t n_utts, const float* Wn,
                          const double* M, uint16_t* bp_b, uint16_t* bp_e, uint32_t* out_labels, uint32_t* out_n, float* out_cost);
 // decode mode: float arc weights + the list of entries to recompute (ScrfDecodeOut)
 void launch_scores_fused_decode(hipStream_t st, const ScrfFusedArgs& fa, const ScrfLayout& lay, const double* lambda,
@@ -182,11 +183,11 @@ void launch_lin_z5(hipStream_t st, const ScrfLayout& lay, ScrfBatchView bv, uint
                    const double* R, double* Z, double* dslab);
 void launch_add_p_exp(hipStream_t st, const ScrfLayout& lay, ScrfBatchView bv, const uint32_t* frame_u, uint32_t u0, uint64_t n_frames,
                       const double* P, double* S, double* smax, double* s_true);
-void launch_post_z(hipStream_t st, const ScrfLayout& lay, ScrfBatchView bv, uint32_t u0, uint32_t n_utts,
+void launch_post_z(hipStream_t st, const ScrfKnobs& kn, const ScrfLayout& lay, ScrfBatchView bv, uint32_t u0, uint32_t n_utts,
                    const uint32_t* next_lab, const double* s_true, const double* M, int m_per_frame, double* ES,
                    const double* smax, const ScrfDpLin& o, const double* zx, double* numer_f, int* status, double* Z,
                    double* mass_s, int la = 0, uint32_t t_max = 0, uint64_t n_frames = 0);
-void launch_expf_fused(hipStream_t st, const ScrfFusedArgs& fa, const ScrfLayout& lay, const double* R,
+void launch_expf_fused(hipStream_t st, const ScrfKnobs& kn, const ScrfFusedArgs& fa, const ScrfLayout& lay, const double* R,
                        uint64_t n_tiles, double* slab, double* dslab, int f32, int la);
 
 // ---- STDSEG (scrf_stdseg.hip): lay is the layout over FULL labels (lay.L = nLabs), La = nActualLabs

@@ -848,7 +848,7 @@ int viterbi_fast_supported(const ScrfLayout& lay) {
   return lay.L <= 64 && lay.D >= 2 && lay.D <= 40 && !lay.use_tf &&
          sizeof(float) * ((size_t)lay.L * lay.L + VF_WAVES * ((size_t)lay.L + (size_t)lay.D * lay.L)) <= 64 * 1024;
 }
-void launch_viterbi_fast(hipStream_t st, const ScrfLayout& lay, ScrfBatchView bv, uint32_t u0, uint32_t n_utts, const float* Wn,
+void launch_viterbi_fast(hipStream_t st, const ScrfKnobs& kn, const ScrfLayout& lay, ScrfBatchView bv, uint32_t u0, uint32_t n_utts, const float* Wn,
                          const double* M, uint16_t* bp_b, uint16_t* bp_e, uint32_t* out_labels, uint32_t* out_n, float* out_cost) {
   if (n_utts == 0) return;
   const size_t sm = sizeof(float) * ((size_t)lay.L * lay.L + VF_WAVES * ((size_t)lay.L + (size_t)lay.D * lay.L));
@@ -860,7 +860,7 @@ void launch_viterbi_fast(hipStream_t st, const ScrfLayout& lay, ScrfBatchView bv
                        out_cost);                                                                                              \
   } while (0)
   // register column + 16-byte reads of the previous node's costs: L a multiple of 4 (the LDS vectors stay 16-byte aligned)
-  static const bool vec_ok = !(getenv("SCRF_VITERBI_VEC") && atoi(getenv("SCRF_VITERBI_VEC")) == 0);
+  const bool vec_ok = kn.viterbi_vec;
 #define VF_GO(N)                                                     \
   do {                                                               \
     if (vec_ok && lay.L % 4 == 0 && lay.L <= 48) VF_GO2(N, 48);      \

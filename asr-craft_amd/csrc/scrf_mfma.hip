@@ -341,14 +341,13 @@ __global__ __launch_bounds__(768) void k_scores_mfma_ws(const float* __restrict_
 }
 
 template <int F32>
-static void launch_scores_mfma_f(hipStream_t st, const float* X, uint32_t F, const uint64_t* xrow, uint64_t n_rows,
+static void launch_scores_mfma_f(hipStream_t st, const ScrfKnobs& kn, const float* X, uint32_t F, const uint64_t* xrow, uint64_t n_rows,
                                  const double* lambda, const ScrfLayout& lay, const ScrfGemmSpec& sp, uint32_t n_out, double* out) {
   const uint32_t gx = (uint32_t)((n_rows + SM_ROWS - 1) / SM_ROWS);
   uint32_t o_base = 0;
-  static const bool ws_off = getenv("SCRF_SCORES_MFMA_WS") && atoi(getenv("SCRF_SCORES_MFMA_WS")) == 0;   // A/B knob
-  // (from 192 features on: with only a few 32-feature chunks the role split is all prologue -- the 40-feature per-window
+  // SCRF_SCORES_MFMA_WS=0 for A/B runs (from 192 features on: with only a few 32-feature chunks the role split is all prologue -- the 40-feature per-window
   // transition scores of STDSEG_NO_DUR: 5.8 ms single-role, 6.1 split)
-  if (!F32 && !ws_off && n_out >= SW_NO && sp.nfe >= 192) {
+  if (!F32 && kn.scores_mfma_ws && n_out >= SW_NO && sp.nfe >= 192) {
     // the wave-specialised form: 16 T outputs as a tiles of 96 and b tiles of 112 (T = 6a + 7b, fewest masked outputs); when
     // the count does not split that way, the whole 96-output tiles go here and the rest to the single-role kernels below
     const uint32_t T = (n_out + 15) / 16;
@@ -378,12 +377,12 @@ static void launch_scores_mfma_f(hipStream_t st, const float* X, uint32_t F, con
   else if (rem > 0)
     hipLaunchKernelGGL((k_scores_mfma<F32, 1>), dim3(gx), dim3(256), 0, st, X, F, xrow, n_rows, lambda, lay, sp, n_out, o_base + n_full * SM_NO, 1u, out);
 }
-void launch_scores_mfma(hipStream_t st, const float* X, uint32_t F, const uint64_t* xrow, uint64_t n_rows,
+void launch_scores_mfma(hipStream_t st, const ScrfKnobs& kn, const float* X, uint32_t F, const uint64_t* xrow, uint64_t n_rows,
                         const double* lambda, const ScrfLayout& lay, const ScrfGemmSpec& sp, uint32_t n_out,
                         double* out, int f32) {
   if (n_rows == 0 || n_out == 0) return;
-  if (f32) launch_scores_mfma_f<1>(st, X, F, xrow, n_rows, lambda, lay, sp, n_out, out);
-  else launch_scores_mfma_f<0>(st, X, F, xrow, n_rows, lambda, lay, sp, n_out, out);
+  if (f32) launch_scores_mfma_f<1>(st, kn, X, F, xrow, n_rows, lambda, lay, sp, n_out, out);
+  else launch_scores_mfma_f<0>(st, kn, X, F, xrow, n_rows, lambda, lay, sp, n_out, out);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -766,21 +765,19 @@ __global__ __launch_bounds__(768) void k_expf_mfma_ws(const double* __restrict__
 }
 
 template <int HAS_XROW, int NW, int KC, int F32, int MT>
-static void launch_expf_mfma_one(hipStream_t st, dim3 grid, size_t sm, const double* A, uint32_t n_out, const float* X, uint32_t F,
+static void launch_expf_mfma_one(hipStream_t st, const ScrfKnobs& kn, dim3 grid, size_t sm, const double* A, uint32_t n_out, const float* X, uint32_t F,
                                  const uint64_t* xrow, uint64_t n_rows, const ScrfLayout& lay, const ScrfGemmSpec& sp,
                                  uint64_t rows_per_chunk, double* slab, uint32_t o_base, uint32_t o_step = 16 * EM_MTW(F32, NW)) {
   constexpr int DB = NW == 8 ? 1 : 0;   // the 8-wave workgroup has its CU to itself: room for a second image pair
-  static const bool db_off = getenv("SCRF_EXPF_DB") && atoi(getenv("SCRF_EXPF_DB")) == 0;   // A/B knob
   constexpr int MTW = EM_MTW(F32, NW);
-  static const bool ws_off = getenv("SCRF_EXPF_MFMA_WS") && atoi(getenv("SCRF_EXPF_MFMA_WS")) == 0;   // A/B knob
-  if (NW == 8 && !F32 && KC == EW_KC && MTW * 16 == EW_NO && !ws_off) {
+  if (NW == 8 && !F32 && KC == EW_KC && MTW * 16 == EW_NO && kn.expf_mfma_ws) {
     constexpr int MTC = MT > 4 ? 4 : MT;
     hipFuncSetAttribute((const void*)k_expf_mfma_ws<HAS_XROW, MTC>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(2 * EW_IMG));
     hipLaunchKernelGGL((k_expf_mfma_ws<HAS_XROW, MTC>), dim3(grid.x * grid.y * grid.z), dim3(768), 2 * EW_IMG, st, A, n_out, X, F, xrow, n_rows, lay, sp,
                        rows_per_chunk, slab, o_base, grid.x, grid.y, o_step);
     return;
   }
-  if (DB && !db_off) {
+  if (DB && kn.expf_db) {
     hipFuncSetAttribute((const void*)k_expf_mfma<HAS_XROW, NW, KC, F32, 0, MT, DB, MTW>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(2 * sm));
     hipLaunchKernelGGL((k_expf_mfma<HAS_XROW, NW, KC, F32, 0, MT, DB, MTW>), dim3(grid.x * grid.y * grid.z), dim3(64 * NW), 2 * sm, st, A, n_out, X, F, xrow,
                        n_rows, lay, sp, rows_per_chunk, slab, o_base, grid.x, grid.y, o_step);
@@ -793,7 +790,7 @@ static void launch_expf_mfma_one(hipStream_t st, dim3 grid, size_t sm, const dou
 // (a mixed tiling of the outputs -- 200 = 64 + 3 x 48 instead of 3 x 64 + a thin 8-output launch -- was measured at config 5:
 // 81.8 against 80.0 ms; the thin launch costs less than the thirteenth M-tile)
 template <int HAS_XROW, int NW, int KC, int F32>
-static void launch_expf_mfma_x(hipStream_t st, const double* A, uint32_t n_out, const float* X, uint32_t F,
+static void launch_expf_mfma_x(hipStream_t st, const ScrfKnobs& kn, const double* A, uint32_t n_out, const float* X, uint32_t F,
                                const uint64_t* xrow, uint64_t n_rows, const ScrfLayout& lay, const ScrfGemmSpec& sp,
                                uint64_t rows_per_chunk, uint32_t n_chunks, double* slab) {
   const uint32_t nfun = sp.nfun();
@@ -803,23 +800,23 @@ static void launch_expf_mfma_x(hipStream_t st, const double* A, uint32_t n_out, 
   const size_t sm = sizeof(double) * KC * em_rss((int)NO) + sizeof(float) * KC * (48 * NW + 16);
   const uint32_t n_full = n_out / NO, rem = n_out % NO;
   if (n_full)
-    launch_expf_mfma_one<HAS_XROW, NW, KC, F32, MTW>(st, dim3(gx, n_full, n_chunks), sm, A, n_out, X, F, xrow, n_rows, lay, sp, rows_per_chunk, slab, 0u);
+    launch_expf_mfma_one<HAS_XROW, NW, KC, F32, MTW>(st, kn, dim3(gx, n_full, n_chunks), sm, A, n_out, X, F, xrow, n_rows, lay, sp, rows_per_chunk, slab, 0u);
   // the outputs past the last full tile: workgroups that carry only the M-tiles holding outputs
   if (MTW > 3 && rem > 48)
-    launch_expf_mfma_one<HAS_XROW, NW, KC, F32, MTW>(st, dim3(gx, 1, n_chunks), sm, A, n_out, X, F, xrow, n_rows, lay, sp, rows_per_chunk, slab, n_full * NO);
+    launch_expf_mfma_one<HAS_XROW, NW, KC, F32, MTW>(st, kn, dim3(gx, 1, n_chunks), sm, A, n_out, X, F, xrow, n_rows, lay, sp, rows_per_chunk, slab, n_full * NO);
   else if (rem > 32)
-    launch_expf_mfma_one<HAS_XROW, NW, KC, F32, 3>(st, dim3(gx, 1, n_chunks), sm, A, n_out, X, F, xrow, n_rows, lay, sp, rows_per_chunk, slab, n_full * NO);
+    launch_expf_mfma_one<HAS_XROW, NW, KC, F32, 3>(st, kn, dim3(gx, 1, n_chunks), sm, A, n_out, X, F, xrow, n_rows, lay, sp, rows_per_chunk, slab, n_full * NO);
   else if (rem > 16)
-    launch_expf_mfma_one<HAS_XROW, NW, KC, F32, 2>(st, dim3(gx, 1, n_chunks), sm, A, n_out, X, F, xrow, n_rows, lay, sp, rows_per_chunk, slab, n_full * NO);
+    launch_expf_mfma_one<HAS_XROW, NW, KC, F32, 2>(st, kn, dim3(gx, 1, n_chunks), sm, A, n_out, X, F, xrow, n_rows, lay, sp, rows_per_chunk, slab, n_full * NO);
   else if (rem > 0)
-    launch_expf_mfma_one<HAS_XROW, NW, KC, F32, 1>(st, dim3(gx, 1, n_chunks), sm, A, n_out, X, F, xrow, n_rows, lay, sp, rows_per_chunk, slab, n_full * NO);
+    launch_expf_mfma_one<HAS_XROW, NW, KC, F32, 1>(st, kn, dim3(gx, 1, n_chunks), sm, A, n_out, X, F, xrow, n_rows, lay, sp, rows_per_chunk, slab, n_full * NO);
 }
 template <int NW, int KC, int F32>
-static void launch_expf_mfma_nw(hipStream_t st, const double* A, uint32_t n_out, const float* X, uint32_t F,
+static void launch_expf_mfma_nw(hipStream_t st, const ScrfKnobs& kn, const double* A, uint32_t n_out, const float* X, uint32_t F,
                                 const uint64_t* xrow, uint64_t n_rows, const ScrfLayout& lay, const ScrfGemmSpec& sp,
                                 uint64_t rows_per_chunk, uint32_t n_chunks, double* slab) {
-  if (xrow) launch_expf_mfma_x<1, NW, KC, F32>(st, A, n_out, X, F, xrow, n_rows, lay, sp, rows_per_chunk, n_chunks, slab);
-  else launch_expf_mfma_x<0, NW, KC, F32>(st, A, n_out, X, F, xrow, n_rows, lay, sp, rows_per_chunk, n_chunks, slab);
+  if (xrow) launch_expf_mfma_x<1, NW, KC, F32>(st, kn, A, n_out, X, F, xrow, n_rows, lay, sp, rows_per_chunk, n_chunks, slab);
+  else launch_expf_mfma_x<0, NW, KC, F32>(st, kn, A, n_out, X, F, xrow, n_rows, lay, sp, rows_per_chunk, n_chunks, slab);
 }
 
 // few feature functions (<= 48) and many outputs: 4 wavefronts share the feature tile and split 192 outputs
@@ -845,33 +842,33 @@ uint32_t expf_mfma_wide_tiles(uint32_t n_out, uint32_t nfun, int f32) {
   return gx * ((n_out + NO - 1) / NO);
 }
 
-void launch_expf_mfma(hipStream_t st, const double* A, uint32_t n_out, const float* X, uint32_t F,
+void launch_expf_mfma(hipStream_t st, const ScrfKnobs& kn, const double* A, uint32_t n_out, const float* X, uint32_t F,
                       const uint64_t* xrow, uint64_t n_rows, const ScrfLayout& lay, const ScrfGemmSpec& sp,
                       uint64_t rows_per_chunk, uint32_t n_chunks, double* slab, int f32) {
   if (n_rows == 0 || n_chunks == 0) return;
   const uint32_t nfun = sp.nfun();
   const uint32_t tiles = (nfun + 47) / 48;  // 48-column wave tiles needed
-#define EXPF_ARGS st, A, n_out, X, F, xrow, n_rows, lay, sp, rows_per_chunk, n_chunks, slab
+#define EXPF_ARGS A, n_out, X, F, xrow, n_rows, lay, sp, rows_per_chunk, n_chunks, slab
   if (tiles <= 1 && n_out >= 4 * EM_SPLIT_NO) {
-    if (f32) launch_expf_mfma_split<1>(EXPF_ARGS);
-    else launch_expf_mfma_split<0>(EXPF_ARGS);
+    if (f32) launch_expf_mfma_split<1>(st, EXPF_ARGS);
+    else launch_expf_mfma_split<0>(st, EXPF_ARGS);
     return;
   }
   if (f32) {
-    if (tiles <= 1) launch_expf_mfma_nw<1, 32, 1>(EXPF_ARGS);
-    else if (tiles <= 2) launch_expf_mfma_nw<2, 64, 1>(EXPF_ARGS);
-    else if (tiles <= 3) launch_expf_mfma_nw<3, 64, 1>(EXPF_ARGS);
-    else if (tiles <= 4) launch_expf_mfma_nw<4, 64, 1>(EXPF_ARGS);
-    else launch_expf_mfma_nw<8, 32, 1>(EXPF_ARGS);
+    if (tiles <= 1) launch_expf_mfma_nw<1, 32, 1>(st, kn, EXPF_ARGS);
+    else if (tiles <= 2) launch_expf_mfma_nw<2, 64, 1>(st, kn, EXPF_ARGS);
+    else if (tiles <= 3) launch_expf_mfma_nw<3, 64, 1>(st, kn, EXPF_ARGS);
+    else if (tiles <= 4) launch_expf_mfma_nw<4, 64, 1>(st, kn, EXPF_ARGS);
+    else launch_expf_mfma_nw<8, 32, 1>(st, kn, EXPF_ARGS);
   } else {
-    if (tiles <= 1) launch_expf_mfma_nw<1, 32, 0>(EXPF_ARGS);
-    else if (tiles <= 2) launch_expf_mfma_nw<2, 64, 0>(EXPF_ARGS);
-    else if (tiles <= 3) launch_expf_mfma_nw<3, 64, 0>(EXPF_ARGS);
-    else if (tiles <= 4) launch_expf_mfma_nw<4, 64, 0>(EXPF_ARGS);
+    if (tiles <= 1) launch_expf_mfma_nw<1, 32, 0>(st, kn, EXPF_ARGS);
+    else if (tiles <= 2) launch_expf_mfma_nw<2, 64, 0>(st, kn, EXPF_ARGS);
+    else if (tiles <= 3) launch_expf_mfma_nw<3, 64, 0>(st, kn, EXPF_ARGS);
+    else if (tiles <= 4) launch_expf_mfma_nw<4, 64, 0>(st, kn, EXPF_ARGS);
     else {
       // (64-row chunks for the 8-wave form were tried: 256 VGPRs + 336 bytes of spills)
       // (two 4-wave workgroups per CU with 64-row chunks instead: 18.1 ms against 14.4 at the TIMIT transition counts)
-      launch_expf_mfma_nw<8, 32, 0>(EXPF_ARGS);
+      launch_expf_mfma_nw<8, 32, 0>(st, kn, EXPF_ARGS);
     }
   }
 #undef EXPF_ARGS

@@ -460,7 +460,7 @@ size_t fb_segtrans_smem_bytes(const ScrfLayout& lay, int NT) {
   return sizeof(double) * ((size_t)3 * lay.D * lay.L + (size_t)2 * G * lay.L);
 }
 
-void launch_fb_segtrans(hipStream_t st, const ScrfLayout& lay, ScrfBatchView bv, uint32_t u0, uint32_t n_utts,
+void launch_fb_segtrans(hipStream_t st, const ScrfKnobs& kn, const ScrfLayout& lay, ScrfBatchView bv, uint32_t u0, uint32_t n_utts,
                         const uint32_t* prev_lab, const double* S, const double* M2, double* AD, double* alpha_g,
                         double* beta_g, double* XI2, double* numer, double* zx, int* status, int write_post) {
   if (n_utts == 0) return;
@@ -469,7 +469,7 @@ void launch_fb_segtrans(hipStream_t st, const ScrfLayout& lay, ScrfBatchView bv,
     hipFuncSetAttribute((const void*)k_fb_segtrans_w, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smw);
     // wavefronts per workgroup: 16 when every CU has at most one utterance, 8 (two workgroups per CU) beyond that
     int nw = n_utts > 256 ? FBW_WAVES / 2 : FBW_WAVES;
-    if (const char* e = getenv("SCRF_FBW_WAVES")) { const int v = atoi(e); if (v >= 1 && v <= FBW_WAVES) nw = v; }
+    if (kn.fbw_waves >= 1 && kn.fbw_waves <= FBW_WAVES) nw = kn.fbw_waves;
     hipLaunchKernelGGL(k_fb_segtrans_w, dim3(n_utts), dim3(64 * nw), smw, st, lay, bv, u0, prev_lab, S, M2, AD, alpha_g, beta_g,
                        XI2, numer, zx, status, write_post);
     return;

@@ -629,7 +629,7 @@ def test_random_shape_sweep_through_the_fused_and_wavefront_kernels():
 
 def test_several_wavefronts_per_sweep_kernel_through_the_same_sweep():
     """k_dp_lin_mv (SCRF_DPLIN_MV=1, opt-in: four wavefronts share one sweep's ring, durations and transition rows
-    split between them) through 30 shapes of the same sweep, in its own process (the switch is read once)"""
+    split between them) through 30 shapes of the same sweep, in its own process (the switch is read at scrf_create)"""
     import subprocess, sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = dict(os.environ, SCRF_DPLIN_MV="1")

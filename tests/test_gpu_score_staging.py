@@ -1,6 +1,7 @@
 """-m gpu: the fused score kernel's staging by LDS-DMA (default: duration table, tile tables, raw frames and -- full
-output blocks of an even label count -- the P image) against staging through registers (SCRF_SCORES_DMA=0).  The knob is
-read once per process, so each setting runs tools/score_staging_cases.py once, in a child, over every shape below.
+output blocks of an even label count -- the P image) against staging through registers (SCRF_SCORES_DMA=0).  Each
+setting runs tools/score_staging_cases.py once, in a child, over every shape below (the knob is read at scrf_create,
+DESIGN.md 4.16; tests/test_gpu_knobs.py runs both settings in one process).
 
 Both forms put the same values through the same instructions in the same order, so everything is compared bit for
 bit: gradient, numerators, Zx, and the labels and costs of viterbi_batch (the decode form of the kernel).  The DMA form

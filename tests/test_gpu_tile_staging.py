@@ -1,6 +1,8 @@
 """-m gpu: the R tiles of the wave-specialised expected-count kernel staged by LDS-DMA (default, even label counts)
 against the register path (SCRF_EXPF_DMA=0), at both tile heights (SCRF_EXPF_BIG) and with the side stream on and off
-(SCRF_SIDE).  The knobs are read once per process, so every setting runs tools/tile_staging_cases.py in a child.
+(SCRF_SIDE).  Every setting runs tools/tile_staging_cases.py in a child: a process per setting is the plainest way to
+run a tool script under it (the knobs are read at scrf_create; tests/test_gpu_knobs.py runs two settings
+in one process).
 
 SCRF_EXPF_BLOCKS=3 makes each persistent workgroup walk many tiles: an edge tile (rows [nrows, ROWS) must read as zero)
 then lands in an LDS image a full tile used before -- launches of fewer tiles than workgroups never get there.

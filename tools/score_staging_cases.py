@@ -1,5 +1,5 @@
 """tile_staging_cases.py plus the decode side: gradients AND best paths of a list of cases under the knobs of the calling
-environment (GPU box), for comparisons between settings of knobs that are read once per process (SCRF_SCORES_DMA ...).
+environment (GPU box), for comparisons between knob settings (SCRF_SCORES_DMA ...: read at scrf_create).
 usage: python tools/score_staging_cases.py OUT.npz '<json list of {"name": .., "prec": .., "kw": {Case arguments}}>'
 OUT.npz holds <name>_p<prec>_{grad,numer,zx,mode,chunks,vchunks,vlabs,voff,vcost} for every entry (mode:
 Engine.batch_fused_mode; chunks / vchunks: chunks of the timed fb_batch / viterbi_batch, counted as launches of the score

@@ -1,5 +1,5 @@
 """Gradients of a list of cases under the knobs of the calling environment (GPU box), for comparisons between knob
-settings that are read once per process (SCRF_EXPF_DMA, SCRF_EXPF_BIG, SCRF_SIDE, SCRF_EXPF_BLOCKS ...).
+settings (SCRF_EXPF_DMA, SCRF_EXPF_BIG, SCRF_SIDE, SCRF_EXPF_BLOCKS ...: read at scrf_create).
 usage: python tools/tile_staging_cases.py OUT.npz '<json list of {"name": .., "prec": .., "kw": {Case arguments}}>'
 OUT.npz holds <name>_p<prec>_{grad,numer,zx,mode} for every entry (mode: Engine.batch_fused_mode)."""
 import json, os, sys
