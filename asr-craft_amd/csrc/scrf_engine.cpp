@@ -980,7 +980,8 @@ static uint64_t expf_rows_per_chunk(uint64_t nseg) {
 // K-chunks of the per-window transition contraction (STDSEG_NO_DUR: [N_seg][L*L] posteriors x a few feature functions):
 // one per 2048 rows while the partial-sum slabs stay within 128 MB (at least 4)
 static uint32_t segtrans_chunks(uint64_t nseg, size_t LL, uint32_t ntf) {
-  const uint64_t cap = std::max<uint64_t>(4, (128ull << 20) / (LL * ntf * sizeof(double)));
+  // (ntf = 0: neither transition features nor a transition bias -- the slabs are empty)
+  const uint64_t cap = std::max<uint64_t>(4, (128ull << 20) / (LL * std::max<uint32_t>(1, ntf) * sizeof(double)));
   return (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(cap, (nseg + 2047) / 2048));
 }
 

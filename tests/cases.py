@@ -74,17 +74,23 @@ def tie_twin_labels(lam, lay, L, K=1):
             lam[lay.state_idx[l] + nsf - 1] += 2.0
 
 
+# feature-map settings a Case takes through fmap= (orc.config and scrf_amd.make_config name them alike)
+FMAP_KEYS = frozenset(("sfs", "sfe", "tfs", "tfe", "use_state_ftrs", "use_state_bias", "use_trans_bias", "state_bias_val", "trans_bias_val"))
+
+
 class Case:
     """L labels, max duration D, raw frame width in_w, utterance lengths Ts.
     trans_ctx=None: `stdstate` map (bias-only transitions); trans_ctx=c: `stdtrans` map whose
     transition features are a second stream of boundary context (c frames each side), like the
     TIMIT demo's ftr2 stream (demo/segmental-timit-demo.cfg.in:21-24).
     family: one of FAMILIES instead of frames in [0, 1) (family_frames); lam_scale then defaults to
-    3 / (nominal max |x| * sqrt(F)), which keeps scores to a few nats, and `tied` also ties two labels (tie_twin_labels)."""
+    3 / (nominal max |x| * sqrt(F)), which keeps scores to a few nats, and `tied` also ties two labels (tie_twin_labels).
+    fmap: feature-map settings (FMAP_KEYS) that replace what the keywords above imply, in both configurations; the frames,
+    labels and the random stream of the weights do not depend on it (only the number of weights drawn does)."""
 
     def __init__(self, L, D, in_w, Ts, trans_ctx=None, seed=0, lam_scale=None, frame_model=False,
                  scratch_bytes=0, precision=0, l1_norm=False, model_type=None, trans_share=None,
-                 num_states=1, conform_labels=True, exact_avg=False, family=None):
+                 num_states=1, conform_labels=True, exact_avg=False, family=None, fmap=None):
         self.L, self.D, self.in_w, self.Ts = L, D, in_w, list(Ts)
         self.trans_ctx = trans_ctx
         self.family = family
@@ -133,6 +139,9 @@ class Case:
             kw["num_states"] = num_states
         if mt == orc.STDSEG:   # the feature map and the weight layout run over all labels: nLabs = nActualLabs * D
             kw["L"] = L * D
+        if fmap is not None:   # feature-map overrides, the same for the oracle and the engine
+            assert set(fmap) <= FMAP_KEYS, sorted(set(fmap) - FMAP_KEYS)
+            kw.update(fmap)
         self.ocfg = orc.config(**kw)
         self.olay = orc.Layout(self.ocfg)
         self.gcfg = scrf_amd.make_config(scratch_bytes=scratch_bytes, precision=precision, **kw)

@@ -142,12 +142,13 @@ def rescaled(c, k):
     return r, raw
 
 
-def predicted_screen_count(c, factor):
+def predicted_screen_count(c, factor, with_bias_value=True):
     """how many float arc weights the fast-decode screen of k_scores_fused sends to k_decode_fixup under
     SCRF_DECODE_BOUND_SCALE=factor, from the oracle's scores: w = float(-S) is listed when float(-S -+ B) != w with
     B = factor * 1.01 * 2^-53 * (F + 1 + 3 W + 8) * xm(u) * |state block of o|_1 and
     xm(u) = nextafter(max(1, |state bias value|, max|x| of utterance u)).  (The kernel's S differs from the oracle's by
-    some 1e-15, B is 1e-11 and more: a prediction to within a few entries, not a bit-exact one.)"""
+    some 1e-15, B is 1e-11 and more: a prediction to within a few entries, not a bit-exact one.)  with_bias_value=False: what
+    a screen that left the bias value out of xm would list."""
     lay, W = c.olay, c.in_w
     nsf = lay.num_state_funcs
     w1 = np.array([np.abs(c.lam[lay.state_idx[l]:lay.state_idx[l] + nsf]).sum() for l in range(c.L)])
@@ -155,7 +156,7 @@ def predicted_screen_count(c, factor):
     n = 0
     for u, T in enumerate(c.Ts):
         S, M = orc.seg_scores(c.ocfg, c.olay, c.lam, c.windows(u), T)
-        xm = np.nextafter(np.float32(max(1.0, np.abs(c.frames[u]).max())), np.float32(np.inf))
+        xm = np.nextafter(np.float32(max(1.0, abs(c.ocfg.state_bias_val) if with_bias_value else 1.0, np.abs(c.frames[u]).max())), np.float32(np.inf))
         v = -S
         B = float(xm) * scale * w1[None, :]
         w = v.astype(np.float32)

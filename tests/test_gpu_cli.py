@@ -89,6 +89,50 @@ def test_crftrain_then_fstdecode_on_bundled_fixture(tmp_path, threads, bunch, ad
         assert list(got[got[:, 0] == u][:, 2]) == list(ol)
 
 
+@pytest.mark.parametrize("use_state_bias", [1, 0])
+def test_crftrain_then_fstdecode_under_other_feature_map_settings(tmp_path, use_state_bias):
+    """the run above (one thread, bunch 3, AdaGrad) with the feature map's flags off their defaults: bias values 2 and 0.5,
+    state columns 1 .. 4 of the 6, and once without the state bias -- against the same oracle restatement under the matching
+    configuration; the FEATURES count is the oracle layout's"""
+    out = str(tmp_path / "weights.out")
+    eta, epochs, bunch = 0.5, 2, 3
+    fmap = ["crf_state_bias_value=2", "crf_trans_bias_value=0.5", "crf_stateftr_start=1", "crf_stateftr_end=4",
+            "crf_use_state_bias=%d" % use_state_bias]
+    cmd = [os.path.join(BIN, "CRFTrain")] + _common_flags() + fmap + [
+        "hardtarget_file=" + os.path.join(G, "crftrain_test.lab.ascii"), "out_weight_file=" + out,
+        "crf_epochs=%d" % epochs, "crf_lr=0.1", "crf_bunch_size=%d" % bunch, "threads=1",
+        "crf_use_adagrad=1", "crf_adagrad_eta=%g" % eta, "crf_utt_rpt=1", "crf_train_order=seq"]
+    r = subprocess.run(cmd, capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, r.stdout + r.stderr
+    utts = _fixture()
+    cfg = orc.config(model_type=orc.STDFRAME, L=48, D=1, F=6, sfs=1, sfe=4, use_state_bias=bool(use_state_bias),
+                     state_bias_val=2.0, trans_bias_val=0.5)
+    lay = orc.Layout(cfg)
+    assert lay.num_state_funcs == 4 + use_state_bias and lay.num_trans_funcs == 1
+    assert "FEATURES: %d" % lay.lambda_len in r.stdout
+    w = np.loadtxt(out)
+    lam = np.zeros(lay.lambda_len); acc = np.zeros_like(lam); gsa = np.zeros_like(lam)
+    for _ in range(epochs):
+        sg = np.zeros((1, lay.lambda_len))      # bunch 3 = the 3 utterances: one step per epoch
+        for X, lab in utts:
+            rc, _, _, _ = orc.frame_build_gradient(cfg, lay, lam, X, lab, X.shape[0], grad=sg[0])
+            assert rc == 0
+        orc.sgd_step(lam, acc, gsa, orc.minibatch_reduce(sg, [1]), eta, True, 1e-12)
+    ref = np.array([float("%g" % v) for v in lam])  # the weight file keeps 6 significant digits
+    np.testing.assert_allclose(w, ref, rtol=2e-5, atol=1e-12)
+
+    dec = str(tmp_path / "labels.txt")
+    r = subprocess.run([os.path.join(BIN, "CRFFstDecode")] + _common_flags() + fmap + ["weight_file=" + out, "crf_output_labelfile=" + dec],
+                       capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, r.stdout + r.stderr
+    got = np.loadtxt(dec).astype(int)
+    for u, (X, _) in enumerate(utts):
+        S, M = orc.seg_scores(cfg, lay, w, X, X.shape[0])
+        arcs, ns, fin = orc.frame_lattice_arcs(cfg, S, M, X.shape[0])
+        ol, _ = orc.best_path(arcs, ns, fin)
+        assert list(got[got[:, 0] == u][:, 2]) == list(ol)
+
+
 def test_segmental_gradbuilder_via_read_protocol(tmp_path):
     """segmental model through CRFTrain with on-GPU window synthesis: one epoch, bunch=all."""
     rng = np.random.RandomState(0)
