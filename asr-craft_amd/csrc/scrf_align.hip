@@ -21,19 +21,6 @@
 
 #define AL_STAY 0x8000u
 
-__device__ inline bool align_live(int t, int k, int T, int K, int D, int mode) {
-  if (k > t || K - 1 - k > T - 1 - t) return false;
-  if (mode == SCRF_ALIGN_ONE && ((long long)(k + 1) * D < t + 1 || (long long)(K - 1 - k) * D < T - 1 - t)) return false;
-  return true;
-}
-
-// the same for boundary(t, k), the start of position k's next segment at frame t: k segments (ONE) cover the t frames before it
-__device__ inline bool align_live_b(int t, int k, int T, int K, int D, int mode) {
-  if (k > t || K - k > T - t) return false;
-  if (mode == SCRF_ALIGN_ONE && ((long long)k * D < t || (long long)(K - k) * D < T - t)) return false;
-  return true;
-}
-
 // the path from end(T-1, K-1) back to frame 0, written first to last; returns the number of segments (0: no path).
 // Only cells with a finite cost are visited: their back pointers were written and point at finite cells.
 __device__ inline uint32_t align_backtrace(const uint16_t* __restrict__ bp, const uint32_t* __restrict__ ph, int T, int K, int L,

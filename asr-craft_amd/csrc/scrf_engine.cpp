@@ -174,6 +174,14 @@ struct scrf_engine_s {
   uint64_t al_cap_ph = 0, al_cap_u = 0;
   std::vector<uint64_t> al_bp_off;
   uint64_t n_al_calls = 0, n_al_chunks = 0, n_al_wave = 0, n_al_group = 0;   // calls; searches launched, and by which kernel
+  // scrf_transcript_batch: the transcripts go into al_ph / al_off; tr_inv holds each transcript's positions
+  // sorted by label and where each label's start (inv_pos [sum K] | inv_off [U][L + 1]); tr_cell_off is the host image
+  // chunk_layout sizes a chunk's forward / backward cells with
+  uint32_t* tr_inv = nullptr;
+  uint64_t tr_cap_inv = 0;
+  std::vector<uint64_t> tr_cell_off;
+  std::vector<uint32_t> tr_inv_h;
+  uint64_t n_tr_calls = 0, n_tr_chunks = 0, n_tr_redone = 0;   // calls; chunks swept (both passes of a redone call); calls redone
   std::string err;
   // per-kernel HIP-event times of the last timed call (scrf_kernel_timing)
   struct KTime { std::string name; double ms; uint32_t n; };
@@ -451,6 +459,7 @@ extern "C" int scrf_destroy(scrf_handle h) {
   if (h->ev_join) hipEventDestroy(h->ev_join);
   hipFree(h->dec_lab); hipFree(h->dec_n); hipFree(h->dec_cost);
   hipFree(h->al_ph); hipFree(h->al_off);
+  hipFree(h->tr_inv);
   hipFree(h->post_buf);
   hipFree(h->lp_arcs); hipFree(h->lp_meta);
   if (h->dec_hlab) hipHostFree(h->dec_hlab);
@@ -1081,12 +1090,14 @@ struct ChunkBufs {
   uint32_t* lat_counts = nullptr;   // [nodes of the chunk] kept arcs per node
   uint64_t* lat_node_off = nullptr; // [nodes + 1]
   uint16_t* al_bp = nullptr;        // forced alignment: sum of T * K back pointers over the chunk's transcripts that fit
+  double *tr_aB = nullptr, *tr_bE = nullptr;   // transcript scoring: the same cells, forward (segment start) and backward (segment end) sums
   bool lamT_ready = false;   // sparse maps: h->d_lamT already re-laid for this call (scrf_fb_batch: once, before the lanes fork)
 };
 
 // ponly (scrf_posteriors_batch): the recursion of the training path without anything that needs labels or feeds the
 // gradient -- the linear-domain vectors (or alpha_dur / beta) and the per-frame state mass, no count buffers
-struct Need { bool fb, post, beta, vit; bool fused = false; bool vitfast = false; bool la = false; bool hybrid = false; bool ponly = false; bool plog = false; bool lat = false; bool align = false; };
+struct Need { bool fb, post, beta, vit; bool fused = false; bool vitfast = false; bool la = false; bool hybrid = false; bool ponly = false; bool plog = false; bool lat = false; bool align = false; bool trans = false; };
+// trans (scrf_transcript_batch): two doubles per (frame, transcript position) cell of the chunk
 // align (scrf_align_batch): the back pointers of the chunk's (frame, transcript position) cells
 // lat (scrf_lattice_prune_batch): four distance arrays over the chunk's frames and the node counts / offsets
 // plog: ponly through the log-domain recursion (SCRF_PREC_EXACT)
@@ -1275,6 +1286,10 @@ static void chunk_layout(scrf_handle h, scrf_batch b, uint32_t u0, uint32_t u1, 
     cb->lat_node_off = a.take<uint64_t>(nfr + nutt + 1);
   }
   if (nd.align) cb->al_bp = a.take<uint16_t>(h->al_bp_off[u1] - h->al_bp_off[u0]);
+  if (nd.trans) {
+    cb->tr_aB = a.take<double>(h->tr_cell_off[u1] - h->tr_cell_off[u0]);
+    cb->tr_bE = a.take<double>(h->tr_cell_off[u1] - h->tr_cell_off[u0]);
+  }
 }
 
 // (*tmp takes the walk's pointers, which a measurement does not use: the planner passes the same one for every candidate)
@@ -2321,6 +2336,37 @@ static int post_run(scrf_handle h, scrf_batch b, const PostOut& po, int latch[2]
   return SCRF_OK;
 }
 
+// the segment queries of a call (scrf_posteriors_batch, scrf_transcript_batch): the segments of a path, back to back per
+// utterance, label value l + L (d - 1) -> q [3][nq]: utterance, end frame, label value
+static int seg_queries(scrf_handle h, scrf_batch b, const char* fn, const uint32_t* seg_labels, const uint64_t* lab_off, bool want,
+                       std::vector<uint32_t>* qv, uint64_t* nq_out) {
+  const ScrfLayout& l = h->lay;
+  const uint64_t nF = b->frame_off[b->U];
+  std::vector<uint32_t>& q = *qv;
+  uint64_t nq = 0;
+  if (want) {
+    if (!seg_labels || !lab_off) return fail(h, SCRF_ERR_INVALID, "%s: seg_post needs seg_labels and lab_off", fn);
+    nq = lab_off[b->U];
+    if (lab_off[0] != 0 || nq > nF) return fail(h, SCRF_ERR_INVALID, "%s: lab_off does not describe back-to-back segments of this batch", fn);
+    q.resize(3 * (size_t)nq + 1);
+    for (uint32_t u = 0; u < b->U; u++) {
+      if (lab_off[u + 1] < lab_off[u] || lab_off[u + 1] > nq) return fail(h, SCRF_ERR_INVALID, "%s: lab_off is not ascending at utterance %u", fn, u);
+      uint64_t e = 0;   // frames consumed so far
+      for (uint64_t i = lab_off[u]; i < lab_off[u + 1]; i++) {
+        const uint32_t v = seg_labels[i];
+        if (v >= l.L * l.D) return fail(h, SCRF_ERR_INVALID, "%s: utterance %u, segment %llu: label %u is out of range (labels x maximum duration = %u)",
+                                        fn, u, (unsigned long long)(i - lab_off[u]), v, l.L * l.D);
+        e += v / l.L + 1;
+        if (e > b->T[u]) return fail(h, SCRF_ERR_INVALID, "%s: utterance %u, segment %llu ends at frame %llu, past the utterance's %u frames",
+                                     fn, u, (unsigned long long)(i - lab_off[u]), (unsigned long long)(e - 1), b->T[u]);
+        q[i] = u; q[nq + i] = (uint32_t)(e - 1); q[2 * nq + i] = v;
+      }
+    }
+  }
+  *nq_out = nq;
+  return SCRF_OK;
+}
+
 extern "C" int scrf_posteriors_batch(scrf_handle h, scrf_batch b, double* zx, double* frame_post, double* end_post,
                                      const uint32_t* seg_labels, const uint64_t* lab_off, double* seg_post) {
   if (!h || !b) return SCRF_ERR_INVALID;
@@ -2329,28 +2375,10 @@ extern "C" int scrf_posteriors_batch(scrf_handle h, scrf_batch b, double* zx, do
   HIPCHK(h, hipSetDevice(h->device));
   const ScrfLayout& l = h->lay;
   const uint64_t nF = b->frame_off[b->U];
-  // the queries: the segments of a path, back to back per utterance, label value l + L (d - 1)
   std::vector<uint32_t> q;   // [3][nq]: utterance, end frame, label value
   uint64_t nq = 0;
-  if (seg_post) {
-    if (!seg_labels || !lab_off) return fail(h, SCRF_ERR_INVALID, "scrf_posteriors_batch: seg_post needs seg_labels and lab_off");
-    nq = lab_off[b->U];
-    if (lab_off[0] != 0 || nq > nF) return fail(h, SCRF_ERR_INVALID, "scrf_posteriors_batch: lab_off does not describe back-to-back segments of this batch");
-    q.resize(3 * (size_t)nq + 1);
-    for (uint32_t u = 0; u < b->U; u++) {
-      if (lab_off[u + 1] < lab_off[u] || lab_off[u + 1] > nq) return fail(h, SCRF_ERR_INVALID, "scrf_posteriors_batch: lab_off is not ascending at utterance %u", u);
-      uint64_t e = 0;   // frames consumed so far
-      for (uint64_t i = lab_off[u]; i < lab_off[u + 1]; i++) {
-        const uint32_t v = seg_labels[i];
-        if (v >= l.L * l.D) return fail(h, SCRF_ERR_INVALID, "scrf_posteriors_batch: utterance %u, segment %llu: label %u is out of range (labels x maximum duration = %u)",
-                                        u, (unsigned long long)(i - lab_off[u]), v, l.L * l.D);
-        e += v / l.L + 1;
-        if (e > b->T[u]) return fail(h, SCRF_ERR_INVALID, "scrf_posteriors_batch: utterance %u, segment %llu ends at frame %llu, past the utterance's %u frames",
-                                     u, (unsigned long long)(i - lab_off[u]), (unsigned long long)(e - 1), b->T[u]);
-        q[i] = u; q[nq + i] = (uint32_t)(e - 1); q[2 * nq + i] = v;
-      }
-    }
-  }
+  rc = seg_queries(h, b, "scrf_posteriors_batch", seg_labels, lab_off, seg_post != nullptr, &q, &nq);
+  if (rc != SCRF_OK) return rc;
   const size_t by_occ = frame_post ? pad256(sizeof(double) * nF * l.L) : 0, by_end = end_post ? pad256(sizeof(double) * nF) : 0;
   const size_t by_seg = pad256(sizeof(double) * nq), by_q = pad256(sizeof(uint32_t) * 3 * nq);
   const size_t need = by_occ + by_end + by_seg + by_q + 256;
@@ -2993,6 +3021,29 @@ extern "C" int scrf_viterbi_batch(scrf_handle h, scrf_batch b, uint32_t* seg_lab
   return decode_result_fetch(h, b, "scrf_viterbi_batch", call, seg_labels, max_labels, lab_off, best_cost);
 }
 
+// the transcripts of a call and two offset arrays ([U + 1] each: phone_off | a second one, the cells before each utterance),
+// uploaded once per call into buffers kept across calls (scrf_align_batch, scrf_transcript_batch)
+static int upload_transcripts(scrf_handle h, uint32_t U, const uint32_t* phones, const uint64_t* phone_off, const uint64_t* cell_off) {
+  const uint64_t NP = phone_off[U];
+  if (NP > h->al_cap_ph) {
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    hipFree(h->al_ph); h->al_ph = nullptr; h->al_cap_ph = 0;
+    HIPCHK(h, hipMalloc((void**)&h->al_ph, sizeof(uint32_t) * NP));
+    h->al_cap_ph = NP;
+  }
+  if (U + 1 > h->al_cap_u) {
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    hipFree(h->al_off); h->al_off = nullptr; h->al_cap_u = 0;
+    HIPCHK(h, hipMalloc((void**)&h->al_off, sizeof(uint64_t) * 2 * (U + 1)));
+    h->al_cap_u = U + 1;
+  }
+  if (NP) HIPCHK(h, hipMemcpyAsync(h->al_ph, phones, sizeof(uint32_t) * NP, hipMemcpyHostToDevice, h->stream));
+  HIPCHK(h, hipMemcpyAsync(h->al_off, phone_off, sizeof(uint64_t) * (U + 1), hipMemcpyHostToDevice, h->stream));
+  HIPCHK(h, hipMemcpyAsync(h->al_off + (U + 1), cell_off, sizeof(uint64_t) * (U + 1), hipMemcpyHostToDevice, h->stream));
+  HIPCHK(h, hipStreamSynchronize(h->stream));   // the host arrays are the caller's (and pageable)
+  return SCRF_OK;
+}
+
 // ---------------------------------------------------------------------------------------------
 // batched forced alignment: scrf_viterbi_batch's chunk loop and score stage, a constrained search
 // ---------------------------------------------------------------------------------------------
@@ -3035,23 +3086,8 @@ extern "C" int scrf_align_batch(scrf_handle h, scrf_batch b, const uint32_t* pho
   CallTimer call(h);
   int rc = decode_result_room(h, b);
   if (rc != SCRF_OK) return rc;
-  // the transcripts and the two offset arrays, uploaded once per call into buffers kept across calls
-  if (NP > h->al_cap_ph) {
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    hipFree(h->al_ph); h->al_ph = nullptr; h->al_cap_ph = 0;
-    HIPCHK(h, hipMalloc((void**)&h->al_ph, sizeof(uint32_t) * NP));
-    h->al_cap_ph = NP;
-  }
-  if (U + 1 > h->al_cap_u) {
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    hipFree(h->al_off); h->al_off = nullptr; h->al_cap_u = 0;
-    HIPCHK(h, hipMalloc((void**)&h->al_off, sizeof(uint64_t) * 2 * (U + 1)));
-    h->al_cap_u = U + 1;
-  }
-  if (NP) HIPCHK(h, hipMemcpyAsync(h->al_ph, phones, sizeof(uint32_t) * NP, hipMemcpyHostToDevice, h->stream));
-  HIPCHK(h, hipMemcpyAsync(h->al_off, phone_off, sizeof(uint64_t) * (U + 1), hipMemcpyHostToDevice, h->stream));
-  HIPCHK(h, hipMemcpyAsync(h->al_off + (U + 1), h->al_bp_off.data(), sizeof(uint64_t) * (U + 1), hipMemcpyHostToDevice, h->stream));
-  HIPCHK(h, hipStreamSynchronize(h->stream));   // the host arrays are the caller's (and pageable)
+  rc = upload_transcripts(h, U, phones, phone_off, h->al_bp_off.data());
+  if (rc != SCRF_OK) return rc;
   h->n_al_calls++;
   Need nd{false, false, false, false};
   nd.align = true;
@@ -3083,6 +3119,186 @@ extern "C" int scrf_align_stats(scrf_handle h, uint64_t* n_calls, uint64_t* n_ch
   if (n_chunks) *n_chunks = h->n_al_chunks;
   if (n_wave) *n_wave = h->n_al_wave;
   if (n_group) *n_group = h->n_al_group;
+  return SCRF_OK;
+}
+
+// ---------------------------------------------------------------------------------------------
+// transcript scoring: post_run's chunk loop, score stage and free recursion (for Zx); the sums over the
+// alignments of each transcript in place of the free occupancy walk
+// ---------------------------------------------------------------------------------------------
+struct TransOut {
+  double* log_num = nullptr;   // [U], always formed (the segment queries read it)
+  double* occ = nullptr;       // [sum T][L]
+  double* end = nullptr;       // [sum T]
+  double* seg = nullptr;       // [n queries]
+  const uint32_t *q_u = nullptr, *q_e = nullptr, *q_lab = nullptr;
+  const uint64_t* lab_off = nullptr;   // host
+};
+
+// The free occupancy walk (k_post_occ*) does not run, so the per-frame state mass k_mass_check compares is not formed and
+// that check is skipped here; the recursion's own checks (an emptied vector, a transition sum below DBL_MIN) still raise
+// SCRF_ERR_NUMERIC, and so does a fitting transcript whose sum is not finite.
+static int transcript_run(scrf_handle h, scrf_batch b, const uint64_t* phone_off, int mode, const TransOut& to, int latch[2]) {
+  const ScrfLayout& l = h->lay;
+  const uint32_t U = b->U;
+  HIPCHK(h, hipMemsetAsync(b->d_status, 0, sizeof(int) * U, h->stream));
+  hipLaunchKernelGGL(k_latch_reset, dim3(1), dim3(1), 0, h->stream, h->d_latch);
+  const bool fast = h->cfg.train_precision >= SCRF_PREC_FAST;
+  const int f32 = h->cfg.train_precision == SCRF_PREC_FAST32;
+  Need nd{true, false, true, false};
+  nd.ponly = true;
+  nd.plog = !fast;
+  nd.trans = true;
+  set_batch_form(h, b, &nd);
+  ScrfBatchView bv = b->view();
+  if (!l.use_tf) ensure_m0(h, h->stream);
+  if (sparse(h)) relay_sparse_lambda(h, h->stream);
+  for (uint32_t u0 = 0; u0 < U;) {
+    const uint32_t u1 = plan_chunk(h, b, u0, nd);
+    ChunkBufs cb;
+    int rc = carve(h, b, u0, u1, nd, &cb, 0);
+    if (rc != SCRF_OK) return rc;
+    cb.lamT_ready = sparse(h);
+    rc = run_scores(h, b, u0, u1, cb, fast, f32);
+    if (rc != SCRF_OK) return rc;
+    PhaseTimer tm(h, PH_FB, cb.st);
+    uint32_t nl = 0;
+    rc = run_dp(h, b, u0, u1, cb, false, &nl, true);
+    if (rc != SCRF_OK) return rc;
+    uint64_t k_max = 0;   // over the transcripts that fit
+    for (uint32_t u = u0; u < u1; u++)
+      if (h->tr_cell_off[u + 1] > h->tr_cell_off[u]) k_max = std::max(k_max, phone_off[u + 1] - phone_off[u]);
+    const ScrfTransArgs ta{h->al_ph, h->al_off, h->al_off + (U + 1), h->tr_inv, h->tr_inv + phone_off[U], cb.tr_aB, cb.tr_bE,
+                           mode, cb.lin ? 1 : 0, to.seg ? 1 : 0};
+    h->n_tr_chunks++;
+    KT_RUN("k_transcript", cb.st, launch_transcript(cb.st, l, bv, u0, u1 - u0, k_max, cb.S, cb.smax, cb.M, cb.m_per_frame, ta, b->d_status,
+                                                    to.log_num, to.occ, to.end));
+    nl++;
+    if (to.seg) {
+      const uint64_t q0 = to.lab_off[u0], nq = to.lab_off[u1] - q0;
+      KT_RUN("k_transcript_seg", cb.st, launch_transcript_seg(cb.st, l, bv, u0, to.q_u, to.q_e, to.q_lab, q0, nq, cb.S, cb.smax, ta, to.log_num, to.seg));
+      nl++;
+    }
+    tm.stop(nl);
+    HIPCHK(h, hipGetLastError());
+    u0 = u1;
+  }
+  int rc = queue_status(h, b);
+  if (rc != SCRF_OK) return rc;
+  HIPCHK(h, hipEventSynchronize(h->ev_status));
+  latch_decode(h->h_latch, latch);
+  return SCRF_OK;
+}
+
+extern "C" int scrf_transcript_batch(scrf_handle h, scrf_batch b, const uint32_t* phones, const uint64_t* phone_off, int mode,
+                                     double* log_num, double* zx, double* frame_post, double* end_post,
+                                     const uint32_t* seg_labels, const uint64_t* lab_off, double* seg_post) {
+  if (!h || !b || !phone_off) return SCRF_ERR_INVALID;
+  const char* fn = "scrf_transcript_batch";
+  int rc = post_model_ok(h, fn);
+  if (rc != SCRF_OK) return rc;
+  const ScrfLayout& l = h->lay;
+  if (l.D > 0x7fff) return fail(h, SCRF_ERR_INVALID, "%s: maximum duration %u is not served (at most %u, as scrf_align_batch)", fn, l.D, 0x7fffu);
+  if (mode != SCRF_ALIGN_ONE && mode != SCRF_ALIGN_RUNS)
+    return fail(h, SCRF_ERR_INVALID, "%s: unknown mode %d (SCRF_ALIGN_ONE = 0, SCRF_ALIGN_RUNS = 1)", fn, mode);
+  const uint32_t U = b->U;
+  const uint64_t NP = phone_off[U], nF = b->frame_off[U];
+  if (phone_off[0] != 0 || (NP && !phones)) return fail(h, SCRF_ERR_INVALID, "%s: phone_off must start at 0 and phones must be given", fn);
+  // the checks of every transcript, the cells before each utterance (the chunk planner sizes a chunk with them) and the
+  // inverted lists: per utterance its positions sorted by label (a counting sort: ascending inside a label)
+  h->tr_cell_off.assign(U + 1, 0);
+  for (uint32_t u = 0; u < U; u++) {
+    if (phone_off[u + 1] < phone_off[u] || phone_off[u + 1] > NP) return fail(h, SCRF_ERR_INVALID, "%s: phone_off decreases at utterance %u", fn, u);
+    const uint64_t K = phone_off[u + 1] - phone_off[u];
+    const uint32_t* ph = phones + phone_off[u];
+    for (uint64_t k = 0; k < K; k++) {
+      if (ph[k] >= l.L)
+        return fail(h, SCRF_ERR_INVALID, "%s: phone %u at position %llu of utterance %u's transcript (the model has %u)", fn, ph[k],
+                    (unsigned long long)k, u, l.L);
+      if (mode == SCRF_ALIGN_RUNS && k >= 1 && ph[k] == ph[k - 1])
+        return fail(h, SCRF_ERR_INVALID, "%s: utterance %u's transcript repeats phone %u at position %llu; with SCRF_ALIGN_RUNS equal "
+                    "neighbours make the sum count a path more than once: collapse them first", fn, u, ph[k], (unsigned long long)k);
+    }
+    const bool fits = scrf_align_feasible(b->T[u], K, l.D, mode);
+    if (fits && transcript_smem_bytes(l, K) + 128 > 160 * 1024)   // + the 16 per-wavefront parts of end[t]
+      return fail(h, SCRF_ERR_INVALID, "%s: utterance %u's transcript of %llu phones needs (%u + 2) x %llu x 8 = %zu bytes of LDS, "
+                  "a workgroup has %d less 128", fn, u, (unsigned long long)K, l.D, (unsigned long long)K, transcript_smem_bytes(l, K), 160 * 1024);
+    h->tr_cell_off[u + 1] = h->tr_cell_off[u] + (fits ? (uint64_t)b->T[u] * K : 0);
+  }
+  std::vector<uint32_t> q;   // [3][nq]: utterance, end frame, label value
+  uint64_t nq = 0;
+  rc = seg_queries(h, b, fn, seg_labels, lab_off, seg_post != nullptr, &q, &nq);
+  if (rc != SCRF_OK) return rc;
+  const uint64_t n_inv = NP + (uint64_t)U * (l.L + 1);
+  h->tr_inv_h.assign(n_inv, 0);
+  for (uint32_t u = 0; u < U; u++) {
+    const uint64_t K = phone_off[u + 1] - phone_off[u];
+    const uint32_t* ph = phones + phone_off[u];
+    uint32_t* ioff = h->tr_inv_h.data() + NP + (uint64_t)u * (l.L + 1);
+    uint32_t* ipos = h->tr_inv_h.data() + phone_off[u];
+    for (uint64_t k = 0; k < K; k++) ioff[ph[k] + 1]++;
+    for (uint32_t c = 0; c < l.L; c++) ioff[c + 1] += ioff[c];
+    for (uint64_t k = 0; k < K; k++) ipos[ioff[ph[k]]++] = (uint32_t)k;   // ioff[c] now = the end of c's list = the start of c + 1's
+    for (uint32_t c = l.L; c >= 1; c--) ioff[c] = ioff[c - 1];
+    ioff[0] = 0;
+  }
+  HIPCHK(h, hipSetDevice(h->device));
+  const size_t by_occ = frame_post ? pad256(sizeof(double) * nF * l.L) : 0, by_end = end_post ? pad256(sizeof(double) * nF) : 0;
+  const size_t by_seg = pad256(sizeof(double) * nq), by_q = pad256(sizeof(uint32_t) * 3 * nq), by_ln = pad256(sizeof(double) * U);
+  const size_t need = by_occ + by_end + by_seg + by_q + by_ln + 256;
+  if (need > h->post_cap) {   // the posterior buffer of the handle, grown on demand and kept (scrf_abi.h)
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    hipFree(h->post_buf); h->post_buf = nullptr; h->post_cap = 0;
+    HIPCHK(h, hipMalloc((void**)&h->post_buf, need));
+    h->post_cap = need;
+  }
+  if (n_inv > h->tr_cap_inv) {
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    hipFree(h->tr_inv); h->tr_inv = nullptr; h->tr_cap_inv = 0;
+    HIPCHK(h, hipMalloc((void**)&h->tr_inv, sizeof(uint32_t) * n_inv));
+    h->tr_cap_inv = n_inv;
+  }
+  TransOut to;
+  char* pb = h->post_buf;
+  if (frame_post) to.occ = (double*)pb;
+  pb += by_occ;
+  if (end_post) to.end = (double*)pb;
+  pb += by_end;
+  to.log_num = (double*)pb;
+  pb += by_ln;
+  if (seg_post && nq) {
+    to.seg = (double*)pb;
+    uint32_t* dq = (uint32_t*)(pb + by_seg);
+    HIPCHK(h, hipMemcpyAsync(dq, q.data(), sizeof(uint32_t) * 3 * nq, hipMemcpyHostToDevice, h->stream));
+    to.q_u = dq; to.q_e = dq + nq; to.q_lab = dq + 2 * nq;
+    to.lab_off = lab_off;
+  }
+  if (n_inv) HIPCHK(h, hipMemcpyAsync(h->tr_inv, h->tr_inv_h.data(), sizeof(uint32_t) * n_inv, hipMemcpyHostToDevice, h->stream));
+  rc = upload_transcripts(h, U, phones, phone_off, h->tr_cell_off.data());   // ends with a synchronize: q may go
+  if (rc != SCRF_OK) return rc;
+  CallTimer call(h);
+  h->n_tr_calls++;
+  const uint64_t fb0 = h->n_lin_fallback;
+  int latch[2] = {0, 0};
+  rc = run_with_redo(h, latch, [&] { return transcript_run(h, b, phone_off, mode, to, latch); });
+  if (h->n_lin_fallback != fb0) h->n_tr_redone++;
+  if (rc != SCRF_OK) return rc;
+  call.stop();
+  if (latch[0] != 0) return fail(h, latch[0], "%s: utterance %d: %s", fn, latch[1], status_text(latch[0]));
+  if (log_num) HIPCHK(h, hipMemcpyAsync(log_num, to.log_num, sizeof(double) * U, hipMemcpyDeviceToHost, h->stream));
+  if (zx) HIPCHK(h, hipMemcpyAsync(zx, b->d_zx, sizeof(double) * U, hipMemcpyDeviceToHost, h->stream));
+  if (frame_post) HIPCHK(h, hipMemcpyAsync(frame_post, to.occ, sizeof(double) * nF * l.L, hipMemcpyDeviceToHost, h->stream));
+  if (end_post) HIPCHK(h, hipMemcpyAsync(end_post, to.end, sizeof(double) * nF, hipMemcpyDeviceToHost, h->stream));
+  if (to.seg) HIPCHK(h, hipMemcpyAsync(seg_post, to.seg, sizeof(double) * nq, hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  return SCRF_OK;
+}
+
+extern "C" int scrf_transcript_stats(scrf_handle h, uint64_t* n_calls, uint64_t* n_chunks, uint64_t* n_redone) {
+  if (!h) return SCRF_ERR_INVALID;
+  if (n_calls) *n_calls = h->n_tr_calls;
+  if (n_chunks) *n_chunks = h->n_tr_chunks;
+  if (n_redone) *n_redone = h->n_tr_redone;
   return SCRF_OK;
 }
 

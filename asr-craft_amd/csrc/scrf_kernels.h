@@ -304,6 +304,20 @@ __host__ __device__ inline bool scrf_align_feasible(uint32_t T, uint64_t K, uint
   if (T == 0 || K == 0 || K > T) return false;
   return mode != SCRF_ALIGN_ONE || K * D >= T;
 }
+// can end(t, k) lie on a complete path?  (shared by the search and by the transcript sums of scrf_transcript.hip)
+__device__ inline bool align_live(int t, int k, int T, int K, int D, int mode) {
+  if (k > t || K - 1 - k > T - 1 - t) return false;
+  if (mode == SCRF_ALIGN_ONE && ((long long)(k + 1) * D < t + 1 || (long long)(K - 1 - k) * D < T - 1 - t)) return false;
+  return true;
+}
+
+// the same for boundary(t, k), the start of position k's next segment at frame t: k segments (ONE) cover the t frames before it
+__device__ inline bool align_live_b(int t, int k, int T, int K, int D, int mode) {
+  if (k > t || K - k > T - t) return false;
+  if (mode == SCRF_ALIGN_ONE && ((long long)k * D < t || (long long)(K - k) * D < T - t)) return false;
+  return true;
+}
+
 int align_wave_supported(const ScrfLayout& lay);
 // S (fp64 scores) or Wn (their float arc weights, segment model only): exactly one is given
 void launch_align_wave(hipStream_t st, const ScrfLayout& lay, ScrfBatchView bv, uint32_t u0, uint32_t n_utts, const double* S,
@@ -313,5 +327,29 @@ size_t align_group_smem_bytes(const ScrfLayout& lay, uint64_t K);
 void launch_align_group(hipStream_t st, const ScrfLayout& lay, ScrfBatchView bv, uint32_t u0, uint32_t n_utts, uint32_t k_max,
                         const double* S, const float* Wn, const double* M, int m_per_frame, int frame_model,
                         const ScrfAlignArgs& aa, uint32_t* out_labels, uint32_t* out_n, float* out_cost);
+
+// ---- transcript scoring (scrf_transcript.hip)
+struct ScrfTransArgs {
+  const uint32_t* phones;      // transcripts of the batch, back to back
+  const uint64_t* phone_off;   // [U + 1]
+  const uint64_t* cell_off;    // [U + 1] (frame, position) cells before each utterance: T * K of every transcript that fits
+  const uint32_t* inv_pos;     // [sum K] per utterance its positions sorted by label, ascending inside a label
+  const uint32_t* inv_off;     // [U][L + 1] where each label's positions start in the utterance's part of inv_pos
+  double* aB;                  // the chunk's forward cells [T][K]; utterance u's start at cell_off[u] - cell_off[u0]
+  double* bE;                  // the chunk's backward cells, laid out the same
+  int mode;                    // scrf_align_mode
+  int lin;                     // the scores are exp(S - smax) with smax per row (the linear-domain path), not S
+  int want_seg;                // segment queries follow: run the backward sweep even without frame / end output
+};
+// dynamic LDS of a workgroup whose longest transcript has K phones: (D + 2) K doubles
+size_t transcript_smem_bytes(const ScrfLayout& lay, uint64_t K);
+// log_num [U], occ [sum T][L] (or NULL), endp [sum T] (or NULL): arrays of the whole batch.  k_max: the longest transcript
+// of the chunk that fits
+void launch_transcript(hipStream_t st, const ScrfLayout& lay, ScrfBatchView bv, uint32_t u0, uint32_t n_utts, uint64_t k_max,
+                       const double* S, const double* smax, const double* M, int m_per_frame, const ScrfTransArgs& ta,
+                       int* status, double* log_num, double* occ, double* endp);
+void launch_transcript_seg(hipStream_t st, const ScrfLayout& lay, ScrfBatchView bv, uint32_t u0, const uint32_t* q_u,
+                           const uint32_t* q_e, const uint32_t* q_lab, uint64_t q0, uint64_t nq, const double* S,
+                           const double* smax, const ScrfTransArgs& ta, const double* log_num, double* out);
 
 #endif  // SCRF_KERNELS_H_

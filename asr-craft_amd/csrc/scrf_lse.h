@@ -37,4 +37,17 @@ __device__ __forceinline__ double col_lse(const FbLse& c, int n_i, VAL val, int*
   return r;
 }
 
+// One thread's max-shifted log-sum-exp over terms given one by one, in the caller's order (scrf_transcript.hip): the shift
+// follows the running maximum, so every term costs one exp and none is evaluated twice.  -inf terms are skipped; no term
+// at all gives -inf; a NaN term gives NaN.
+struct LseAcc {
+  double m = -INFINITY, s = 0.0;
+  __device__ __forceinline__ void add(double x) {
+    if (x == -INFINITY) return;
+    if (x > m) { s = s * exp(m - x) + 1.0; m = x; }
+    else s += exp(x - m);
+  }
+  __device__ __forceinline__ double value() const { return (s > 0.0 || s != s) ? m + log(s) : -INFINITY; }
+};
+
 #endif  // SCRF_LSE_H_

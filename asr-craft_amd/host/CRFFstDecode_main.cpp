@@ -44,6 +44,15 @@
 //   of every aligned segment.  A transcript that does not fit gets the align mode's warning and an empty entry.
 //   crf_align_unit=label (default) is the host path on phone-duration labels, unchanged.  Refused outside align mode and
 //   together with crf_lat_outdir / crf_output_mlffile (no lattice is built).
+// A fifth one (transcript scoring), both flags in crf_decode_mode=align crf_align_unit=phone only:
+//   crf_output_scorefile=PATH: one line per utterance, `sent n_phones log_num zx logp` (17 significant digits): the log of the
+//   sum over EVERY alignment of the transcript, the log-partition, and their difference log P(transcript | x).  A transcript
+//   that does not fit gets the align mode's warning and -inf.  Runs under crf_precision (default fast).  `sent` is the
+//   running index of the utterance among those decoded, as in the label file and crf_output_conffile; with crf_eval_range
+//   the warnings on stderr name the sentence of the input files instead.
+//   crf_conf_given=transcript|none (default none = the bytes of before): whether the last column of crf_output_conffile is
+//   the posterior of the aligned segment given the transcript, or the free one (which mostly measures whether free
+//   decoding agrees with the transcript).
 #include "cli_common.h"
 
 #include <math.h>
@@ -108,6 +117,13 @@ int main(int argc, char** argv) {
   const long align_repeat = a.num("crf_align_repeat", 1);
   if (align_repeat != 0 && align_repeat != 1) { std::cerr << "crf_align_repeat=" << align_repeat << " (1|0)" << std::endl; return 1; }
   const bool want_conf = a.has("crf_output_conffile");
+  const bool want_score = a.has("crf_output_scorefile");
+  if (want_score && !align_phone) { std::cerr << "crf_output_scorefile needs crf_decode_mode=align crf_align_unit=phone" << std::endl; return 1; }
+  if (a.has("crf_conf_given") && !align_phone) { std::cerr << "crf_conf_given needs crf_decode_mode=align crf_align_unit=phone" << std::endl; return 1; }
+  const std::string conf_given = a.str("crf_conf_given", "none");
+  if (conf_given != "none" && conf_given != "transcript") { std::cerr << "crf_conf_given=" << conf_given << " (transcript|none)" << std::endl; return 1; }
+  if (conf_given == "transcript" && !want_conf) { std::cerr << "crf_conf_given=transcript needs crf_output_conffile" << std::endl; return 1; }
+  const bool conf_transcript = conf_given == "transcript";
   if (want_conf && (post_mode || (align_mode && !align_phone) || a.has("crf_lat_outdir") || a.has("crf_output_mlffile"))) {
     std::cerr << "crf_output_conffile goes with the best paths of the label file only: not with crf_decode_mode=" << mode
               << ", crf_lat_outdir or crf_output_mlffile" << std::endl;
@@ -170,7 +186,7 @@ int main(int argc, char** argv) {
   crf.setNActualLabs(m.fmap.nActualLabs);
   crf.setModelType(m.mtype);
   crf.setDevice((int)a.num("crf_device", 0));
-  if (post_mode || want_conf) crf.setTrainPrecision(parse_precision(a));   // the posterior pass runs under the training precision
+  if (post_mode || want_conf || want_score) crf.setTrainPrecision(parse_precision(a));   // the posterior pass runs under the training precision
   try {
     crf.setFeatureMap(CRF_FeatureMap::createFeatureMap(&m.fmap));
   } catch (std::exception& e) { std::cerr << "Exception: " << e.what() << std::endl; return -1; }
@@ -365,13 +381,31 @@ int main(int argc, char** argv) {
   if (align_phone) {
     // forced alignment on phones, whole device batches of utterances (crf_bunch_size of them, default 256)
     const size_t bunch = (size_t)std::max(1L, a.num("crf_bunch_size", 256));
+    std::ofstream score;
+    if (want_score) {
+      score.open(a.str("crf_output_scorefile").c_str());
+      if (!score.is_open()) { std::cerr << "ERROR: Failed opening file: " << a.str("crf_output_scorefile") << std::endl; return -1; }
+      score.precision(17);
+    }
+    const int amode = align_repeat ? SCRF_ALIGN_RUNS : SCRF_ALIGN_ONE;
     bool at_end = strm.nextseg() == QN_SEGID_BAD;
     while (!at_end) {
       try {
         std::vector<std::vector<uint32_t> > labs;
         std::vector<float> costs;
         std::vector<std::vector<double> > sp;
-        crf_amd_alignments(&strm, &crf, bunch, align_repeat ? SCRF_ALIGN_RUNS : SCRF_ALIGN_ONE, &labs, &costs, want_conf ? &sp : nullptr, &at_end);
+        if (want_score || conf_transcript) {
+          // the same alignment, and on the same device batch the sums over all alignments of each transcript
+          std::vector<double> log_num, zx;
+          std::vector<uint32_t> n_ph;
+          crf_amd_transcript_scores(&strm, &crf, bunch, amode, &log_num, &zx, &n_ph, &labs, &costs, (want_conf && conf_transcript) ? &sp : nullptr,
+                                    (want_conf && !conf_transcript) ? &sp : nullptr, &at_end);
+          if (want_score)
+            for (size_t i = 0; i < log_num.size(); i++)
+              score << u + i << " " << n_ph[i] << " " << log_num[i] << " " << zx[i] << " " << log_num[i] - zx[i] << "\n";
+        } else {
+          crf_amd_alignments(&strm, &crf, bunch, amode, &labs, &costs, want_conf ? &sp : nullptr, &at_end);
+        }
         if (want_conf) write_conf(labs, sp);
         for (const auto& l : labs) {
           if (l.empty()) std::cerr << "WARNING: the labels of sentence " << sents[u] << " do not fit its lattice" << std::endl;

@@ -11,18 +11,8 @@ size_t crf_amd_alignments(CRF_FeatureStream* ftr_strm, CRF_Model* crf, size_t ma
   const uint32_t L = crf->getNActualLabs() ? crf->getNActualLabs() : crf->getNLabs();
   // the transcripts: the phones of the labelled nodes in order, runs collapsed where a phone may repeat over segments anyway
   std::vector<uint32_t> phones;
-  std::vector<uint64_t> poff(U + 1, 0);
-  for (size_t u = 0; u < U; u++) {
-    const uint32_t* lab = sb.labels(u);
-    if (!lab) throw std::runtime_error("crf_amd_alignments: The label stream is found NULL or the label width is found 0 under the align mode.");
-    for (uint32_t t = 0; t < sb.T[u]; t++) {
-      if (lab[t] == CRF_LAB_BAD) continue;
-      const uint32_t p = lab[t] % L;
-      if (mode == SCRF_ALIGN_RUNS && phones.size() > poff[u] && phones.back() == p) continue;
-      phones.push_back(p);
-    }
-    poff[u + 1] = phones.size();
-  }
+  std::vector<uint64_t> poff;
+  crf_amd::node_label_transcripts(sb, L, mode, "crf_amd_alignments", &phones, &poff);
   std::vector<uint32_t> labs(sb.frames);
   std::vector<uint64_t> off(U + 1, 0);
   std::vector<float> cst(U, 0.0f);

@@ -655,6 +655,41 @@ size_t crf_amd_alignments(CRF_FeatureStream* ftr_strm, CRF_Model* crf, size_t ma
                           std::vector<std::vector<uint32_t> >* labels, std::vector<float>* costs,
                           std::vector<std::vector<double> >* seg_post, bool* at_end);
 
+// the phone transcripts of a batch's utterances as the two calls on transcripts read them from the node labels (see above):
+// phones back to back, poff [U + 1].  An utterance without a label stream throws, naming `fn`.
+namespace crf_amd {
+inline void node_label_transcripts(const StreamBatch& sb, uint32_t L, int mode, const char* fn, std::vector<uint32_t>* phones,
+                                   std::vector<uint64_t>* poff) {
+  const size_t U = sb.T.size();
+  phones->clear();
+  poff->assign(U + 1, 0);
+  for (size_t u = 0; u < U; u++) {
+    const uint32_t* lab = sb.labels(u);
+    if (!lab) throw std::runtime_error(std::string(fn) + ": The label stream is found NULL or the label width is found 0 under the align mode.");
+    for (uint32_t t = 0; t < sb.T[u]; t++) {
+      if (lab[t] == CRF_LAB_BAD) continue;
+      const uint32_t p = lab[t] % L;
+      if (mode == SCRF_ALIGN_RUNS && phones->size() > (*poff)[u] && phones->back() == p) continue;
+      phones->push_back(p);
+    }
+    (*poff)[u + 1] = phones->size();
+  }
+}
+}  // namespace crf_amd
+
+// Transcript scoring (scrf_transcript_batch) of one device batch, in the style of crf_amd_alignments and on
+// the same transcripts (read from the node labels; with SCRF_ALIGN_RUNS equal neighbours are collapsed, which that mode of
+// the engine call requires).  log_num[u] = the log of the sum over every alignment of the transcript (-inf when it does
+// not fit), zx[u] = the log-partition, n_phones[u] = the transcript's length; each may be NULL.  With `labels` the batch is
+// also aligned (scrf_align_batch, as crf_amd_alignments does) and labels / costs return the paths; seg_post_given then
+// receives the posterior of every aligned segment GIVEN the transcript, seg_post_free the free one of crf_amd_alignments
+// (each may be NULL).  All device calls run on the same batch; the stream is advanced once.
+size_t crf_amd_transcript_scores(CRF_FeatureStream* ftr_strm, CRF_Model* crf, size_t max_utts, int mode,
+                                 std::vector<double>* log_num, std::vector<double>* zx, std::vector<uint32_t>* n_phones,
+                                 std::vector<std::vector<uint32_t> >* labels, std::vector<float>* costs,
+                                 std::vector<std::vector<double> >* seg_post_given,
+                                 std::vector<std::vector<double> >* seg_post_free, bool* at_end);
+
 // lattice builders: same call as the reference's templates; the arcs come from the engine in
 // AddArc order and are replayed into the caller's FST object
 class CRF_LatticeBuilder {

@@ -454,6 +454,61 @@ class Engine:
         self._chk(self.lib.scrf_align_stats(self.h, *[C.byref(x) for x in v]))
         return tuple(x.value for x in v)
 
+    @staticmethod
+    def _ragged(x, U):
+        """(flat uint32 values, uint64 offsets [U + 1]) of per-utterance sequences or of a RaggedLabels"""
+        if isinstance(x, RaggedLabels):
+            return (np.ascontiguousarray(x.flat[:int(x.off[U])], dtype=np.uint32), np.ascontiguousarray(x.off, dtype=np.uint64))
+        off = np.zeros(U + 1, dtype=np.uint64)
+        off[1:] = np.cumsum([len(t) for t in x])
+        flat = np.ascontiguousarray(np.concatenate([np.asarray(t, dtype=np.uint32) for t in x]) if U else [], dtype=np.uint32)
+        return flat, off
+
+    def transcript_batch(self, batch, transcripts, mode=ALIGN_RUNS, frame=True, end=True, segments=None):
+        """Transcript scoring (scrf_transcript_batch): the sum over every alignment of each utterance's phone transcript.
+        transcripts as align_batch takes them (with ALIGN_RUNS equal neighbours are refused, not collapsed).  Returns a dict
+        in posteriors_batch's format -- "frame", "end", "segments" are now conditioned on the transcript; segments takes what
+        align_batch returns -- plus "log_num" [U] (the log of the sum), "zx" [U] and "logp" = log_num - zx = log P(q | x).
+        An utterance whose transcript does not fit gets log_num = -inf and zeros."""
+        U = batch.n
+        if batch.Ts is None:
+            raise ValueError("transcript_batch: the batch does not know its utterance lengths (Batch.Ts)")
+        if len(transcripts) != U:
+            raise ValueError("transcript_batch: %d transcripts for a batch of %d utterances" % (len(transcripts), U))
+        if segments is not None and len(segments) != U:
+            raise ValueError("transcript_batch: segments has %d entries for a batch of %d utterances" % (len(segments), U))
+        ph, poff = self._ragged(transcripts, U)
+        out = {"log_num": np.empty(U), "zx": np.empty(U)}
+        fp = np.empty((batch.n_frames, self.L)) if frame else None
+        ep = np.empty(batch.n_frames) if end else None
+        labs = off = sp = None
+        if segments is not None:
+            labs, off = self._ragged(segments, U)
+            sp = np.empty(int(off[U]))
+        self._chk(self.lib.scrf_transcript_batch(self.h, batch.handle, _p(ph), _p(poff), C.c_int(int(mode)), _p(out["log_num"]),
+                                                 _p(out["zx"]), _p(fp) if frame else None, _p(ep) if end else None,
+                                                 _p(labs) if sp is not None else None, _p(off) if sp is not None else None,
+                                                 _p(sp) if sp is not None else None))
+        with np.errstate(invalid="ignore"):
+            out["logp"] = out["log_num"] - out["zx"]
+        fo = np.concatenate([[0], np.cumsum(batch.Ts)]).astype(np.int64)
+        if frame:
+            out["frame_flat"] = fp
+            out["frame"] = [fp[fo[u]:fo[u + 1]] for u in range(U)]
+        if end:
+            out["end_flat"] = ep
+            out["end"] = [ep[fo[u]:fo[u + 1]] for u in range(U)]
+        if sp is not None:
+            out["segments_flat"] = sp
+            out["segments"] = [sp[int(off[u]):int(off[u + 1])] for u in range(U)]
+        return out
+
+    def transcript_stats(self):
+        """(scrf_transcript_batch calls, chunks swept, calls redone in the log domain) since create"""
+        v = [C.c_uint64() for _ in range(3)]
+        self._chk(self.lib.scrf_transcript_stats(self.h, *[C.byref(x) for x in v]))
+        return tuple(x.value for x in v)
+
     def batch_is_fused(self, batch):
         f = C.c_int()
         self._chk(self.lib.scrf_batch_is_fused(self.h, batch.handle, C.byref(f)))

@@ -377,6 +377,58 @@ int scrf_align_batch(scrf_handle h, scrf_batch b, const uint32_t* phones, const 
  * through the EXACT path instead, once per sub-chunk it is re-planned into); of these, by the wavefront / by the workgroup kernel */
 int scrf_align_stats(scrf_handle h, uint64_t* n_calls, uint64_t* n_chunks, uint64_t* n_wave, uint64_t* n_group);
 
+/* ---- transcript scoring --------------------------------------------------------------------------- */
+/* replaces: the numerator gammas of lattice o label acceptor, CRF_LatticeBuilder::getAlignmentGammas and
+ * computeAlignedAlphaBeta (decoders/CRF_LatticeBuilder.cpp:129-165, :374-386), as
+ * trainers/gradbuilders/CRF_NewGradBuilderSoft.cpp:44-58 consumes them -- for every utterance of the batch, on phones, and
+ * as outputs only (nothing here feeds a gradient).  The log-semiring twin of scrf_align_batch: the same transcripts
+ * (phones / phone_off), the same hypotheses (the paths of the full lattice restricted by `mode`), but the SUM over all of
+ * them, in fp64: the score of a path is the fp64 sum of its log scores, there are no float arc weights.  With S(t,d,l) the
+ * score of the segment that ends at frame t with duration d and label l, M_t the transition matrix of frame t (or the only
+ * one; the transition into a segment is scored with M of the segment's first frame, as in scrf_posteriors_batch), D =
+ * lab_max_dur and LSE the log of a sum of exponentials:
+ *   aB(t,k) = LSE( aE(t-1,k-1) + M_t(q_{k-1},q_k)          advance, k >= 1
+ *                , aE(t-1,k)   + M_t(q_k,q_k) )            stay, SCRF_ALIGN_RUNS only
+ *   aE(t,k) = LSE_d( aB(t-d+1,k) + S(t,d,q_k) ), d = 1..min(D,t+1); the start term (d = t+1, k = 0) is S(t,t+1,q_0) alone
+ *   A       = aE(T-1,K-1)
+ *   bE(T-1,K-1) = 0;  bE(t,k) = LSE( bB(t+1,k+1) + M_{t+1}(q_k,q_{k+1}),  RUNS: bB(t+1,k) + M_{t+1}(q_k,q_k) )
+ *   bB(t,k) = LSE_d( S(t+d-1,d,q_k) + bE(t+d-1,k) )
+ *   g(t,d,k) = exp( aB(t-d+1,k) + S(t,d,q_k) + bE(t,k) - A )         (start term: aB := 0)
+ * The frame model has D = 1 and a segment is a frame.  SCRF_ALIGN_ONE sums over the paths whose label sequence is q,
+ * SCRF_ALIGN_RUNS over those whose collapsed phone sequence is q; either way the transcripts partition the lattice:
+ * sum over q of exp(A(q)) = exp(Zx).  With q_k == q_{k+1} in SCRF_ALIGN_RUNS one path would get several position
+ * assignments and be counted more than once: such a transcript is SCRF_ERR_INVALID (the message names utterance and
+ * position); collapse equal neighbours first.  SCRF_ALIGN_ONE takes repeats.
+ * Outputs are host arrays, each formed only when its pointer is not NULL; the batch needs no labels:
+ *   log_num[u]       = A;  zx[u] = Zx of the free recursion of the same pass (log P(q|x) = log_num - zx);
+ *   frame_post[f][l] = sum of g(t,d,k) over the k with q_k == l and the (t,d) covering f: scrf_posteriors_batch's layout,
+ *                      every row of a fitting utterance sums to 1;
+ *   end_post[t]      = sum over d, k of g(t,d,k) (1 at the last frame);
+ *   seg_post[i]      = sum over the k with q_k == l of g(e,d,k) for segment i of a query path, the queries exactly as
+ *                      scrf_posteriors_batch takes them -- what scrf_align_batch returned can be passed straight in.
+ * A transcript that does not fit (scrf_align_batch's rule, T = 0 included) is not an error: log_num = -inf, its frame_post
+ * / end_post / seg_post entries are 0, zx is delivered, the other utterances are unaffected.  q_k >= num_labs, an unknown
+ * mode, descending offsets, bad queries and the repeated-phone rule are SCRF_ERR_INVALID, checked before any launch.
+ * Runs as scrf_posteriors_batch does (train_precision, batch forms, chunking under scratch_bytes -- 16 bytes per frame x
+ * transcript position are part of a chunk --, the handle's posterior array for the outputs), without the free occupancy
+ * walk and therefore without the posterior-mass self-check that needs it.  No floating-point atomics: two runs and any
+ * chunking give the same bytes.  One workgroup per utterance; (lab_max_dur + 2) * K * 8 bytes must fit a workgroup's
+ * 160 KiB of LDS (SCRF_ERR_INVALID beyond, with the figure).  On the linear-domain tiers a score more than ~708 nats
+ * under its row's maximum reads as -inf; where that leaves a fitting transcript without a finite sum the call is redone
+ * in the log domain (the redo of the free recursion, counted below); a non-finite sum after that is SCRF_ERR_NUMERIC.
+ * Models: as scrf_posteriors_batch; SCRF_STDSEG, SCRF_STDSEG_NO_DUR, num_states > 1 and lab_max_dur > 32767 are refused. */
+int scrf_transcript_batch(scrf_handle h, scrf_batch b, const uint32_t* phones, const uint64_t* phone_off /* [n_utts+1] */,
+                          int mode,
+                          double* log_num,     /* [n_utts] or NULL */
+                          double* zx,          /* [n_utts] or NULL */
+                          double* frame_post,  /* [sum T][L] or NULL */
+                          double* end_post,    /* [sum T] or NULL */
+                          const uint32_t* seg_labels, const uint64_t* lab_off,   /* as scrf_align_batch wrote them, or NULL */
+                          double* seg_post);   /* [lab_off[n_utts]] or NULL */
+/* since scrf_create: calls; chunks swept (a redone call sweeps its chunks twice); calls redone in the log domain (the sums
+ * above, computeAlignedAlphaBeta's, lost every path of a fitting transcript to underflow, or the free recursion gave up) */
+int scrf_transcript_stats(scrf_handle h, uint64_t* n_calls, uint64_t* n_chunks, uint64_t* n_redone);
+
 /* ---- minibatch reduce + optimizer ------------------------------------------------------------ */
 /* replaces the join/sum/average of CRF_Minibatch_GradAccumulator::accumulateGradient
  * (trainers/accumulators/CRF_Minibatch_GradAccumulator.cpp:277-312): all-reduce (sum) of the
@@ -434,7 +486,7 @@ int scrf_sgd_step(scrf_handle h, double lr_or_eta, int use_adagrad, double eps);
  * kernel (the three that dominate a step). */
 #define SCRF_N_PHASES 10
 int scrf_last_timing(scrf_handle h, float* ms, uint32_t* n_launch);
-/* HIP-event time of every kernel of the last timed scrf_fb_batch / scrf_posteriors_batch / scrf_viterbi_batch / scrf_lattice_prune_batch / scrf_align_batch, one line per kernel
+/* HIP-event time of every kernel of the last timed scrf_fb_batch / scrf_posteriors_batch / scrf_viterbi_batch / scrf_lattice_prune_batch / scrf_align_batch / scrf_transcript_batch, one line per kernel
  * name: "name\tmilliseconds\tlaunches\n" (events recorded on the stream the kernel is launched on) */
 int scrf_kernel_timing(scrf_handle h, char* buf, size_t cap);
 int scrf_enable_timing(scrf_handle h, int on);
