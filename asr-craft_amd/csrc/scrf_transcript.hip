@@ -14,10 +14,13 @@
 // Cells that cannot lie on a complete path (align_live / align_live_b, the bounds of the search) are -inf and not computed.
 // Every sum is a max-shifted one over terms in a fixed order (LseAcc, scrf_lse.h); there is no floating-point atomic, and
 // nothing a cell adds depends on the launch: two runs and any chunking give the same bytes.
+// On the linear path (scores kept as exp(S - row maximum)) a live term whose exponential is zero or subnormal sends the
+// utterance to the log-domain redo (tr_score_live): the sum over a transcript's alignments has no right to drop it.
 //
 //   k_transcript      one workgroup per utterance, threads strided over k: the forward sweep, then the backward sweep with
 //                     the occupancy walk of k_post_occ per position and a per-label retire
 //   k_transcript_seg  one thread per segment query: sum over the positions that carry the queried label
+#include <float.h>
 #include <math.h>
 
 #include "scrf_dp_common.h"
@@ -32,6 +35,19 @@ __device__ __forceinline__ double tr_score(const double* __restrict__ Su, const 
                                            uint32_t L, uint32_t q) {
   const double v = Su[row * L + q];
   return lin ? smu[row] + log(v) : v;
+}
+
+// The same for a term of the forward sweep, whose other summand `with` is finite: on the linear path an ES below DBL_MIN
+// (zero: the term would vanish; subnormal: its log has lost bits) sets `lost`.  A free recursion may drop
+// such a term, because the label that holds the row maximum stands in the same sum; a sum over the alignments of a
+// transcript may not, because that label need not be in the transcript: the alignments through the term can carry all of
+// the mass, and A stays finite on those that are left.
+__device__ __forceinline__ double tr_score_live(const double* __restrict__ Su, const double* __restrict__ smu, int lin, uint64_t row,
+                                                uint32_t L, uint32_t q, bool with, bool& lost) {
+  const double v = Su[row * L + q];
+  if (!lin) return v;
+  lost |= with && v < DBL_MIN;
+  return smu[row] + log(v);
 }
 
 // threads that own transcript positions: K rounded up to a wavefront, at most 1024 -- a function of K alone, so that the
@@ -81,7 +97,11 @@ __global__ __launch_bounds__(1024) void k_transcript(ScrfLayout lay, ScrfBatchVi
   if (!m_per_frame) { mA1 = M[(size_t)qp1 * L + q1]; mS1 = M[(size_t)q1 * L + q1]; mN1 = M[(size_t)q1 * L + qn1]; }
   const bool regs = one && !m_per_frame;
 
-  // ---- forward
+  // ---- forward.  Every term whose aB is finite is read here through tr_score_live.  The backward sweep and
+  // k_transcript_seg read no other live term: a term (t, d, k) adds to g or to bB only where aB(t-d+1, k) and bE(t, k) are
+  // both finite, and with no term lost a finite aB is the aB of this sweep -- so they need no guard of their own.
+  bool lost = false;
+  if (tid == 0) wsum[0] = 0.0;   // the workgroup's flag until the backward sweep takes wsum; the frames' barriers come before any set
   {
     double* ring = trsm + 2 * (size_t)K;   // [D][K] aB(t', .), slot t' % D, a column private to its thread
     int slot = 0;
@@ -107,10 +127,11 @@ __global__ __launch_bounds__(1024) void k_transcript(ScrfLayout lay, ScrfBatchVi
           double e = -INFINITY;
           if (align_live(t, k, T, K, D, mode)) {
             LseAcc a;
-            if (k == 0 && t < D) a.add(tr_score(Su, smu, lin, base + t, L, q));   // from the start: duration t + 1
+            if (k == 0 && t < D) a.add(tr_score_live(Su, smu, lin, base + t, L, q, true, lost));   // from the start: duration t + 1
             for (int d = t < D ? t : D; d >= 1; d--) {
               const int s = slot - (d - 1) < 0 ? slot - (d - 1) + D : slot - (d - 1);
-              a.add(ring[(size_t)s * K + k] + tr_score(Su, smu, lin, base + d - 1, L, q));
+              const double ab = ring[(size_t)s * K + k];
+              a.add(ab + tr_score_live(Su, smu, lin, base + d - 1, L, q, ab > -INFINITY, lost));
             }
             e = a.value();
           }
@@ -122,8 +143,12 @@ __global__ __launch_bounds__(1024) void k_transcript(ScrfLayout lay, ScrfBatchVi
   }
   const double A = trsm[(size_t)((T - 1) & 1) * K + K - 1];
   if (tid == 0) log_num[u] = A;
-  if (!(A > -INFINITY && A < INFINITY)) {
-    // a transcript that fits has a path: every path lost a segment to ES == 0 (or the scores are not finite).  The call is
+  if (lost) wsum[0] = 1.0;
+  __syncthreads();
+  const bool any_lost = wsum[0] != 0.0;
+  if (any_lost || !(A > -INFINITY && A < INFINITY)) {
+    // a live term was lost to ES < DBL_MIN: whatever A is, it is the sum over the alignments that are left.  Or A is not
+    // finite: a transcript that fits has a path, so every path lost a segment (or the scores are not finite).  The call is
     // redone on the log path, or reports this utterance.
     if (tid == 0) atomicMax(&status[u], SCRF_ERR_NUMERIC);
     if (occ) for (uint64_t i = tid; i < (uint64_t)T * L; i += NB) occ[F0 * L + i] = 0.0;

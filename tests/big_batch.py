@@ -256,6 +256,8 @@ def array_bytes(name):
             out[a] = ns * L * L * 8
         elif a == "TE":                 # n-state: [nfr][P * P] fp64 next to five [nfr][L] (nstate_layout, scrf_engine.cpp:1909-1911)
             out[a] = nf * max(kw["P"] * kw["P"], kw["P"] * kw["K"]) * 8
+        elif a == "cells":              # transcript scoring: aB and bE, each [sum T * K] fp64 over the chunk's transcripts
+            out[a] = 8 * sum(n * T * K for T, K, n in zip(kw["Ts"], TRANSCRIPT_K[name], row["counts"]))
         elif a == "arcs":               # kept arcs, 20 bytes each: per frame t and duration d <= min(D, t + 1): L start or L * L
             out[a] = 20 * sum(n * lattice_arcs(T, L, D) for T, n in zip(kw["Ts"], row["counts"]))
         else:
@@ -288,7 +290,8 @@ def need_bytes(name, prec=EXACT):
         per_seg += 3 * L * D * L * 8                      # MX [nseg][L * D][La] and its posteriors
     if name == "latprune":
         per_fr += 20 * (D * L + L * L)
-    return int(1.25 * (ns * per_seg + nf * per_fr)) + (2 << 30)
+    cells = 2 * array_bytes(name)["cells"] if "cells" in row["arrays"] else 0
+    return int(1.25 * (ns * per_seg + nf * per_fr + cells)) + (2 << 30)
 
 
 C48 = [950, 820, 150, 50]
@@ -311,7 +314,17 @@ CASES = {
     "nstate": _case_row(dict(P=3, K=2, F=3, Ts=BASE_TS, seed=2108), [400, 300, 100, 50], largest="TE", make=NStateCase),
     "frame": _case_row(dict(L=6, D=1, in_w=3, Ts=BASE_TS, trans_ctx=0, frame_model=True, seed=2109), [400, 300, 100, 50], largest="M"),
     "latprune": _case_row(dict(L=48, D=25, in_w=5, Ts=BASE_TS, seed=2101), [130, 110, 20, 8], arrays=("arcs",)),
+    # transcript scoring: the long-K shape of tests/test_gpu_transcript.py, 510 utterances
+    "transcript": _case_row(dict(L=2, D=2, in_w=2, Ts=[1100, 1090], seed=2110), [270, 240], arrays=("cells",)),
 }
+TRANSCRIPT_K = {"transcript": [1030, 1020]}       # phones per base utterance (SCRF_ALIGN_ONE: K <= T <= K * D)
+
+
+def transcript_phones(name):
+    """the seeded transcript of every base utterance of CASES[name]"""
+    row = CASES[name]
+    rng = np.random.RandomState(row["kw"]["seed"] + 1)
+    return [rng.randint(0, row["kw"]["L"], K).astype(np.uint32) for K in TRANSCRIPT_K[name]]
 BOUNDARY = {"expf": EXPF_BREAK, "atb": ATB_BREAK, "sl": SL_BREAK, "transframe": TRANSFRAME_BREAK}
 
 # axis B: more utterances than the chunk caps

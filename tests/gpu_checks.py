@@ -1,6 +1,7 @@
 """Checks shared by tests/test_gpu_input_ranges.py and tests/test_gpu_fmap_settings.py: the decode surfaces of a batch against
 the oracle bit for bit, one training call per tier at the project's per-tier bounds of tests/test_gpu_parity.py, and the
-posterior output against tests/post_ref.py.  Each prints the largest deviation it saw before it asserts."""
+posterior output against tests/post_ref.py; and all_devs, the deviations of one transcript-scoring result (tests/test_gpu_transcript.py,
+tests/test_gpu_transcript_spread.py).  Each check prints the largest deviation it saw before it asserts."""
 import numpy as np
 
 import orc
@@ -80,3 +81,13 @@ def check_posteriors(c, ref, eng, b, tol, what):
         assert abs(out["zx"][u] - zx) <= max(1e-11, tol * 1e-2) * max(1, abs(zx))
     print("posteriors %s: max deviation %.3e (bound %.0e)" % (what, dev, tol))
     assert dev <= tol, dev
+
+
+def all_devs(out, u, r, zx, labs):
+    """every output of utterance u (a transcript that fits) against a reference Result and the free log-partition"""
+    T = r.frame_post.shape[0]
+    return [abs(out["zx"][u] - zx) / max(1.0, abs(zx)), abs(out["log_num"][u] - r.A) / max(1.0, abs(r.A)),
+            abs(out["logp"][u] - (r.A - zx)) / max(1.0, abs(r.A - zx)),
+            np.abs(out["frame"][u] - r.frame_post).max(), np.abs(out["end"][u] - r.end_post).max(),
+            np.abs(out["frame"][u].sum(axis=1) - 1.0).max(), abs(out["end"][u][T - 1] - 1.0),
+            np.abs(out["segments"][u] - r.queries(labs)).max()]

@@ -105,6 +105,12 @@ def test_every_axis_a_case_crosses_what_it_is_there_for():
     assert bb.atb_rows_per_chunk(bb.case_sizes("fused")[1]) > 64
     assert bb.sl_rows_per_chunk(bb.case_sizes("stdseg_lin")[1]) > 64
     assert bb.need_bytes("fused") < 64 << 30 and bb.need_bytes("general") < 64 << 30
+    # transcript scoring: each of the two cell arrays alone passes 2^32 bytes, every transcript fits in SCRF_ALIGN_ONE mode
+    kw = bb.CASES["transcript"]["kw"]
+    assert all(K <= T <= K * kw["D"] for T, K in zip(kw["Ts"], bb.TRANSCRIPT_K["transcript"]))
+    assert [len(p) for p in bb.transcript_phones("transcript")] == bb.TRANSCRIPT_K["transcript"]
+    assert bb.array_bytes("transcript")["cells"] == 8 * (270 * 1100 * 1030 + 240 * 1090 * 1020)
+    assert bb.need_bytes("transcript") < 16 << 30
 
 
 def test_axis_b_passes_the_utterance_caps():

@@ -1,7 +1,7 @@
 """-m gpu: batches of the size the engine is built for -- arrays past 2^32 bytes inside one chunk (axis A) and more utterances
 than the chunk caps (axis B) -- against the CPU oracle.  Every batch is a few base utterances repeated many times
 (tests/big_batch.py), so the expected gradient is sum_i counts[i] * g_i of the per-utterance oracle gradients and the
-expected numerator, Zx, best path, alignment, posteriors and pruned arcs of every copy are those of its base utterance.
+expected numerator, Zx, best path, alignment, transcript score, posteriors and pruned arcs of every copy are those of its base utterance.
 tests/test_big_batch.py (no GPU) asserts that each shape here crosses the byte size and the plan breakpoints it is there for.
 
 Bounds, all taken from the suite and none measured on the code under test: gradient relative to max |g| 1e-9 EXACT / FAST,
@@ -10,7 +10,8 @@ FAST32 (tests/test_gpu_score_staging.py, which holds the numerator to no bound o
 relative to max(1, |numerator|), 1e-11 EXACT / FAST, 1e-6 FASTLIN, 1e-5 FAST32 (tests/test_gpu_input_ranges.py, and for
 FASTLIN tests/test_gpu_parity.py::test_fb_batch_gradient_fastlin_precision: that tier takes the window average as the
 exact mean where the oracle rounds it to float, which moves the labelled path's score by a few 1e-8 at any batch size);
-posteriors 1e-9 / 1e-6 / 1e-5 absolute (tests/test_gpu_posteriors.py); best paths, alignments and pruned arcs bit for bit.  Position must not matter: all copies of a base utterance agree with its
+posteriors 1e-9 / 1e-6 / 1e-5 absolute (tests/test_gpu_posteriors.py; transcript scoring against form 1 of tests/transcript_ref.py at the
+same bounds, tests/test_gpu_transcript.py); best paths, alignments and pruned arcs bit for bit.  Position must not matter: all copies of a base utterance agree with its
 first copy bit for bit where the path is deterministic per utterance (EXACT scalars, every decode output) and within 1e-12
 relative on the FAST tiers (the cross-chunking bound of tests/test_gpu_parity.py:516); each test prints whether the FAST
 tiers held bit for bit too.  A second fb_batch under the tiny scratch budget of the existing chunked tests (1 << 16) must
@@ -34,12 +35,16 @@ import latprune_ref as lr
 import orc
 import post_ref
 import scrf_amd
+import transcript_ref as tref
 from big_batch import EXACT, FAST, FAST32, FASTLIN, PREC_NAME
 
 pytestmark = pytest.mark.gpu
 
 ONE_CHUNK = 96 << 30      # scratch budget (only what a chunk needs is allocated)
 TINY = 1 << 16            # tests/test_gpu_parity.py::test_chunking_is_invisible
+SMALL_CELLS = 1 << 30     # transcript scoring on 1100-frame utterances: the cells of one utterance take 18 MB and a workgroup per
+                          # utterance walks its frames one after the other, so a chunk per utterance would run 510 sweeps
+                          # back to back; this budget holds a few dozen utterances per chunk
 TINY_FUSED = 1 << 21      # the fused path's count slabs alone pass 1 << 16: the first rung of its ladder in
                           # tests/test_gpu_chunk_plan.py that holds more than one (short) utterance per chunk
 GRAD_TOL = {EXACT: 1e-9, FAST: 1e-9, FASTLIN: 1e-6, FAST32: 1e-5}
@@ -230,6 +235,47 @@ def check_align(what, t, ref, eng, b, labs, chunks=1):
         assert [int(x) for x in al[u]] == want_l and np.float32(cost[u]).tobytes() == np.float32(want_c).tobytes(), (what, i)
 
 
+def check_transcript(what, t, ref, eng, b, transcripts, prec, chunks=1):
+    """every copy scored against its transcript (SCRF_ALIGN_ONE): equal to the first copy's bit for bit (zx, which the free
+    recursion supplies, and logp within the position bound on the FAST tiers), the first copy's equal to form 1 of
+    tests/transcript_ref.py on the oracle's scores within the tier's bound; returns the output"""
+    c0, k0, r0 = eng.transcript_stats()
+    out = eng.transcript_batch(b, transcripts, scrf_amd.ALIGN_ONE)
+    c1, k1, r1 = eng.transcript_stats()
+    n, k = k1 - k0, len(t.counts)
+    off = t.frame_off()
+    same_a, _ = bb.copies_vs_first(out["log_num"], t.base, k)
+    same_f, _ = bb.blocks_vs_first(out["frame_flat"], off, t.base, k)
+    same_e, _ = bb.blocks_vs_first(out["end_flat"], off, t.base, k)
+    same_z, rel_z = bb.copies_vs_first(out["zx"], t.base, k)
+    same_p, rel_p = bb.copies_vs_first(out["logp"], t.base, k)
+    dev = 0.0
+    for i in range(k):
+        u = int(t.first[i])
+        r = tref.dp(tref.case_scores(ref.case, i), transcripts[u], scrf_amd.ALIGN_ONE)
+        zx = ref.posteriors()[i][3]
+        T = r.frame_post.shape[0]
+        devs = [abs(out["zx"][u] - zx) / max(1.0, abs(zx)), abs(out["log_num"][u] - r.A) / max(1.0, abs(r.A)),
+                abs(out["logp"][u] - (r.A - zx)) / max(1.0, abs(r.A - zx)), np.abs(out["frame"][u] - r.frame_post).max(),
+                np.abs(out["end"][u] - r.end_post).max(), np.abs(out["frame"][u].sum(axis=1) - 1.0).max(), abs(out["end"][u][T - 1] - 1.0)]
+        assert np.isfinite(r.A) and max(devs) <= POST_TOL[prec], (what, i, devs)
+        dev = max(dev, max(devs))
+    print("%s transcript_batch %s: %d chunk(s), redone %d, vs form 1 %.2e (bound %.0e); copies vs first copy: log_num %s, frame %s, end %s, Zx %s (%.1e), logp %s (%.1e)"
+          % (what, PREC_NAME[prec], n, r1 - r0, dev, POST_TOL[prec], same_a, same_f, same_e, same_z, rel_z, same_p, rel_p))
+    assert c1 == c0 + 1 and r1 == r0, (what, c1 - c0, r1 - r0)
+    assert (n > -chunks) if chunks < 0 else (n == chunks), (what, n)
+    assert same_a and same_f and same_e, what
+    if prec == EXACT:
+        assert same_z and same_p, what
+    else:
+        assert rel_z <= POSITION_TOL and rel_p <= POSITION_TOL, (what, rel_z, rel_p)
+    return out
+
+
+def best_path_phones(labs, L):
+    return scrf_amd.RaggedLabels((np.asarray(labs.flat) % L).astype(np.uint32), labs.off)
+
+
 def check_pruned(what, t, ref, eng, b, beam, chunks=1, fetch_all=True):
     s0 = eng.lattice_prune_stats()[1]
     off, best = eng.lattice_prune_batch(b, beam)
@@ -292,6 +338,7 @@ def test_general_path_with_scores_and_windows_past_4_gib(refs, monkeypatch):
     try:
         labs, _ = check_viterbi("general", t, ref, eng, b)
         check_align("general", t, ref, eng, b, labs)
+        check_transcript("general", t, ref, eng, b, best_path_phones(labs, ref.case.ocfg.num_labs), EXACT)
     finally:
         b.close(); eng.close()
 
@@ -346,6 +393,30 @@ def test_kept_arc_array_past_4_gib(refs):
         b.close(); eng.close()
 
 
+def test_transcript_cells_past_4_gib(refs):
+    """L = 2, D = 2, 510 utterances of 1100 / 1090 frames with transcripts of 1030 / 1020 phones: aB and bE, [sum T K] fp64 each,
+    are 4.58e9 bytes (1.07 x 2^32) apiece in one chunk, every workgroup strides 1024 threads over its positions, and the
+    cells of the last utterances sit past 2^32 bytes from the chunk's first.  Then the same call under a budget of a tenth of
+    that (SMALL_CELLS): several chunks, the same bytes."""
+    ref, t = tiled_of(refs, "transcript")
+    require_memory("transcript", bb.need_bytes("transcript"))
+    phones = bb.transcript_phones("transcript")
+    ts = [phones[i] for i in t.base]
+    keys = ("log_num", "zx", "logp", "frame_flat", "end_flat")
+    eng = t.engine(FAST, ONE_CHUNK); b = t.batch(eng, with_labels=False)
+    try:
+        one = check_transcript("transcript", t, ref, eng, b, ts, FAST)
+    finally:
+        b.close(); eng.close()
+    eng = t.engine(FAST, SMALL_CELLS); b = t.batch(eng, with_labels=False)
+    try:
+        many = check_transcript("transcript under %d bytes of scratch" % SMALL_CELLS, t, ref, eng, b, ts, FAST, chunks=-4)
+        for k in keys:
+            assert np.array_equal(many[k].view(np.uint64), one[k].view(np.uint64)), k
+    finally:
+        b.close(); eng.close()
+
+
 # ---- axis B: more utterances than the chunk caps ----------------------------------------------------------------------
 def many_of(refs, name):
     ref = refs("many_" + name)
@@ -372,6 +443,7 @@ def test_70000_utterances_decode_outputs(name, refs, monkeypatch):
             if fast_decode == "1":
                 continue
             check_align(what, t, ref, eng, b, labs, chunks=2)
+            check_transcript(what, t, ref, eng, b, best_path_phones(labs, ref.case.ocfg.num_labs), EXACT, chunks=2)
             check_posteriors(what, t, ref, eng, b, EXACT, chunks=2)
             check_pruned(what, t, ref, eng, b, 2.0, chunks=2)
         finally:

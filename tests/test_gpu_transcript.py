@@ -15,6 +15,7 @@ import scrf_amd
 import sparse_ref as sr
 import transcript_ref as tr
 from cases import Case
+from gpu_checks import all_devs
 from scrf_amd import PREC_EXACT as EXACT, PREC_FAST as FAST, PREC_FAST32 as FAST32, PREC_FASTLIN as FASTLIN
 from spread_ladder import wide_spread_case
 
@@ -173,13 +174,14 @@ def test_every_output_equals_the_reference(si, prec):
 
 
 @pytest.mark.parametrize("prec", [FASTLIN, FAST32])
-@pytest.mark.parametrize("si", [1, 3])
+@pytest.mark.parametrize("si", range(len(SHAPES)))
 def test_the_other_tiers(si, prec):
+    """every shape and every transcript set of the EXACT / FAST sweep above, at the tier's bound"""
     c = case(si, precision=prec)
     eng = c.engine(); b = c.batch(eng, with_labels=False)
     dev = 0.0
     for mode in MODES:
-        for name, ts in transcript_sets(si, mode)[:1] + [("viterbi", viterbi_transcript(eng, b, c.L, mode))]:
+        for name, ts in transcript_sets(si, mode) + [("viterbi", viterbi_transcript(eng, b, c.L, mode))]:
             _, d = check_against_reference(si, eng, b, ts, mode, TOL[prec], what="shape %d %s mode %d %s" % (si, NAME[prec], mode, name))
             dev = max(dev, d)
     print("shape %d %s: max deviation %.3e" % (si, NAME[prec], dev))
@@ -278,16 +280,6 @@ def test_chunked_runs_equal_the_one_chunk_run_and_repeat_bit_for_bit(prec):
             assert np.array_equal(bits(o3[k]), bits(on[k])), (mode, k)
     assert e1.transcript_stats() == (2, 2, 0)
     b1.close(); e1.close(); bn.close(); en.close()
-
-
-def all_devs(out, u, r, zx, labs):
-    """every output of utterance u (a transcript that fits) against a reference Result and the free log-partition"""
-    T = r.frame_post.shape[0]
-    return [abs(out["zx"][u] - zx) / max(1.0, abs(zx)), abs(out["log_num"][u] - r.A) / max(1.0, abs(r.A)),
-            abs(out["logp"][u] - (r.A - zx)) / max(1.0, abs(r.A - zx)),
-            np.abs(out["frame"][u] - r.frame_post).max(), np.abs(out["end"][u] - r.end_post).max(),
-            np.abs(out["frame"][u].sum(axis=1) - 1.0).max(), abs(out["end"][u][T - 1] - 1.0),
-            np.abs(out["segments"][u] - r.queries(labs)).max()]
 
 
 def test_a_transcript_the_linear_domain_loses_comes_back_from_the_log_domain():

@@ -45,6 +45,18 @@ class Scores:
         return self.S[orc.seg_base(t, self.D) + d - 1, lab]
 
 
+def linear_view(w, float_smax=False):
+    """the Scores of w as the linear-domain score stage leaves them and tr_score reads them back: per row
+    smax + log(exp(S - smax)), -inf where exp gives 0; M untouched.  smax is the fp64 row maximum (k_exp_rows, k_add_p_exp)
+    or, float_smax, the row maximum rounded to float (the fused score kernel)."""
+    smax = w.S.max(axis=1, keepdims=True)
+    if float_smax:
+        smax = smax.astype(np.float32).astype(np.float64)
+    with np.errstate(divide="ignore", under="ignore"):
+        S = smax + np.log(np.exp(w.S - smax))
+    return Scores(S, w.M, w.T, w.L, w.D, w.frame_model)
+
+
 class Result:
     def __init__(self, w, phones, A, g):
         T, L, D = w.T, w.L, w.D
