@@ -138,6 +138,12 @@ struct scrf_engine_s {
   double* d_pack = nullptr;   // [L * nsf + 8]: the state weights of every label + the 8 scalars, one small message
   void* d_rtab = nullptr;       // k_tile_tables: row records / row bases / rowmap of a steady-state score tile
   size_t rtab_bytes = 0;
+  // the tables depend on (D, TB, la) alone: launched when that key changes or the buffer moves, on rtab_stream;
+  // a call on another stream waits for ev_rtab
+  uint32_t rtab_key[3] = {0, 0, 0};
+  bool rtab_valid = false;
+  hipStream_t rtab_stream = nullptr;
+  hipEvent_t ev_rtab = nullptr;
   double* d_dtab = nullptr;     // k_dur_table: duration weight + bias per output block, for the fused score kernel
   double* d_sl_tab = nullptr;   // STDSEG, bias-only transitions: E, E^T (nLabs^2 each) and max M (scrf_stdseg_lin.hip)
   bool frame_mass = false;   // posterior-mass self-checks with the frame model's bounds (scrf_set_frame_mass_check)
@@ -414,6 +420,7 @@ extern "C" int scrf_create(const scrf_config* cfg, scrf_handle* out) {
   CRCHK(hipStreamCreateWithFlags(&h->up_stream, hipStreamNonBlocking));
   CRCHK(hipEventCreateWithFlags(&h->ev_fork, hipEventDisableTiming));
   CRCHK(hipEventCreateWithFlags(&h->ev_join, hipEventDisableTiming));
+  CRCHK(hipEventCreateWithFlags(&h->ev_rtab, hipEventDisableTiming));
   CRCHK(hipMemsetAsync(h->d_lambda, 0, nb, h->stream));
   CRCHK(hipMemsetAsync(h->d_lambda_acc, 0, nb, h->stream));
   CRCHK(hipMemsetAsync(h->d_gsa, 0, nb, h->stream));
@@ -457,6 +464,7 @@ extern "C" int scrf_destroy(scrf_handle h) {
   for (int i = 0; i < 8; i++) if (h->pool_ev[i]) hipEventDestroy(h->pool_ev[i]);
   if (h->ev_fork) hipEventDestroy(h->ev_fork);
   if (h->ev_join) hipEventDestroy(h->ev_join);
+  if (h->ev_rtab) hipEventDestroy(h->ev_rtab);
   hipFree(h->dec_lab); hipFree(h->dec_n); hipFree(h->dec_cost);
   hipFree(h->al_ph); hipFree(h->al_off);
   hipFree(h->tr_inv);
@@ -1450,11 +1458,18 @@ static int run_scores(scrf_handle h, scrf_batch b, uint32_t u0, uint32_t u1, Chu
       fa.dtab = h->d_dtab;
       const size_t nb = fused_tile_table_bytes(l.D, fa.TB);
       if (nb > h->rtab_bytes) {
-        hipFree(h->d_rtab); h->d_rtab = nullptr; h->rtab_bytes = 0;
+        hipFree(h->d_rtab); h->d_rtab = nullptr; h->rtab_bytes = 0; h->rtab_valid = false;
         HIPCHK(h, hipMalloc(&h->d_rtab, nb));
         h->rtab_bytes = nb;
       }
-      launch_tile_tables(cb.st, l.D, fa.TB, (cb.la && !cb.Wn) ? 1 : 0, h->d_rtab);
+      const uint32_t key[3] = {l.D, fa.TB, (cb.la && !cb.Wn) ? 1u : 0u};
+      if (!h->rtab_valid || memcmp(key, h->rtab_key, sizeof(key)) != 0) {
+        launch_tile_tables(cb.st, key[0], key[1], (int)key[2], h->d_rtab);
+        HIPCHK(h, hipEventRecord(h->ev_rtab, cb.st));
+        memcpy(h->rtab_key, key, sizeof(key));
+        h->rtab_valid = true;
+        h->rtab_stream = cb.st;
+      } else if (cb.st != h->rtab_stream) HIPCHK(h, hipStreamWaitEvent(cb.st, h->ev_rtab, 0));
       if (h->kn.rtab) fa.rtab = h->d_rtab;
       fa.dma = h->kn.scores_dma ? 1 : 0;
     }
@@ -1562,7 +1577,11 @@ static int run_scores(scrf_handle h, scrf_batch b, uint32_t u0, uint32_t u1, Chu
 // forward + backward (+ posteriors when `post`): wavefront-per-utterance kernels for L <= 64,
 // the workgroup-per-utterance kernel otherwise.  Leaves R = Y - gamma in cb.AD (post) or
 // alpha-with-duration (no post), alpha in cb.alpha, beta in cb.beta (wave path or nd.beta).
-static int run_dp(scrf_handle h, scrf_batch b, uint32_t u0, uint32_t u1, ChunkBufs& cb, bool post, uint32_t* nl_out, bool ponly = false) {
+// side_checks: the chunk's count phase will use the engine's second stream (fb_run), so the linear-domain path's check
+// kernels go there right behind the posterior walk -- and, with status_too (last chunk), the batch's status copy.
+static int queue_status(scrf_handle h, scrf_batch b, hipStream_t st);
+static int run_dp(scrf_handle h, scrf_batch b, uint32_t u0, uint32_t u1, ChunkBufs& cb, bool post, uint32_t* nl_out, bool ponly = false,
+                  bool side_checks = false, bool status_too = false) {
   const ScrfLayout& l = h->lay;
   const uint64_t nutt = u1 - u0, nfr = b->frame_off[u1] - b->frame_off[u0];
   // (only the posterior-mass self-checks look at it in the recursion kernels)
@@ -1616,14 +1635,28 @@ static int run_dp(scrf_handle h, scrf_batch b, uint32_t u0, uint32_t u1, ChunkBu
         KT_RUN("k_post_lin", cb.st, launch_post_lin(cb.st, l, bv, b->d_frame_u, u0, nfr, b->d_next_lab, cb.s_true, cb.M, cb.m_per_frame, cb.S,
                         cb.smax, cb.dl, b->d_zx, cb.numer_f, b->d_status, cb.mass_s));
       }
+      // Nothing the count kernel reads comes from the three kernels below (it takes R, the frames and the tile list):
+      // with side_checks they leave the main stream, which goes from the posterior walk straight to the count kernel.
+      // The second stream keeps their order, and what they write is read behind the join of the count phase
+      // (k_batch_sums: d_numer; k_commit: the latch) or by that stream's own k_atb (the rescaled gsd).
+      hipStream_t ck = cb.st;
+      if (side_checks) {
+        HIPCHK(h, hipEventRecord(h->ev_fork, cb.st));
+        HIPCHK(h, hipStreamWaitEvent(h->stream2, h->ev_fork, 0));
+        ck = h->stream2;
+      }
       // the reference's posterior-mass self-checks (computeExpF :917-947), before sd / gsd are rescaled below
-      KT_RUN("k_mass_check", cb.st, launch_mass_check(cb.st, bv, b->d_frame_u, u0, nfr, l.L, frame_model, 1, cb.dl.a, cb.dl.ga, cb.dl.b, cb.dl.gb,
+      KT_RUN("k_mass_check", ck, launch_mass_check(ck, bv, b->d_frame_u, u0, nfr, l.L, frame_model, 1, cb.dl.a, cb.dl.ga, cb.dl.b, cb.dl.gb,
                         b->d_zx, cb.mass_s, b->d_status));
-      KT_RUN("k_numer_reduce", cb.st, launch_numer_reduce(cb.st, bv, u0, (uint32_t)nutt, cb.numer_f, b->d_numer));
+      KT_RUN("k_numer_reduce", ck, launch_numer_reduce(ck, bv, u0, (uint32_t)nutt, cb.numer_f, b->d_numer));
       // transition posteriors: with transition features the rescaled sd rows are needed as an array; with
       // bias-only transitions only their per-frame factor is, applied inside the A^T B contraction
-      if (l.use_tf) KT_RUN("k_xi_lin", cb.st, launch_xi_lin(cb.st, l, bv, b->d_frame_u, u0, nfr, cb.dl, b->d_zx));
-      else KT_RUN("k_xi_scale", cb.st, launch_xi_scale(cb.st, bv, b->d_frame_u, u0, nfr, cb.dl, b->d_zx));
+      if (l.use_tf) KT_RUN("k_xi_lin", ck, launch_xi_lin(ck, l, bv, b->d_frame_u, u0, nfr, cb.dl, b->d_zx));
+      else KT_RUN("k_xi_scale", ck, launch_xi_scale(ck, bv, b->d_frame_u, u0, nfr, cb.dl, b->d_zx));
+      if (side_checks && status_too) {   // every status of the batch is final behind k_mass_check
+        int rc = queue_status(h, b, ck);
+        if (rc != SCRF_OK) return rc;
+      }
       nl += 5;
       if (l.use_tf) {
         KT_RUN("k_xi_full", cb.st, launch_xi_full(cb.st, l, bv, u0, u1, nfr, b->d_next_lab, cb.fA, cb.fB, cb.E, cb.msh, cb.XI));
@@ -1714,12 +1747,13 @@ static const char* status_text(int code) {
                                     : "overflow / NaN / log of zero in the recursion, or posterior-mass check failed";
 }
 
-static int queue_status(scrf_handle h, scrf_batch b) {
-  hipLaunchKernelGGL(k_latch_status, dim3((b->U + 255) / 256), dim3(256), 0, h->stream, b->d_status, b->U, h->d_latch);
-  HIPCHK(h, hipMemcpyAsync(h->h_latch, h->d_latch, sizeof(int) * 2, hipMemcpyDeviceToHost, h->stream));
-  HIPCHK(h, hipEventRecord(h->ev_status, h->stream));
+static int queue_status(scrf_handle h, scrf_batch b, hipStream_t st) {
+  hipLaunchKernelGGL(k_latch_status, dim3((b->U + 255) / 256), dim3(256), 0, st, b->d_status, b->U, h->d_latch);
+  HIPCHK(h, hipMemcpyAsync(h->h_latch, h->d_latch, sizeof(int) * 2, hipMemcpyDeviceToHost, st));
+  HIPCHK(h, hipEventRecord(h->ev_status, st));
   return SCRF_OK;
 }
+static int queue_status(scrf_handle h, scrf_batch b) { return queue_status(h, b, h->stream); }
 
 // ---------------------------------------------------------------------------------------------
 // STDSEG (duration-labelled, scrf_stdseg.hip): its own small pipeline -- windows, scores, workgroup recursion,
@@ -2031,16 +2065,24 @@ static int fb_run(scrf_handle h, scrf_batch b, int latch[2], bool* used_lin) {
     const uint64_t nutt = u1 - u0, nfr = b->frame_off[u1] - b->frame_off[u0], nseg = b->seg_off[u1] - b->seg_off[u0];
     rc = run_scores(h, b, u0, u1, cb, fast, f32);
     if (rc != SCRF_OK) return rc;
+    // all-reduce / compute overlap (fused call only, below): it waits for the status on the host, on the main stream
+    const bool ov = h->overlap_comm && h->kn.comm_overlap && two_block_reduce(h) && !use2 && !h->timing && !sparse(h);
+    // Side stream: whether part of this chunk's count work will run on the engine's second stream (the count phase
+    // below) is known here, and then the recursion's check kernels and the status copy go there as well.  These are
+    // the conditions under which run_dp's linear-domain fused branch runs (it sets cb.z_ready) and the count phase can
+    // hand k_ztf and k_atb over.
+    const bool side_pre = h->kn.side && !use2 && !h->timing && !ov && cb.fused && cb.lin && cb.wave && !l.use_tf && !segtrans(h) &&
+                          pframe_supported(b->recipe[0].in_width) && cb.expf_plan.ws;
     {
       PhaseTimer tm(h, PH_FB, cb.st);
       uint32_t nl = 0;
-      rc = run_dp(h, b, u0, u1, cb, true, &nl);
+      rc = run_dp(h, b, u0, u1, cb, true, &nl, false, side_pre, ci + 1 == n_chunks);
       if (rc != SCRF_OK) return rc;
       tm.stop(nl);
     }
     // every per-utterance status of the batch is final once the last chunk's posterior kernels are queued:
-    // its copy to the host travels under the expected-count kernels
-    if (!use2 && ci + 1 == n_chunks) {
+    // its copy to the host travels under the expected-count kernels (side_pre: run_dp queued it on the second stream)
+    if (!use2 && !side_pre && ci + 1 == n_chunks) {
       rc = queue_status(h, b);
       if (rc != SCRF_OK) return rc;
     }
@@ -2048,7 +2090,6 @@ static int fb_run(scrf_handle h, scrf_batch b, int latch[2], bool* used_lin) {
     // are committed and their all-reduce goes to the second stream, under the state contraction.  A NUMERIC failure of
     // the recursion is retried with the log-domain kernels by the caller: that has to be known BEFORE a collective is
     // issued (the peers issue theirs exactly once), so the host waits for the status here.
-    const bool ov = h->overlap_comm && h->kn.comm_overlap && two_block_reduce(h) && !use2 && !h->timing && !sparse(h);
     bool trans_done = false;   // the transition counts of this chunk are already in the staged gradient
     if (ov) {
       if (ci + 1 == n_chunks) {
@@ -2086,11 +2127,9 @@ static int fb_run(scrf_handle h, scrf_batch b, int latch[2], bool* used_lin) {
         // k_expf_fused_ws, whose one workgroup per CU leaves 80 registers per SIMD lane and the wave slots for a narrow
         // k_ztf (one output tile per wavefront).  The two sides add into disjoint weights; the streams join before the
         // commit.  Off while kernels are timed one by one (scrf_enable_timing) and with SCRF_SIDE=0.
-        side = h->kn.side && !use2 && !h->timing && cb.z_ready && pframe_supported(W0) && !l.use_tf && !segtrans(h) && cb.wave &&
-               cb.expf_plan.ws;
+        // The second stream was forked behind k_post_z (run_dp) and holds the check kernels already: no second fork.
+        side = side_pre;   // (cb.z_ready holds: run_dp took the branch that forks)
         if (side) {
-          HIPCHK(h, hipEventRecord(h->ev_fork, cb.st));
-          HIPCHK(h, hipStreamWaitEvent(h->stream2, h->ev_fork, 0));
           launch_ztf(h->stream2, cb.Z, (cb.la ? 6 : 5) * l.L, b->d_frames[0] + b->frame_off[u0] * W0, W0, nfr, cb.rpc_l, cb.nch_l, cb.slab_l, 1);
           launch_reduce_slabs(h->stream2, cb.slab_l, cb.nch_l, (cb.la ? 6 : 5) * l.L, l, spec_samples(W0), cb.grad);
           launch_atb(h->stream2, l, cb.fA, cb.fB, nfr, cb.rpc_atb, cb.nch_atb, cb.slab_atb, h->d_m0, cb.grad, cb.lin ? cb.dl.gsd : nullptr);

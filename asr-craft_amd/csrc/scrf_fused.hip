@@ -2042,6 +2042,14 @@ __global__ __launch_bounds__(FE_NT, 2) void k_expf_fused(ScrfFusedArgs fa, ScrfL
 #ifndef FW_DMA_NT
 #define FW_DMA_NT 1     // cache policy of the R tile's LDS-DMA loads: 1 = nt (R is read once, as on the register path)
 #endif
+// Form of the producers' steady-state max | min scan ([max | min] launches that are not z-blocked), by tile height:
+// split = one statistic per wavefront, merged = both statistics of a (frame, column) from one set of loads.
+// FW_SCAN: 1 = split at 76 rows, merged at 100 (the measured choice, profiles/EXPERIMENTS.md); 0 = merged and 2 = split
+// at every height (A/B builds)
+#ifndef FW_SCAN
+#define FW_SCAN 1
+#endif
+constexpr bool fw_scan_split(int rows) { return FW_SCAN == 2 || (FW_SCAN == 1 && rows <= 76); }
 // The R tile's loads: fu_dma above, 16 bytes per lane, cache policy FW_DMA_NT
 __device__ __forceinline__ void fw_dma16(uint32_t voff, const void* sbase, uint32_t lds) { fu_dma<16, FW_DMA_NT>(voff, sbase, lds); }
 // ROWS = window rows per tile (76, or 100 where the two image pairs still fit 160 KB: fewer tiles, fewer barriers and
@@ -2191,6 +2199,21 @@ __device__ __forceinline__ void expf_fused_ws_body(const ScrfFusedArgs& fa, cons
         else fu_scan_ext_full<DMAX, 0, xs>(v, o);
       };
       if (FU_ABL == 6) {
+      } else if (fw_scan_split(ROWS) && G0 == 1 && ngrp == 2 && full) {
+        // one statistic per wavefront: producers 0-1 take the maxima, 2-3 the minima, one task per lane and
+        // (frame, column).  A 76-row tile at W = 39 has 117 tasks per statistic -- 59 / 58 lanes of the two wavefronts,
+        // ONE pass of 25 loads + 25 v_max|v_min + 25 LDS stores each, where the merged form below issues 25 + 50 + 50
+        // on 30 lanes.  The values and their places in the image are the merged form's.  More than 128 tasks loop.
+        const uint32_t pw = wave - 4, half = (nfW + 1) >> 1, pl = ptid & 63;
+        const uint32_t lo = (pw & 1) ? half : 0u, hi = (pw & 1) ? nfW : half;
+        for (uint32_t i = lo + pl; i < hi; i += 64) {
+          const uint32_t tl = fu_div(i, mW), c = i - tl * W;
+          float v[DMAX];
+          fu_load_vals_full<DMAX>(gfr, (ft.t0 + tl - ft.f0) * W + c, W, v);
+          float* o = Xs + tl * (DMAX * xs) + c;
+          if (pw < 2) fu_scan_ext_full<DMAX, 1, xs>(v, o);
+          else fu_scan_ext_full<DMAX, 0, xs>(v, o + W);
+        }
       } else if (G0 == 1 && ngrp == 2 && full) {
         // max and min of a (frame, column) from ONE set of loads; the tile's nfr W tasks are dealt evenly to the four
         // producer wavefronts (a 100-row tile has 156 of them: 39 lanes of every wavefront, one pass each, instead of
