@@ -177,7 +177,7 @@ struct scrf_engine_s {
   // kept across calls; al_bp_off is the host image chunk_layout sizes a chunk's back pointers with
   uint32_t* al_ph = nullptr;
   uint64_t* al_off = nullptr;
-  uint64_t al_cap_ph = 0, al_cap_u = 0;
+  uint64_t al_cap_ph = 0, al_cap_off = 0;
   std::vector<uint64_t> al_bp_off;
   uint64_t n_al_calls = 0, n_al_chunks = 0, n_al_wave = 0, n_al_group = 0;   // calls; searches launched, and by which kernel
   // scrf_transcript_batch: the transcripts go into al_ph / al_off; tr_inv holds each transcript's positions
@@ -258,6 +258,12 @@ static int fail(scrf_handle h, int code, const char* fmt, ...) {
     if (e_ != hipSuccess)                                                                 \
       return fail(h, SCRF_ERR_HIP, "%s failed: %s (%s:%d)", #call, hipGetErrorString(e_), \
                   __FILE__, __LINE__);                                                    \
+  } while (0)
+// the same for a call that returns one of the engine's own codes (it has set the error text)
+#define RCCHK(...)                     \
+  do {                                 \
+    int rc_ = (__VA_ARGS__);           \
+    if (rc_ != SCRF_OK) return rc_;    \
   } while (0)
 
 static uint32_t window_width(const scrf_stream_recipe& r, uint32_t D) {
@@ -730,8 +736,7 @@ static int upload(scrf_handle h, Tp** d, const Tp* src, size_t n) {
   *d = nullptr;
   if (n == 0) n = 1;
   void* p = nullptr;
-  int rc = pool_alloc(h, sizeof(Tp) * n, &p);
-  if (rc != SCRF_OK) return rc;
+  RCCHK(pool_alloc(h, sizeof(Tp) * n, &p));
   *d = (Tp*)p;
   if (src) HIPCHK(h, hipMemcpyAsync(*d, src, sizeof(Tp) * n, hipMemcpyHostToDevice, upload_stream(h)));
   return SCRF_OK;
@@ -1104,11 +1109,25 @@ struct ChunkBufs {
 
 // ponly (scrf_posteriors_batch): the recursion of the training path without anything that needs labels or feeds the
 // gradient -- the linear-domain vectors (or alpha_dur / beta) and the per-frame state mass, no count buffers
-struct Need { bool fb, post, beta, vit; bool fused = false; bool vitfast = false; bool la = false; bool hybrid = false; bool ponly = false; bool plog = false; bool lat = false; bool align = false; bool trans = false; };
+struct Need {
+  bool fb = false, post = false, beta = false, vit = false;
+  bool fused = false, vitfast = false, la = false, hybrid = false;   // the batch's form (set_batch_form, decode_chunks)
+  bool ponly = false, plog = false, lat = false, align = false, trans = false;
+  // one constructor per kind of pass, so that no call site depends on the order of the fields
+  static Need scores() { return Need(); }                                              // windows and scores only
+  static Need recursion() { Need n; n.fb = n.beta = true; return n; }                  // + the log-domain node values (hooks)
+  static Need alpha_sum(bool on) { Need n; n.fb = on; return n; }                      // scores (+ Zx, for a normalised lattice)
+  static Need training() { Need n; n.fb = n.post = true; return n; }
+  static Need posterior(bool fast) { Need n = recursion(); n.ponly = true; n.plog = !fast; return n; }
+  static Need transcript(bool fast) { Need n = posterior(fast); n.trans = true; return n; }
+  static Need viterbi() { Need n; n.vit = true; return n; }
+  static Need lattice() { Need n; n.lat = true; return n; }
+  static Need alignment() { Need n; n.align = true; return n; }
+};
 // trans (scrf_transcript_batch): two doubles per (frame, transcript position) cell of the chunk
 // align (scrf_align_batch): the back pointers of the chunk's (frame, transcript position) cells
 // lat (scrf_lattice_prune_batch): four distance arrays over the chunk's frames and the node counts / offsets
-// plog: ponly through the log-domain recursion (SCRF_PREC_EXACT)
+// plog: ponly through the log-domain recursion (SCRF_PREC_EXACT: no FAST precision)
 static bool need_lin(const Need& nd) { return nd.post || (nd.ponly && !nd.plog); }
 
 // entries the decode screen may list per chunk before the chunk falls back to the EXACT path
@@ -1323,8 +1342,7 @@ static uint32_t plan_chunk(scrf_handle h, scrf_batch b, uint32_t u0, const Need&
 }
 
 static int carve(scrf_handle h, scrf_batch b, uint32_t u0, uint32_t u1, const Need& nd, ChunkBufs* cb, int lane = 0) {
-  int rc = ensure_scratch(h, chunk_size(h, b, u0, u1, nd, cb), lane);
-  if (rc != SCRF_OK) return rc;
+  RCCHK(ensure_scratch(h, chunk_size(h, b, u0, u1, nd, cb), lane));
   Arena a{lane ? h->scratch2 : h->scratch, lane ? h->scratch2_cap : h->scratch_cap, 0};
   cb->st = lane ? h->stream2 : h->stream;
   cb->grad = lane ? h->d_grad2 : h->d_grad;
@@ -1474,14 +1492,12 @@ static int run_scores(scrf_handle h, scrf_batch b, uint32_t u0, uint32_t u1, Chu
       fa.dma = h->kn.scores_dma ? 1 : 0;
     }
     // per-frame projections of the five sampled blocks, then the dense part + gather
-    if (pframe_supported(W0)) {
+    if (pframe_supported(W0))
       KT_RUN("k_pframe", cb.st, launch_pframe(cb.st, b->d_frames[0] + b->frame_off[u0] * W0, W0, nfr, h->d_lambda, l, (cb.la ? 6 : 5) * l.L, cb.P));
-      if (cb.la) KT_RUN("k_avg_prefix", cb.st, launch_avg_prefix(cb.st, bv, u0, u1 - u0, l.L, cb.P));
-    } else {
+    else
       KT_RUN("k_scores_mfma(samples)", cb.st, launch_scores_mfma(cb.st, h->kn, b->d_frames[0] + b->frame_off[u0] * W0, W0, nullptr, nfr, h->d_lambda, l,
                          spec_samples(W0), (cb.la ? 6 : 5) * l.L, cb.P));
-      if (cb.la) KT_RUN("k_avg_prefix", cb.st, launch_avg_prefix(cb.st, bv, u0, u1 - u0, l.L, cb.P));
-    }
+    if (cb.la) KT_RUN("k_avg_prefix", cb.st, launch_avg_prefix(cb.st, bv, u0, u1 - u0, l.L, cb.P));
     if (cb.Wn) {
       // decode: float arc weights + the rounding screen
       launch_state_l1(cb.st, h->d_lambda, l, h->d_w1);
@@ -1574,118 +1590,173 @@ static int run_scores(scrf_handle h, scrf_batch b, uint32_t u0, uint32_t u1, Chu
   return SCRF_OK;
 }
 
-// forward + backward (+ posteriors when `post`): wavefront-per-utterance kernels for L <= 64,
-// the workgroup-per-utterance kernel otherwise.  Leaves R = Y - gamma in cb.AD (post) or
-// alpha-with-duration (no post), alpha in cb.alpha, beta in cb.beta (wave path or nd.beta).
-// side_checks: the chunk's count phase will use the engine's second stream (fb_run), so the linear-domain path's check
-// kernels go there right behind the posterior walk -- and, with status_too (last chunk), the batch's status copy.
+// the longest utterance of chunk [u0, u1): a launch of few utterances splits each into segments of frames
+static uint32_t longest_utt(scrf_batch b, uint32_t u0, uint32_t u1) { return *std::max_element(b->T.begin() + u0, b->T.begin() + u1); }
+
+// carve + scores: the head of every chunk.  SCORE_EXACT: the hooks and the decode paths (reference-order scores, sparse
+// maps re-lay lambda per chunk); SCORE_PASS: a training or label-free pass (the handle's precision; the pass re-laid lambda
+// once, before its first chunk)
+enum ScoreMode { SCORE_EXACT, SCORE_PASS };
+static bool prec_fast(scrf_handle h) { return h->cfg.train_precision >= SCRF_PREC_FAST; }
+static int prec_f32(scrf_handle h) { return h->cfg.train_precision == SCRF_PREC_FAST32; }
+static int score_chunk(scrf_handle h, scrf_batch b, uint32_t u0, uint32_t u1, const Need& nd, ChunkBufs* cb, ScoreMode mode = SCORE_EXACT, int lane = 0) {
+  RCCHK(carve(h, b, u0, u1, nd, cb, lane));
+  if (mode == SCORE_EXACT) return run_scores(h, b, u0, u1, *cb);
+  cb->lamT_ready = sparse(h);
+  return run_scores(h, b, u0, u1, *cb, prec_fast(h), prec_f32(h));
+}
+
+// Where a chunk of the training pass runs (fb_route): its lane; whether it is the batch's last; whether the transition block
+// is counted first and all-reduced early, under the state contraction (overlap); whether the engine's second stream takes
+// the recursion's check kernels, the status copy, k_ztf and k_atb (side).
+struct FbRoute { int lane = 0; bool two_lanes = false, last = false, overlap = false, side = false; };
+
+// What a caller wants of run_dp.  The hooks take the default: the log-domain node values of the chunk.
+struct DpOpts {
+  bool post = false;    // + posteriors, numerators and xi: leaves R = Y - gamma in cb.R
+  bool ponly = false;   // the recursion alone: the caller's posterior-output kernels take it from there
+  FbRoute route;        // training pass: side sends the linear-domain path's check kernels to the second stream
+  static DpOpts training(const FbRoute& rt) { DpOpts o; o.post = true; o.route = rt; return o; }
+  static DpOpts recursion_only() { DpOpts o; o.ponly = true; return o; }
+};
+
+// (only the posterior-mass self-checks look at it in the recursion kernels)
+static int frame_mass_model(scrf_handle h) { return h->cfg.model_type == SCRF_STDFRAME || h->frame_mass; }
+
 static int queue_status(scrf_handle h, scrf_batch b, hipStream_t st);
-static int run_dp(scrf_handle h, scrf_batch b, uint32_t u0, uint32_t u1, ChunkBufs& cb, bool post, uint32_t* nl_out, bool ponly = false,
-                  bool side_checks = false, bool status_too = false) {
+
+// STDSEG_NO_DUR: one transition matrix per window, its own workgroup recursion
+static int dp_segtrans(scrf_handle h, scrf_batch b, uint32_t u0, uint32_t u1, ChunkBufs& cb, bool post, uint32_t* nl) {
   const ScrfLayout& l = h->lay;
-  const uint64_t nutt = u1 - u0, nfr = b->frame_off[u1] - b->frame_off[u0];
-  // (only the posterior-mass self-checks look at it in the recursion kernels)
-  const int frame_model = h->cfg.model_type == SCRF_STDFRAME || h->frame_mass;
+  if (fb_segtrans_smem_bytes(l, fb_block_threads(l)) > 160 * 1024)
+    return fail(h, SCRF_ERR_INVALID, "labels x maximum duration = %u x %u is too large for the stdseg_no_dur recursion "
+                "(its three [D][L] rings must fit 160 KB of LDS)", l.L, l.D);
+  KT_RUN("k_fb_segtrans", cb.st, launch_fb_segtrans(cb.st, h->kn, l, b->view(), u0, u1 - u0, b->d_prev_lab, cb.S, cb.M, cb.AD, cb.alpha, cb.beta,
+                     post ? cb.XI : nullptr, b->d_numer, b->d_zx, b->d_status, post ? 1 : 0));
+  *nl += 1;
+  return SCRF_OK;
+}
+
+// the workgroup-per-utterance kernel: column-wise max-shifted log-sum-exp like the reference's LogMath
+static int dp_group(scrf_handle h, scrf_batch b, uint32_t u0, uint32_t u1, ChunkBufs& cb, bool post, uint32_t* nl) {
+  const ScrfLayout& l = h->lay;
+  const uint32_t nutt = u1 - u0;
+  if (fb_smem_bytes(l, fb_block_threads(l)) > 160 * 1024)
+    return fail(h, SCRF_ERR_INVALID, "labels x maximum duration = %u x %u is too large for the workgroup-per-utterance recursion "
+                "(its two [D][L] rings must fit 160 KB of LDS; the wavefront kernels cover L <= 256 with D <= 40)", l.L, l.D);
+  if (post && cb.xi_acc) HIPCHK(h, hipMemsetAsync(cb.xi_acc, 0, sizeof(double) * nutt * l.L * l.L, cb.st));
+  KT_RUN("k_fb", cb.st, launch_fb(cb.st, l, b->view(), u0, nutt, cb.S, cb.M, cb.m_per_frame, cb.AD, cb.alpha, cb.beta, post ? cb.XI : nullptr,
+            post ? cb.xi_acc : nullptr, b->d_numer, b->d_zx, b->d_status, post ? 1 : 0, frame_mass_model(h)));
+  *nl += 1;
+  return SCRF_OK;
+}
+
+// Behind the posterior walk of either wavefront recursion: the reference's posterior-mass self-checks (computeExpF :917-947),
+// the numerators and the xi factors on `ck`, then -- with transition features -- the full xi on the chunk's stream.  The two
+// recursions check different vectors and form their factors with different kernels: each passes its own launches.
+template <class MassCheck, class XiFactors>
+static uint32_t post_tail(scrf_handle h, scrf_batch b, uint32_t u0, uint32_t u1, ChunkBufs& cb, hipStream_t ck, MassCheck mass_check,
+                          XiFactors xi_factors) {
+  const ScrfLayout& l = h->lay;
+  const uint64_t nfr = b->frame_off[u1] - b->frame_off[u0];
+  KT_RUN("k_mass_check", ck, mass_check());
+  KT_RUN("k_numer_reduce", ck, launch_numer_reduce(ck, b->view(), u0, u1 - u0, cb.numer_f, b->d_numer));
+  xi_factors();
+  if (!l.use_tf) return 3;
+  KT_RUN("k_xi_full", cb.st, launch_xi_full(cb.st, l, b->view(), u0, u1, nfr, b->d_next_lab, cb.fA, cb.fB, cb.E, cb.msh, cb.XI));
+  return 4;
+}
+
+// the scaled linear-domain wavefront recursion (training and label-free passes)
+static int dp_wave_lin(scrf_handle h, scrf_batch b, uint32_t u0, uint32_t u1, ChunkBufs& cb, const DpOpts& o, uint32_t* nl) {
+  const ScrfLayout& l = h->lay;
+  const uint32_t nutt = u1 - u0;
+  const uint64_t nfr = b->frame_off[u1] - b->frame_off[u0], nseg = b->seg_off[u1] - b->seg_off[u0];
   ScrfBatchView bv = b->view();
-  uint32_t nl = 0;
-  if (segtrans(h)) {
-    if (fb_segtrans_smem_bytes(l, fb_block_threads(l)) > 160 * 1024)
-      return fail(h, SCRF_ERR_INVALID, "labels x maximum duration = %u x %u is too large for the stdseg_no_dur recursion "
-                  "(its three [D][L] rings must fit 160 KB of LDS)", l.L, l.D);
-    KT_RUN("k_fb_segtrans", cb.st, launch_fb_segtrans(cb.st, h->kn, l, bv, u0, (uint32_t)nutt, b->d_prev_lab, cb.S, cb.M, cb.AD, cb.alpha, cb.beta,
-                       post ? cb.XI : nullptr, b->d_numer, b->d_zx, b->d_status, post ? 1 : 0));
-    nl = 1;
-  } else if (!cb.wave) {
-    if (fb_smem_bytes(l, fb_block_threads(l)) > 160 * 1024)
-      return fail(h, SCRF_ERR_INVALID, "labels x maximum duration = %u x %u is too large for the workgroup-per-utterance recursion "
-                  "(its two [D][L] rings must fit 160 KB of LDS; the wavefront kernels cover L <= 256 with D <= 40)", l.L, l.D);
-    if (post && cb.xi_acc) HIPCHK(h, hipMemsetAsync(cb.xi_acc, 0, sizeof(double) * nutt * l.L * l.L, cb.st));
-    KT_RUN("k_fb", cb.st, launch_fb(cb.st, l, bv, u0, (uint32_t)nutt, cb.S, cb.M, cb.m_per_frame, cb.AD, cb.alpha, cb.beta, post ? cb.XI : nullptr,
-              post ? cb.xi_acc : nullptr, b->d_numer, b->d_zx, b->d_status, post ? 1 : 0, frame_model));
-    nl = 1;
+  if (!cb.es_ready) {
+    if (!o.ponly) KT_RUN("k_true_scores", cb.st, launch_true_scores(cb.st, l, bv, b->d_frame_u, u0, nfr, cb.S, cb.s_true));
+    KT_RUN("k_exp_rows", cb.st, launch_exp_rows(cb.st, cb.S, nseg, l.L, cb.smax));
+    *nl += o.ponly ? 1 : 2;
+  }
+  {
+    PhaseTimer tk(h, PH_K_DP, cb.st);
+    KT_RUN(l.L > 64 ? "k_dp_lin_mw" : "k_dp_lin", cb.st, launch_dp_lin(cb.st, h->kn, l, bv, u0, nutt, cb.S, cb.smax, cb.E, cb.ET, cb.msh, cb.m_per_frame, cb.dl,
+                    b->d_zx, b->d_status));
+    tk.stop(1);
+  }
+  *nl += 1;
+  if (o.ponly) return SCRF_OK;
+  if (cb.fused) {
+    // posterior pass and the per-frame sums of R in one walk (R is not read back for Z)
+    if (l.L > 64) HIPCHK(h, hipMemsetAsync(cb.mass_s, 0, sizeof(double) * nfr, cb.st));   // summed over the 64-output groups
+    const uint32_t t_max = longest_utt(b, u0, u1);
+    KT_RUN("k_post_z", cb.st, launch_post_z(cb.st, h->kn, l, bv, u0, nutt, b->d_next_lab, cb.s_true, cb.M, cb.m_per_frame, cb.S, cb.smax,
+                  cb.dl, b->d_zx, cb.numer_f, b->d_status, cb.Z, cb.mass_s, cb.la ? 1 : 0, t_max, nfr));
+    cb.z_ready = true;
   } else {
-    if (cb.m_per_frame) { KT_RUN("k_exp_m", cb.st, launch_exp_m(cb.st, h->kn, cb.M, l.L, nfr, cb.E, cb.ET, cb.msh)); nl++; }
-    if (cb.lin) {
-      const uint64_t nseg = b->seg_off[u1] - b->seg_off[u0];
-      if (!cb.es_ready) {
-        if (!ponly) KT_RUN("k_true_scores", cb.st, launch_true_scores(cb.st, l, bv, b->d_frame_u, u0, nfr, cb.S, cb.s_true));
-        KT_RUN("k_exp_rows", cb.st, launch_exp_rows(cb.st, cb.S, nseg, l.L, cb.smax));
-        nl += ponly ? 1 : 2;
-      }
-      {
-        PhaseTimer tk(h, PH_K_DP, cb.st);
-        KT_RUN(l.L > 64 ? "k_dp_lin_mw" : "k_dp_lin", cb.st, launch_dp_lin(cb.st, h->kn, l, bv, u0, (uint32_t)nutt, cb.S, cb.smax, cb.E, cb.ET, cb.msh, cb.m_per_frame, cb.dl,
-                      b->d_zx, b->d_status));
-        tk.stop(1);
-      }
-      if (ponly) {   // the caller's posterior-output kernels take it from here
-        if (nl_out) *nl_out = nl + 1;
-        HIPCHK(h, hipGetLastError());
-        return SCRF_OK;
-      }
-      if (cb.fused) {
-        // posterior pass and the per-frame sums of R in one walk (R is not read back for Z)
-        if (l.L > 64) HIPCHK(h, hipMemsetAsync(cb.mass_s, 0, sizeof(double) * nfr, cb.st));   // summed over the 64-output groups
-        uint32_t t_max = 0;   // the longest utterance of the chunk: a launch of few utterances splits each into segments
-        for (uint64_t u = u0; u < u1; u++) t_max = std::max(t_max, b->T[u]);
-        KT_RUN("k_post_z", cb.st, launch_post_z(cb.st, h->kn, l, bv, u0, (uint32_t)nutt, b->d_next_lab, cb.s_true, cb.M, cb.m_per_frame, cb.S, cb.smax,
-                      cb.dl, b->d_zx, cb.numer_f, b->d_status, cb.Z, cb.mass_s, cb.la ? 1 : 0, t_max, nfr));
-        cb.z_ready = true;
-      } else {
-        KT_RUN("k_post_lin", cb.st, launch_post_lin(cb.st, l, bv, b->d_frame_u, u0, nfr, b->d_next_lab, cb.s_true, cb.M, cb.m_per_frame, cb.S,
-                        cb.smax, cb.dl, b->d_zx, cb.numer_f, b->d_status, cb.mass_s));
-      }
-      // Nothing the count kernel reads comes from the three kernels below (it takes R, the frames and the tile list):
-      // with side_checks they leave the main stream, which goes from the posterior walk straight to the count kernel.
-      // The second stream keeps their order, and what they write is read behind the join of the count phase
-      // (k_batch_sums: d_numer; k_commit: the latch) or by that stream's own k_atb (the rescaled gsd).
-      hipStream_t ck = cb.st;
-      if (side_checks) {
-        HIPCHK(h, hipEventRecord(h->ev_fork, cb.st));
-        HIPCHK(h, hipStreamWaitEvent(h->stream2, h->ev_fork, 0));
-        ck = h->stream2;
-      }
-      // the reference's posterior-mass self-checks (computeExpF :917-947), before sd / gsd are rescaled below
-      KT_RUN("k_mass_check", ck, launch_mass_check(ck, bv, b->d_frame_u, u0, nfr, l.L, frame_model, 1, cb.dl.a, cb.dl.ga, cb.dl.b, cb.dl.gb,
-                        b->d_zx, cb.mass_s, b->d_status));
-      KT_RUN("k_numer_reduce", ck, launch_numer_reduce(ck, bv, u0, (uint32_t)nutt, cb.numer_f, b->d_numer));
-      // transition posteriors: with transition features the rescaled sd rows are needed as an array; with
-      // bias-only transitions only their per-frame factor is, applied inside the A^T B contraction
-      if (l.use_tf) KT_RUN("k_xi_lin", ck, launch_xi_lin(ck, l, bv, b->d_frame_u, u0, nfr, cb.dl, b->d_zx));
-      else KT_RUN("k_xi_scale", ck, launch_xi_scale(ck, bv, b->d_frame_u, u0, nfr, cb.dl, b->d_zx));
-      if (side_checks && status_too) {   // every status of the batch is final behind k_mass_check
-        int rc = queue_status(h, b, ck);
-        if (rc != SCRF_OK) return rc;
-      }
-      nl += 5;
-      if (l.use_tf) {
-        KT_RUN("k_xi_full", cb.st, launch_xi_full(cb.st, l, bv, u0, u1, nfr, b->d_next_lab, cb.fA, cb.fB, cb.E, cb.msh, cb.XI));
-        nl++;
-      }
-      if (nl_out) *nl_out = nl;
-      HIPCHK(h, hipGetLastError());
-      return SCRF_OK;
+    KT_RUN("k_post_lin", cb.st, launch_post_lin(cb.st, l, bv, b->d_frame_u, u0, nfr, b->d_next_lab, cb.s_true, cb.M, cb.m_per_frame, cb.S,
+                    cb.smax, cb.dl, b->d_zx, cb.numer_f, b->d_status, cb.mass_s));
+  }
+  // Nothing the count kernel reads comes from the check kernels (it takes R, the frames and the tile list): on a side
+  // route they leave the main stream, which goes from the posterior walk straight to the count kernel.  The second stream
+  // keeps their order, and what they write is read behind the join of the count phase (k_batch_sums: d_numer; k_commit:
+  // the latch) or by that stream's own k_atb (the rescaled gsd).
+  hipStream_t ck = cb.st;
+  if (o.route.side) {
+    HIPCHK(h, hipEventRecord(h->ev_fork, cb.st));
+    HIPCHK(h, hipStreamWaitEvent(h->stream2, h->ev_fork, 0));
+    ck = h->stream2;
+  }
+  *nl += 1 + post_tail(h, b, u0, u1, cb, ck,
+      [&] {   // before sd / gsd are rescaled below
+        launch_mass_check(ck, bv, b->d_frame_u, u0, nfr, l.L, frame_mass_model(h), 1, cb.dl.a, cb.dl.ga, cb.dl.b, cb.dl.gb, b->d_zx, cb.mass_s, b->d_status);
+      },
+      [&] {   // with transition features the rescaled sd rows are needed as an array; with bias-only transitions only their
+              // per-frame factor is, applied inside the A^T B contraction
+        if (l.use_tf) KT_RUN("k_xi_lin", ck, launch_xi_lin(ck, l, bv, b->d_frame_u, u0, nfr, cb.dl, b->d_zx));
+        else KT_RUN("k_xi_scale", ck, launch_xi_scale(ck, bv, b->d_frame_u, u0, nfr, cb.dl, b->d_zx));
+      });
+  // every status of the batch is final behind the last chunk's k_mass_check (a side route has no transition features: no k_xi_full)
+  if (o.route.side && o.route.last) return queue_status(h, b, ck);
+  return SCRF_OK;
+}
+
+// the log-domain wavefront recursion (hooks, SCRF_PREC_EXACT passes, training without the linear-domain kernels)
+static int dp_wave_log(scrf_handle h, scrf_batch b, uint32_t u0, uint32_t u1, ChunkBufs& cb, bool post, uint32_t* nl) {
+  const ScrfLayout& l = h->lay;
+  const uint32_t nutt = u1 - u0;
+  const uint64_t nfr = b->frame_off[u1] - b->frame_off[u0];
+  ScrfBatchView bv = b->view();
+  {
+    PhaseTimer tk(h, PH_K_DP, cb.st);
+    KT_RUN("k_dp_wave", cb.st, launch_dp_wave(cb.st, l, bv, u0, nutt, cb.S, cb.E, cb.ET, cb.msh, cb.m_per_frame, cb.AD, cb.alpha,
+                   cb.beta, cb.sd, b->d_zx, b->d_status));
+    tk.stop(1);
+  }
+  *nl += 1;
+  if (!post) return SCRF_OK;
+  KT_RUN("k_post_state", cb.st, launch_post_state(cb.st, l, bv, u0, u1, nfr, b->d_next_lab, cb.S, cb.M, cb.m_per_frame, cb.AD, cb.beta,
+                    b->d_zx, cb.numer_f, b->d_status, cb.mass_s));
+  *nl += 1 + post_tail(h, b, u0, u1, cb, cb.st,
+      [&] { launch_mass_check(cb.st, bv, b->d_frame_u, u0, nfr, l.L, frame_mass_model(h), 0, cb.alpha, nullptr, cb.beta, nullptr, b->d_zx, cb.mass_s, b->d_status); },
+      [&] { KT_RUN("k_xi_factors", cb.st, launch_xi_factors(cb.st, l, bv, u0, u1, nfr, cb.alpha, cb.sd, b->d_zx, cb.fA, cb.fB)); });
+  return SCRF_OK;
+}
+
+// forward + backward (+ posteriors with o.post) of chunk [u0, u1) by the recursion its carve chose: wavefront-per-utterance
+// kernels for L <= 64 (and the multi-wavefront linear-domain one up to 256), the workgroup-per-utterance kernel otherwise.
+// Leaves R = Y - gamma in cb.R (post) or alpha-with-duration in cb.AD (no post), alpha in cb.alpha, beta in cb.beta (wave
+// path or nd.beta).  *nl_out: the launches queued.
+static int run_dp(scrf_handle h, scrf_batch b, uint32_t u0, uint32_t u1, ChunkBufs& cb, const DpOpts& o, uint32_t* nl_out) {
+  uint32_t nl = 0;
+  if (segtrans(h)) RCCHK(dp_segtrans(h, b, u0, u1, cb, o.post, &nl));
+  else if (!cb.wave) RCCHK(dp_group(h, b, u0, u1, cb, o.post, &nl));
+  else {
+    if (cb.m_per_frame) {
+      KT_RUN("k_exp_m", cb.st, launch_exp_m(cb.st, h->kn, cb.M, h->lay.L, b->frame_off[u1] - b->frame_off[u0], cb.E, cb.ET, cb.msh));
+      nl++;
     }
-    {
-      PhaseTimer tk(h, PH_K_DP, cb.st);
-      KT_RUN("k_dp_wave", cb.st, launch_dp_wave(cb.st, l, bv, u0, (uint32_t)nutt, cb.S, cb.E, cb.ET, cb.msh, cb.m_per_frame, cb.AD, cb.alpha,
-                     cb.beta, cb.sd, b->d_zx, b->d_status));
-      tk.stop(1);
-    }
-    nl++;
-    if (post) {
-      KT_RUN("k_post_state", cb.st, launch_post_state(cb.st, l, bv, u0, u1, nfr, b->d_next_lab, cb.S, cb.M, cb.m_per_frame, cb.AD, cb.beta,
-                        b->d_zx, cb.numer_f, b->d_status, cb.mass_s));
-      KT_RUN("k_mass_check", cb.st, launch_mass_check(cb.st, bv, b->d_frame_u, u0, nfr, l.L, frame_model, 0, cb.alpha, nullptr, cb.beta, nullptr,
-                        b->d_zx, cb.mass_s, b->d_status));
-      KT_RUN("k_numer_reduce", cb.st, launch_numer_reduce(cb.st, bv, u0, (uint32_t)nutt, cb.numer_f, b->d_numer));
-      KT_RUN("k_xi_factors", cb.st, launch_xi_factors(cb.st, l, bv, u0, u1, nfr, cb.alpha, cb.sd, b->d_zx, cb.fA, cb.fB));
-      nl += 4;
-      if (l.use_tf) {
-        KT_RUN("k_xi_full", cb.st, launch_xi_full(cb.st, l, bv, u0, u1, nfr, b->d_next_lab, cb.fA, cb.fB, cb.E, cb.msh, cb.XI));
-        nl++;
-      }
-    }
+    RCCHK(cb.lin ? dp_wave_lin(h, b, u0, u1, cb, o, &nl) : dp_wave_log(h, b, u0, u1, cb, o.post, &nl));
   }
   if (nl_out) *nl_out = nl;
   HIPCHK(h, hipGetLastError());
@@ -1763,6 +1834,38 @@ static int queue_status(scrf_handle h, scrf_batch b) { return queue_status(h, b,
 static bool stdseg(scrf_handle h) { return h->cfg.model_type == SCRF_STDSEG; }
 static uint32_t stdseg_La(scrf_handle h) { return h->lay.L / h->lay.D; }
 
+// The small pipelines (STDSEG log-domain, STDSEG linear-domain, n-state) each have a layout function: one walk over an Arena
+// for sizing and carving, like chunk_layout.  What differs between them besides the layout is carried here, as it has always
+// been (tests/test_gpu_chunk_plan.py pins every cut): the bytes of slack a chunk's size adds and the most utterances a chunk
+// may hold (0: no cap).
+template <class Bufs>
+struct SmallPipe {
+  void (*layout)(scrf_handle, scrf_batch, uint32_t, uint32_t, bool, Arena&, Bufs*);
+  size_t slack;
+  uint32_t max_utts;
+  size_t chunk_size(scrf_handle h, scrf_batch b, uint32_t u0, uint32_t u1, bool post) const {
+    Arena m{nullptr, 0, 0};
+    Bufs sb;
+    layout(h, b, u0, u1, post, m, &sb);
+    return m.off + slack;
+  }
+  // carves the chunk on the engine's scratch and queues its window vectors (batches made from frames)
+  int begin_chunk(scrf_handle h, scrf_batch b, uint32_t u0, uint32_t u1, bool post, Bufs* sb) const {
+    RCCHK(ensure_scratch(h, chunk_size(h, b, u0, u1, post)));
+    Arena a{h->scratch, h->scratch_cap, 0};
+    layout(h, b, u0, u1, post, a, sb);
+    if (a.off > a.cap) return fail(h, SCRF_ERR_INVALID, "internal: scratch arena overflow");
+    if (b->mode == 1) launch_chunk_windows(h, b, u0, u1, h->stream, sb->X);
+    return SCRF_OK;
+  }
+  // largest u1 > u0 whose chunk fits the budget (always at least one utterance)
+  uint32_t plan(scrf_handle h, scrf_batch b, uint32_t u0, bool post) const {
+    uint32_t u1 = u0 + 1;
+    while (u1 < b->U && (!max_utts || u1 - u0 < max_utts) && chunk_size(h, b, u0, u1 + 1, post) <= h->cfg.scratch_bytes) u1++;
+    return u1;
+  }
+};
+
 struct StdsegBufs {
   float* X; uint32_t *row_t, *row_d, *row_u;
   double *S, *MX, *alpha, *beta, *G, *XI, *mass_s, *mass_t;
@@ -1782,12 +1885,7 @@ static void stdseg_layout(scrf_handle h, scrf_batch b, uint32_t u0, uint32_t u1,
     sb->mass_s = a.take<double>(nfr); sb->mass_t = a.take<double>(nfr);
   }
 }
-static size_t stdseg_chunk_size(scrf_handle h, scrf_batch b, uint32_t u0, uint32_t u1, bool post) {
-  Arena m{nullptr, 0, 0};
-  StdsegBufs sb;
-  stdseg_layout(h, b, u0, u1, post, m, &sb);
-  return m.off;
-}
+static const SmallPipe<StdsegBufs> stdseg_pipe = {stdseg_layout, 0, 0};   // no slack, no cap
 // ---- STDSEG, bias-only transitions, FAST precisions, training path: scrf_stdseg_lin.hip (not during a log-domain redo,
 // force_fb: that one runs k_stdseg_fb, the reference's order)
 static bool stdseg_lin(scrf_handle h) {
@@ -1803,7 +1901,7 @@ struct StdsegLinBufs {
   double *slab_s, *slab_t, *obs;   // state-count slabs (one duration at a time), transition slabs, observed transitions
   uint64_t rpc; uint32_t nch;
 };
-static void stdseg_lin_layout(scrf_handle h, scrf_batch b, uint32_t u0, uint32_t u1, Arena& a, StdsegLinBufs* sb) {
+static void stdseg_lin_layout(scrf_handle h, scrf_batch b, uint32_t u0, uint32_t u1, bool /*post: always*/, Arena& a, StdsegLinBufs* sb) {
   const ScrfLayout& l = h->lay;
   const uint32_t La = stdseg_La(h);
   const uint64_t nfr = b->frame_off[u1] - b->frame_off[u0], nseg = b->seg_off[u1] - b->seg_off[u0];
@@ -1820,26 +1918,16 @@ static void stdseg_lin_layout(scrf_handle h, scrf_batch b, uint32_t u0, uint32_t
   sb->slab_t = a.take<double>((size_t)sb->nch * l.L * l.L);
   sb->obs = a.take<double>((size_t)l.L * l.L);
 }
-static size_t stdseg_lin_chunk_size(scrf_handle h, scrf_batch b, uint32_t u0, uint32_t u1) {
-  Arena m{nullptr, 0, 0};
-  StdsegLinBufs sb;
-  stdseg_lin_layout(h, b, u0, u1, m, &sb);
-  return m.off + 4096;
-}
+static const SmallPipe<StdsegLinBufs> stdseg_lin_pipe = {stdseg_lin_layout, 4096, 32767};   // 4 KB of slack, at most 32,767 utterances
 static int stdseg_lin_run_chunk(scrf_handle h, scrf_batch b, uint32_t u0, uint32_t u1, double* grad) {
   const ScrfLayout& l = h->lay;
   const uint32_t La = stdseg_La(h);
   const uint64_t nfr = b->frame_off[u1] - b->frame_off[u0];
-  int rc = ensure_scratch(h, stdseg_lin_chunk_size(h, b, u0, u1));
-  if (rc != SCRF_OK) return rc;
-  Arena a{h->scratch, h->scratch_cap, 0};
   StdsegLinBufs sb;
-  stdseg_lin_layout(h, b, u0, u1, a, &sb);
-  if (a.off > a.cap) return fail(h, SCRF_ERR_INVALID, "internal: scratch arena overflow");
+  RCCHK(stdseg_lin_pipe.begin_chunk(h, b, u0, u1, true, &sb));
   ScrfBatchView bv = b->view();
   hipStream_t st = h->stream;
   const int f32 = h->cfg.train_precision == SCRF_PREC_FAST32;
-  if (b->mode == 1) launch_chunk_windows(h, b, u0, u1, st, sb.X);
   // the transition table and its exponential (once per call: lambda may have changed)
   double* E = h->d_sl_tab; double* ET = E + (size_t)l.L * l.L; double* mmax = ET + (size_t)l.L * l.L;
   launch_sl_tables(st, l, h->d_lambda, E, ET, mmax);
@@ -1877,15 +1965,10 @@ static int stdseg_run_chunk(scrf_handle h, scrf_batch b, uint32_t u0, uint32_t u
   const ScrfLayout& l = h->lay;
   const uint32_t La = stdseg_La(h);
   const uint64_t nfr = b->frame_off[u1] - b->frame_off[u0], nseg = b->seg_off[u1] - b->seg_off[u0];
-  int rc = ensure_scratch(h, stdseg_chunk_size(h, b, u0, u1, post));
-  if (rc != SCRF_OK) return rc;
-  Arena a{h->scratch, h->scratch_cap, 0};
   StdsegBufs sb;
-  stdseg_layout(h, b, u0, u1, post, a, &sb);
-  if (a.off > a.cap) return fail(h, SCRF_ERR_INVALID, "internal: scratch arena overflow");
+  RCCHK(stdseg_pipe.begin_chunk(h, b, u0, u1, post, &sb));
   ScrfBatchView bv = b->view();
   hipStream_t st = h->stream;
-  if (b->mode == 1) launch_chunk_windows(h, b, u0, u1, st, sb.X);
   launch_stdseg_rowinfo(st, bv, b->d_frame_u, u0, nfr, l.D, sb.row_t, sb.row_d, sb.row_u);
   KT_RUN("k_stdseg_scores", st, launch_stdseg_scores(st, l, La, sb.X, nseg, sb.row_t, sb.row_d, h->d_lambda, sb.S, sb.MX));
   KT_RUN("k_stdseg_fb", st, launch_stdseg_fb(st, l, La, bv, u0, u1 - u0, sb.S, sb.MX, sb.alpha, sb.beta, b->d_zx, b->d_status));
@@ -1899,15 +1982,6 @@ static int stdseg_run_chunk(scrf_handle h, scrf_batch b, uint32_t u0, uint32_t u
   HIPCHK(h, hipGetLastError());
   if (out) *out = sb;
   return SCRF_OK;
-}
-static uint32_t stdseg_plan_chunk(scrf_handle h, scrf_batch b, uint32_t u0, bool post) {
-  uint32_t u1 = u0 + 1;
-  if (post && stdseg_lin(h)) {
-    while (u1 < b->U && u1 - u0 < 32767 && stdseg_lin_chunk_size(h, b, u0, u1 + 1) <= h->cfg.scratch_bytes) u1++;
-    return u1;
-  }
-  while (u1 < b->U && stdseg_chunk_size(h, b, u0, u1 + 1, post) <= h->cfg.scratch_bytes) u1++;
-  return u1;
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -1935,24 +2009,14 @@ static void nstate_layout(scrf_handle h, scrf_batch b, uint32_t u0, uint32_t u1,
     nb->slab = a.take<double>((size_t)ns_expf_slices(nfr) * l.lambda_len);
   }
 }
-static size_t nstate_chunk_size(scrf_handle h, scrf_batch b, uint32_t u0, uint32_t u1, bool post) {
-  Arena m{nullptr, 0, 0};
-  NstateBufs nb;
-  nstate_layout(h, b, u0, u1, post, m, &nb);
-  return m.off;
-}
+static const SmallPipe<NstateBufs> nstate_pipe = {nstate_layout, 0, 0};   // no slack, no cap
 static int nstate_run_chunk(scrf_handle h, scrf_batch b, uint32_t u0, uint32_t u1, bool post, double* grad, NstateBufs* out) {
   const ScrfLayout& l = h->lay;
   const uint64_t nfr = b->frame_off[u1] - b->frame_off[u0];
-  int rc = ensure_scratch(h, nstate_chunk_size(h, b, u0, u1, post));
-  if (rc != SCRF_OK) return rc;
-  Arena a{h->scratch, h->scratch_cap, 0};
   NstateBufs nb;
-  nstate_layout(h, b, u0, u1, post, a, &nb);
-  if (a.off > a.cap) return fail(h, SCRF_ERR_INVALID, "internal: scratch arena overflow");
+  RCCHK(nstate_pipe.begin_chunk(h, b, u0, u1, post, &nb));
   ScrfBatchView bv = b->view();
   hipStream_t st = h->stream;
-  if (b->mode == 1) launch_chunk_windows(h, b, u0, u1, st, nb.X);
   KT_RUN("k_ns_scores", st, launch_ns_scores(st, l, nb.X, nfr, h->d_lambda, nb.S, nb.TD, nb.TO, nb.TE));
   KT_RUN("k_ns_fb", st, launch_ns_fb(st, l, bv, u0, u1 - u0, nb.S, nb.TD, nb.TO, nb.TE, nb.alpha, nb.beta, b->d_zx, b->d_status));
   if (post) {
@@ -1966,10 +2030,11 @@ static int nstate_run_chunk(scrf_handle h, scrf_batch b, uint32_t u0, uint32_t u
   if (out) *out = nb;
   return SCRF_OK;
 }
-static uint32_t nstate_plan_chunk(scrf_handle h, scrf_batch b, uint32_t u0, bool post) {
-  uint32_t u1 = u0 + 1;
-  while (u1 < b->U && nstate_chunk_size(h, b, u0, u1 + 1, post) <= h->cfg.scratch_bytes) u1++;
-  return u1;
+// the next chunk of the small pipeline this model and pass run
+static uint32_t small_plan_chunk(scrf_handle h, scrf_batch b, uint32_t u0, bool post) {
+  if (nstate(h)) return nstate_pipe.plan(h, b, u0, post);
+  if (post && stdseg_lin(h)) return stdseg_lin_pipe.plan(h, b, u0, post);
+  return stdseg_pipe.plan(h, b, u0, post);
 }
 
 // The form a batch's training and posterior passes take, by ingredient (scrf_batch_is_fused reports them as they are):
@@ -1994,257 +2059,326 @@ static void set_batch_form(scrf_handle h, scrf_batch b, Need* nd) {
   nd->la = nd->fused && f.la;
 }
 
-// One pass of the forward-backward pipeline over the batch into the staging gradient.  latch[2] receives
-// {status code, utterance} of the first failed utterance (0 = clean, gradient committed); *used_lin tells
-// whether any chunk ran the linear-domain recursion.
+// ---------------------------------------------------------------------------------------------
+// the training pass (scrf_fb_batch): one pass of the forward-backward pipeline over the batch into the staging gradient,
+// in phases -- fb_begin, then per chunk (fb_chunk) scores, recursion, counts and their reductions, then fb_commit
+// ---------------------------------------------------------------------------------------------
 static int allreduce_block(scrf_handle h, hipStream_t st, int part);
 static bool two_block_reduce(scrf_handle h) { return h->comm && h->lay.use_tf && h->cfg.model_type != SCRF_STDSEG_NO_DUR && h->cfg.model_type != SCRF_STDSEG && h->lay.K <= 1 && !h->shadow; }
 
-static int fb_run(scrf_handle h, scrf_batch b, int latch[2], bool* used_lin) {
-  const ScrfLayout& l = h->lay;
+// arms the status latch and clears the staging gradient and sums
+static int fb_begin(scrf_handle h, scrf_batch b) {
   HIPCHK(h, hipMemsetAsync(b->d_status, 0, sizeof(int) * b->U, h->stream));
   hipLaunchKernelGGL(k_latch_reset, dim3(1), dim3(1), 0, h->stream, h->d_latch);
-  HIPCHK(h, hipMemsetAsync(h->d_stage, 0, sizeof(double) * l.lambda_len, h->stream));
+  HIPCHK(h, hipMemsetAsync(h->d_stage, 0, sizeof(double) * h->lay.lambda_len, h->stream));
   HIPCHK(h, hipMemsetAsync(h->d_sums_stage, 0, sizeof(double) * 4, h->stream));
-  *used_lin = false;
-  if (stdseg(h) || nstate(h)) {
-    for (uint32_t u0 = 0; u0 < b->U;) {
-      const uint32_t u1 = nstate(h) ? nstate_plan_chunk(h, b, u0, true) : stdseg_plan_chunk(h, b, u0, true);
-      int rc = nstate(h) ? nstate_run_chunk(h, b, u0, u1, true, h->d_stage, nullptr) : stdseg_run_chunk(h, b, u0, u1, true, h->d_stage, nullptr);
-      if (rc != SCRF_OK) return rc;
-      launch_stdseg_sums(h->stream, b->d_numer, b->d_zx, u0, u1 - u0, h->d_sums_stage);
-      u0 = u1;
-    }
-    int rc = queue_status(h, b);
-    if (rc != SCRF_OK) return rc;
-    hipLaunchKernelGGL(k_commit, dim3((l.lambda_len + 255) / 256), dim3(256), 0, h->stream, h->d_grad, h->d_stage, l.lambda_len,
-                       h->d_sums, h->d_sums_stage, h->d_latch);
-    HIPCHK(h, hipGetLastError());
+  return SCRF_OK;
+}
+
+// the staged gradient into the engine's (a no-op on a latched batch): all of it, or one block of the weight vector
+// (k_commit_part: 1 = the transition weights, 0 = the state weights and the batch sums)
+enum { COMMIT_STATE = 0, COMMIT_TRANS = 1, COMMIT_ALL = 2 };
+static void commit_staged(scrf_handle h, int part) {
+  const ScrfLayout& l = h->lay;
+  const dim3 grid((l.lambda_len + 255) / 256), block(256);
+  if (part == COMMIT_ALL)
+    hipLaunchKernelGGL(k_commit, grid, block, 0, h->stream, h->d_grad, h->d_stage, l.lambda_len, h->d_sums, h->d_sums_stage, h->d_latch);
+  else
+    hipLaunchKernelGGL(k_commit_part, grid, block, 0, h->stream, h->d_grad, h->d_stage, l.lambda_len, l.stride, l.nsf, part, h->d_sums,
+                       h->d_sums_stage, h->d_latch);
+}
+
+// commits what the early all-reduce has not, and waits for the batch's status: latch[2] receives {status code, utterance} of
+// the first failed utterance (0 = clean, gradient committed)
+static int fb_commit(scrf_handle h, int latch[2]) {
+  commit_staged(h, h->early_done ? COMMIT_STATE : COMMIT_ALL);   // early_done: the transition block was committed (and sent) already
+  HIPCHK(h, hipGetLastError());
+  HIPCHK(h, hipEventSynchronize(h->ev_status));
+  latch_decode(h->h_latch, latch);
+  return SCRF_OK;
+}
+
+// STDSEG and the n-state frame model: their own small pipelines, chunk by chunk on the engine stream
+static int fb_run_small(scrf_handle h, scrf_batch b, int latch[2]) {
+  RCCHK(fb_begin(h, b));
+  for (uint32_t u0 = 0; u0 < b->U;) {
+    const uint32_t u1 = small_plan_chunk(h, b, u0, true);
+    RCCHK(nstate(h) ? nstate_run_chunk(h, b, u0, u1, true, h->d_stage, nullptr) : stdseg_run_chunk(h, b, u0, u1, true, h->d_stage, nullptr));
+    launch_stdseg_sums(h->stream, b->d_numer, b->d_zx, u0, u1 - u0, h->d_sums_stage);
+    u0 = u1;
+  }
+  RCCHK(queue_status(h, b));
+  return fb_commit(h, latch);
+}
+
+// The chunks of a training pass: each must fit the scratch budget; with two lanes a batch is cut into at least four chunks
+// (none above a quarter of the utterances) so that both streams always have work.  Chunk i is [cuts[i], cuts[i + 1]).
+struct FbPlan {
+  std::vector<uint32_t> cuts;
+  bool use2 = false;   // two lanes: odd chunks on the second stream, into a gradient of their own
+  size_t n_chunks() const { return cuts.size() - 1; }
+  int lane(size_t ci) const { return use2 ? (int)(ci & 1) : 0; }
+};
+static FbPlan fb_plan(scrf_handle h, scrf_batch b, const Need& nd) {
+  FbPlan p;
+  p.cuts.push_back(0);
+  const bool two_lanes = h->kn.lanes > 1 && !h->timing && b->U >= 64;
+  const uint32_t cap = two_lanes ? (b->U + 3) / 4 : b->U;
+  for (uint32_t u0 = 0; u0 < b->U;) {
+    const uint32_t u1 = std::min(plan_chunk(h, b, u0, nd), u0 + cap);
+    p.cuts.push_back(u1);
+    u0 = u1;
+  }
+  p.use2 = two_lanes && p.n_chunks() >= 2;
+  return p;
+}
+
+// The route of chunk ci, once it is carved.  overlap (fused call only, scrf_fb_batch_allreduce): it waits for the status on
+// the host, on the main stream.  side: the fused count kernel's wave-specialised form leaves room for a narrow k_ztf beside
+// it, so k_ztf, its reduction and the transition counts A^T B run on the second stream -- and so do the recursion's check
+// kernels and the status copy.  That needs the linear-domain fused branch of the recursion (dp_wave_lin: it forms Z in the
+// posterior walk) and bias-only transitions.  Off while kernels are timed one by one (scrf_enable_timing), with two lanes
+// (the second stream is a lane then) and with SCRF_SIDE=0.
+static FbRoute fb_route(scrf_handle h, scrf_batch b, const ChunkBufs& cb, const FbPlan& plan, size_t ci) {
+  FbRoute rt;
+  rt.lane = plan.lane(ci);
+  rt.two_lanes = plan.use2;
+  rt.last = ci + 1 == plan.n_chunks();
+  rt.overlap = h->overlap_comm && h->kn.comm_overlap && two_block_reduce(h) && !plan.use2 && !h->timing && !sparse(h);
+  rt.side = h->kn.side && !plan.use2 && !h->timing && !rt.overlap && cb.fused && cb.lin && cb.wave && !h->lay.use_tf && !segtrans(h) &&
+            pframe_supported(b->recipe[0].in_width) && cb.expf_plan.ws;
+  return rt;
+}
+
+// The count launches of a chunk and the slab reductions they owe.  Each count function states the ScrfGemmSpec of a slab
+// next to the launch that fills it; the reduce phase applies them, in launch order, behind all the count launches.
+struct SlabSum { const double* slab; uint32_t nch, n_out; ScrfGemmSpec spec; };
+struct ChunkCounts {
+  SlabSum owed[4];   // at most three state slabs and one transition slab
+  uint32_t n_owed = 0;
+  uint32_t launches = 1;   // what PH_EXPF reports
+  void owe(const double* slab, uint32_t nch, uint32_t n_out, const ScrfGemmSpec& spec) { owed[n_owed++] = SlabSum{slab, nch, n_out, spec}; }
+};
+static void reduce_owed(scrf_handle h, const ChunkBufs& cb, const ChunkCounts& cc) {
+  for (uint32_t i = 0; i < cc.n_owed; i++)
+    launch_reduce_slabs(cb.st, cc.owed[i].slab, cc.owed[i].nch, cc.owed[i].n_out, h->lay, cc.owed[i].spec, cb.grad);
+}
+// one-hot duration + bias counts from a slab of their own (the fused kernel's wave-specialised form, k_lin_z5)
+static ScrfGemmSpec spec_dur_bias(const ScrfLayout& l, uint32_t W) { return ScrfGemmSpec{0, 0, l.D, (uint32_t)l.use_sb, l.sbv, 8 * W, 0}; }
+
+// fused form: R's contraction with the synthesised windows, the sampled blocks through the per-frame sums Z
+static int count_fused(scrf_handle h, scrf_batch b, uint32_t u0, uint32_t u1, ChunkBufs& cb, const FbRoute& rt, ChunkCounts* cc) {
+  const ScrfLayout& l = h->lay;
+  const uint32_t W0 = b->recipe[0].in_width, nz = (cb.la ? 6 : 5) * l.L;
+  const uint64_t nfr = b->frame_off[u1] - b->frame_off[u0];
+  const auto* fr0 = b->d_frames[0] + b->frame_off[u0] * W0;
+  const ScrfFusedExpfPlan& plan = cb.expf_plan;
+  ScrfFusedArgs fa = fused_args(h, b, u0, plan.tile_list);
+  if (rt.side) {
+    // k_ztf, its reduction and A^T B need Z / the recursion's vectors, not R's contraction: they run on the second stream
+    // UNDER k_expf_fused_ws, whose one workgroup per CU leaves 80 registers per SIMD lane and the wave slots for a narrow
+    // k_ztf (one output tile per wavefront).  The two sides add into disjoint weights; the streams join in the reduce phase.
+    // The second stream was forked behind k_post_z (dp_wave_lin) and holds the check kernels already: no second fork.
+    launch_ztf(h->stream2, cb.Z, nz, fr0, W0, nfr, cb.rpc_l, cb.nch_l, cb.slab_l, 1);
+    launch_reduce_slabs(h->stream2, cb.slab_l, cb.nch_l, nz, l, spec_samples(W0), cb.grad);
+    launch_atb(h->stream2, l, cb.fA, cb.fB, nfr, cb.rpc_atb, cb.nch_atb, cb.slab_atb, h->d_m0, cb.grad, cb.lin ? cb.dl.gsd : nullptr);
+    HIPCHK(h, hipEventRecord(h->ev_join, h->stream2));
+  }
+  {
+    PhaseTimer tk(h, PH_K_EXPF, cb.st);
+    KT_RUN("k_expf_fused", cb.st, launch_expf_fused(cb.st, h->kn, fa, l, cb.R, b->tile_off[plan.tile_list][u1] - b->tile_off[plan.tile_list][u0], cb.slab_s, cb.slab_d, prec_f32(h), cb.la ? 1 : 0));
+    tk.stop(1);
+  }
+  if (plan.ndur) {
+    // dense groups [avg |] max | min at columns (5 + g0) W ..; one-hot duration + bias counts from their own slab
+    cc->owe(cb.slab_s, cb.nch_s, l.L, ScrfGemmSpec{0, 0, plan.ncol, 0, 0.0, (5 + plan.g0) * W0, 0});
+    cc->owe(cb.slab_d, cb.nch_s, l.L, spec_dur_bias(l, W0));
+  } else cc->owe(cb.slab_s, cb.nch_s, l.L, spec_dense(l, W0));
+  if (!cb.z_ready) KT_RUN("k_lin_z", cb.st, launch_lin_z(cb.st, l, b->view(), u0, u1 - u0, cb.R, cb.Z));
+  if (!rt.side) {
+    if (pframe_supported(W0)) KT_RUN("k_ztf", cb.st, launch_ztf(cb.st, cb.Z, nz, fr0, W0, nfr, cb.rpc_l, cb.nch_l, cb.slab_l));
+    else KT_RUN("k_expf_mfma(samples)", cb.st, launch_expf_mfma(cb.st, h->kn, cb.Z, nz, fr0, W0, nullptr, nfr, l, spec_samples(W0), cb.rpc_l, cb.nch_l, cb.slab_l));
+    cc->owe(cb.slab_l, cb.nch_l, nz, spec_samples(W0));
+  }
+  cc->launches += 2;
+  return SCRF_OK;
+}
+
+// hybrid form: materialised dense statistics, the sampled blocks through Z
+static void count_hybrid(scrf_handle h, scrf_batch b, uint32_t u0, uint32_t u1, ChunkBufs& cb, ChunkCounts* cc) {
+  const ScrfLayout& l = h->lay;
+  const uint32_t W0 = b->recipe[0].in_width, nutt = u1 - u0;
+  const uint64_t nfr = b->frame_off[u1] - b->frame_off[u0], nseg = b->seg_off[u1] - b->seg_off[u0];
+  const auto* fr0 = b->d_frames[0] + b->frame_off[u0] * W0;
+  const uint32_t t_max = longest_utt(b, u0, u1);   // k_lin_z5's segments, and so the blocks of its slab
+  {
+    PhaseTimer tk(h, PH_K_EXPF, cb.st);
+    // [avg | max | min] only: the one-hot duration and bias counts are sums of R (k_lin_z5), and 3 W columns are one
+    // 384-column tile of the count kernel where 3 W + D + 1 were two
+    KT_RUN("k_expf_mfma(state)", cb.st, launch_expf_mfma(cb.st, h->kn, cb.R, l.L, cb.X, hybrid_row_floats(l, W0), nullptr, nseg, l, spec_stats_x(l, W0), cb.rpc_s, cb.nch_s, cb.slab_s, prec_f32(h)));
+    tk.stop(1);
+  }
+  cc->owe(cb.slab_s, cb.nch_s, l.L, spec_stats_x(l, W0));
+  KT_RUN("k_lin_z5", cb.st, launch_lin_z5(cb.st, l, b->view(), u0, nutt, t_max, nfr, cb.R, cb.Z, cb.slab_d));
+  int seg_len = 0;
+  cc->owe(cb.slab_d, nutt * lin_z5_segments(nutt, l.L, l.D, t_max, &seg_len), l.L, spec_dur_bias(l, W0));
+  if (pframe_supported(W0)) KT_RUN("k_ztf", cb.st, launch_ztf(cb.st, cb.Z, 5 * l.L, fr0, W0, nfr, cb.rpc_l, cb.nch_l, cb.slab_l));
+  else KT_RUN("k_expf_mfma(samples)", cb.st, launch_expf_mfma(cb.st, h->kn, cb.Z, 5 * l.L, fr0, W0, nullptr, nfr, l, spec_samples(W0), cb.rpc_l, cb.nch_l, cb.slab_l));
+  cc->owe(cb.slab_l, cb.nch_l, 5 * l.L, spec_samples(W0));
+  cc->launches += 2;
+}
+
+// sparse maps: inverted index of the chunk's windows, per-index sums of R, bias sums; then the transition counts of the
+// next node's first window (the dense path's xrow_next) over Y - xi.  The sparse kernels add into the gradient themselves.
+static void count_sparse(scrf_handle h, scrf_batch b, uint32_t u0, uint32_t u1, ChunkBufs& cb, ChunkCounts* cc) {
+  const ScrfLayout& l = h->lay;
+  const uint64_t nfr = b->frame_off[u1] - b->frame_off[u0], nseg = b->seg_off[u1] - b->seg_off[u0];
+  PhaseTimer tk(h, PH_K_EXPF, cb.st);
+  KT_RUN("sparse state counts", cb.st, launch_sp_counts(cb.st, cb.X, l.F, nullptr, nseg, cb.R, l, 0, cb.spx[0], cb.grad));
+  tk.stop(1);
+  if (!l.use_tf) return;
+  launch_frame_rows(cb.st, b->view(), u0, u1, l.D, nfr, cb.xrow_next, 1);
+  KT_RUN("sparse transition counts", cb.st, launch_sp_counts(cb.st, cb.X, l.F, cb.xrow_next, nfr, cb.XI, l, 1, cb.spx[1], cb.grad));
+  cc->launches += 2;
+}
+
+// dense form: R's contraction with the materialised windows
+static void count_dense(scrf_handle h, scrf_batch b, uint32_t u0, uint32_t u1, ChunkBufs& cb, ChunkCounts* cc) {
+  const ScrfLayout& l = h->lay;
+  const uint64_t nseg = b->seg_off[u1] - b->seg_off[u0];
+  PhaseTimer tk(h, PH_K_EXPF, cb.st);
+  if (prec_fast(h)) KT_RUN("k_expf_mfma(state)", cb.st, launch_expf_mfma(cb.st, h->kn, cb.R, l.L, cb.X, l.F, nullptr, nseg, l, scrf_spec_state(l), cb.rpc_s, cb.nch_s, cb.slab_s, prec_f32(h)));
+  else KT_RUN("k_expf_gemm(state)", cb.st, launch_expf_gemm(cb.st, cb.R, l.L, cb.X, l.F, nullptr, nseg, l, 0, cb.rpc_s, cb.nch_s, cb.slab_s));
+  tk.stop(1);
+  cc->owe(cb.slab_s, cb.nch_s, l.L, scrf_spec_state(l));
+}
+
+// transition counts over the transition features.  by_window (STDSEG_NO_DUR): XI's rows are windows, contracted with the
+// segment's own window, no row map; otherwise its rows are frames, contracted with the next node's first window.
+static void count_trans(scrf_handle h, scrf_batch b, uint32_t u0, uint32_t u1, ChunkBufs& cb, bool by_window, ChunkCounts* cc) {
+  const ScrfLayout& l = h->lay;
+  const uint64_t nfr = b->frame_off[u1] - b->frame_off[u0], nseg = b->seg_off[u1] - b->seg_off[u0];
+  const uint64_t* rows = by_window ? nullptr : cb.xrow_next;
+  const uint64_t n_rows = by_window ? nseg : nfr;
+  if (!by_window) launch_frame_rows(cb.st, b->view(), u0, u1, l.D, nfr, cb.xrow_next, 1);
+  if (prec_fast(h)) KT_RUN("k_expf_mfma(trans)", cb.st, launch_expf_mfma(cb.st, h->kn, cb.XI, l.L * l.L, cb.X, l.F, rows, n_rows, l, scrf_spec_trans(l), cb.rpc_t, cb.nch_t, cb.slab_t, prec_f32(h)));
+  else KT_RUN("k_expf_gemm(trans)", cb.st, launch_expf_gemm(cb.st, cb.XI, l.L * l.L, cb.X, l.F, rows, n_rows, l, 1, cb.rpc_t, cb.nch_t, cb.slab_t));
+  cc->owe(cb.slab_t, cb.nch_t, l.L * l.L, scrf_spec_trans(l));
+  cc->launches += by_window ? 1 : 2;
+}
+
+// All-reduce / compute overlap: the chunk's transition counts first, reduced at once; once the last chunk's are in they are
+// committed and their all-reduce goes to the second stream, under the state contraction.  A NUMERIC failure of the recursion
+// is retried with the log-domain kernels by the caller: that has to be known BEFORE a collective is issued (the peers issue
+// theirs exactly once), so the host waits for the status here.  *redo: the caller reruns; nothing committed, nothing sent.
+static int fb_early_trans(scrf_handle h, scrf_batch b, uint32_t u0, uint32_t u1, ChunkBufs& cb, const FbRoute& rt, int latch[2], bool* redo) {
+  if (rt.last) {
     HIPCHK(h, hipEventSynchronize(h->ev_status));
     latch_decode(h->h_latch, latch);
-    return SCRF_OK;
+    if (latch[0] == SCRF_ERR_NUMERIC && wave_path(h, true)) { *redo = true; return SCRF_OK; }
   }
-  Need nd{true, true, false, false};
-  ScrfBatchView bv = b->view();
-  const bool fast = h->cfg.train_precision >= SCRF_PREC_FAST;
-  const int f32 = h->cfg.train_precision == SCRF_PREC_FAST32;
-  set_batch_form(h, b, &nd);
+  ChunkCounts tc;
+  count_trans(h, b, u0, u1, cb, false, &tc);
+  reduce_owed(h, cb, tc);
+  if (!rt.last) return SCRF_OK;
+  commit_staged(h, COMMIT_TRANS);
+  HIPCHK(h, hipEventRecord(h->ev_fork, h->stream));
+  HIPCHK(h, hipStreamWaitEvent(h->stream2, h->ev_fork, 0));
+  RCCHK(allreduce_block(h, h->stream2, 1));
+  HIPCHK(h, hipEventRecord(h->ev_join, h->stream2));
+  h->early_done = true;
+  return SCRF_OK;
+}
 
-  // plan the chunks first: each must fit the scratch budget; with two lanes a batch is cut into
-  // at least four chunks so that both streams always have work
-  std::vector<uint32_t> cuts(1, 0);
-  const bool two_lanes = h->kn.lanes > 1 && !h->timing && b->U >= 64;
+// the count phase of a chunk: the state counts of its form, then the transition counts over transition features (unless the
+// early all-reduce took them, or the sparse kernels did)
+static int fb_count(scrf_handle h, scrf_batch b, uint32_t u0, uint32_t u1, ChunkBufs& cb, const FbRoute& rt, ChunkCounts* cc) {
+  PhaseTimer tm(h, PH_EXPF, cb.st);
+  if (cb.fused) RCCHK(count_fused(h, b, u0, u1, cb, rt, cc));
+  else if (cb.hybrid) count_hybrid(h, b, u0, u1, cb, cc);
+  else if (sparse(h)) count_sparse(h, b, u0, u1, cb, cc);
+  else count_dense(h, b, u0, u1, cb, cc);
+  if (segtrans(h)) count_trans(h, b, u0, u1, cb, true, cc);
+  else if (!sparse(h) && h->lay.use_tf && !rt.overlap) count_trans(h, b, u0, u1, cb, false, cc);
+  tm.stop(cc->launches);
+  return SCRF_OK;
+}
+
+// the reduce phase: the owed slabs into the lane's gradient, the transition counts of bias-only transitions (no slab of
+// split-K sums: A^T B over the xi factors, or the workgroup recursion's per-utterance xi), the batch sums
+static int fb_reduce(scrf_handle h, scrf_batch b, uint32_t u0, uint32_t u1, ChunkBufs& cb, const FbRoute& rt, const ChunkCounts& cc) {
+  const ScrfLayout& l = h->lay;
+  const uint32_t nutt = u1 - u0;
+  PhaseTimer tm(h, PH_REDUCE, cb.st);
+  KernelTimer kt(h, "reductions (k_reduce_slabs, k_atb, k_batch_sums)", cb.st);
+  reduce_owed(h, cb, cc);
+  if (rt.side) HIPCHK(h, hipStreamWaitEvent(cb.st, h->ev_join, 0));   // the side stream's weights (k_ztf's, A^T B's) are in
+  else if (l.use_tf || segtrans(h)) {}
+  else if (cb.wave) launch_atb(cb.st, l, cb.fA, cb.fB, b->frame_off[u1] - b->frame_off[u0], cb.rpc_atb, cb.nch_atb, cb.slab_atb, h->d_m0, cb.grad,
+                               cb.lin ? cb.dl.gsd : nullptr);
+  else launch_reduce_xiacc(cb.st, cb.xi_acc, nutt, l, cb.grad);
+  launch_batch_sums(cb.st, b->d_numer + u0, b->d_zx + u0, nutt, cb.sums);
+  kt.stop(4);
+  tm.stop(3);
+  return SCRF_OK;
+}
+
+// chunk ci of the pass, on its lane.  *redo: see fb_early_trans.
+static int fb_chunk(scrf_handle h, scrf_batch b, const FbPlan& plan, size_t ci, const Need& nd, int latch[2], bool* redo) {
+  const uint32_t u0 = plan.cuts[ci], u1 = plan.cuts[ci + 1];
+  ChunkBufs cb;
+  RCCHK(score_chunk(h, b, u0, u1, nd, &cb, SCORE_PASS, plan.lane(ci)));
+  if (!plan.lane(ci)) { cb.grad = h->d_stage; cb.sums = h->d_sums_stage; }
+  const FbRoute rt = fb_route(h, b, cb, plan, ci);
   {
-    const uint32_t cap = two_lanes ? (b->U + 3) / 4 : b->U;
-    for (uint32_t u0 = 0; u0 < b->U;) {
-      uint32_t u1 = plan_chunk(h, b, u0, nd);
-      if (u1 - u0 > cap) u1 = u0 + cap;
-      cuts.push_back(u1);
-      u0 = u1;
-    }
+    PhaseTimer tm(h, PH_FB, cb.st);
+    uint32_t nl = 0;
+    RCCHK(run_dp(h, b, u0, u1, cb, DpOpts::training(rt), &nl));
+    tm.stop(nl);
   }
-  const size_t n_chunks = cuts.size() - 1;
-  const bool use2 = two_lanes && n_chunks >= 2;
+  // every per-utterance status of the batch is final once the last chunk's posterior kernels are queued: its copy to the
+  // host travels under the expected-count kernels (side: run_dp queued it on the second stream; two lanes: behind the join)
+  if (rt.last && !rt.two_lanes && !rt.side) RCCHK(queue_status(h, b));
+  if (rt.overlap) {
+    RCCHK(fb_early_trans(h, b, u0, u1, cb, rt, latch, redo));
+    if (*redo) return SCRF_OK;
+  }
+  ChunkCounts cc;
+  RCCHK(fb_count(h, b, u0, u1, cb, rt, &cc));
+  RCCHK(fb_reduce(h, b, u0, u1, cb, rt, cc));
+  HIPCHK(h, hipGetLastError());
+  return SCRF_OK;
+}
+
+static int fb_run(scrf_handle h, scrf_batch b, int latch[2]) {
+  const ScrfLayout& l = h->lay;
+  RCCHK(fb_begin(h, b));
+  Need nd = Need::training();
+  set_batch_form(h, b, &nd);
+  const FbPlan plan = fb_plan(h, b, nd);
   if (!l.use_tf && !segtrans(h)) ensure_m0(h, h->stream);   // before the lanes fork
   if (sparse(h)) relay_sparse_lambda(h, h->stream);
-  if (use2) {
+  if (plan.use2) {
     HIPCHK(h, hipMemsetAsync(h->d_grad2, 0, sizeof(double) * l.lambda_len, h->stream));
     HIPCHK(h, hipMemsetAsync(h->d_sums2, 0, sizeof(double) * 4, h->stream));
     HIPCHK(h, hipEventRecord(h->ev_fork, h->stream));
     HIPCHK(h, hipStreamWaitEvent(h->stream2, h->ev_fork, 0));
   }
-  for (size_t ci = 0; ci < n_chunks; ci++) {
-    const uint32_t u0 = cuts[ci], u1 = cuts[ci + 1];
-    const int lane = use2 ? (int)(ci & 1) : 0;
-    ChunkBufs cb;
-    int rc = carve(h, b, u0, u1, nd, &cb, lane);
-    if (rc != SCRF_OK) return rc;
-    if (!lane) { cb.grad = h->d_stage; cb.sums = h->d_sums_stage; }
-    cb.lamT_ready = sparse(h);
-    if (cb.lin) *used_lin = true;
-    const uint64_t nutt = u1 - u0, nfr = b->frame_off[u1] - b->frame_off[u0], nseg = b->seg_off[u1] - b->seg_off[u0];
-    rc = run_scores(h, b, u0, u1, cb, fast, f32);
-    if (rc != SCRF_OK) return rc;
-    // all-reduce / compute overlap (fused call only, below): it waits for the status on the host, on the main stream
-    const bool ov = h->overlap_comm && h->kn.comm_overlap && two_block_reduce(h) && !use2 && !h->timing && !sparse(h);
-    // Side stream: whether part of this chunk's count work will run on the engine's second stream (the count phase
-    // below) is known here, and then the recursion's check kernels and the status copy go there as well.  These are
-    // the conditions under which run_dp's linear-domain fused branch runs (it sets cb.z_ready) and the count phase can
-    // hand k_ztf and k_atb over.
-    const bool side_pre = h->kn.side && !use2 && !h->timing && !ov && cb.fused && cb.lin && cb.wave && !l.use_tf && !segtrans(h) &&
-                          pframe_supported(b->recipe[0].in_width) && cb.expf_plan.ws;
-    {
-      PhaseTimer tm(h, PH_FB, cb.st);
-      uint32_t nl = 0;
-      rc = run_dp(h, b, u0, u1, cb, true, &nl, false, side_pre, ci + 1 == n_chunks);
-      if (rc != SCRF_OK) return rc;
-      tm.stop(nl);
-    }
-    // every per-utterance status of the batch is final once the last chunk's posterior kernels are queued:
-    // its copy to the host travels under the expected-count kernels (side_pre: run_dp queued it on the second stream)
-    if (!use2 && !side_pre && ci + 1 == n_chunks) {
-      rc = queue_status(h, b);
-      if (rc != SCRF_OK) return rc;
-    }
-    // all-reduce / compute overlap (fused call only): transition counts first; once the last chunk's are reduced they
-    // are committed and their all-reduce goes to the second stream, under the state contraction.  A NUMERIC failure of
-    // the recursion is retried with the log-domain kernels by the caller: that has to be known BEFORE a collective is
-    // issued (the peers issue theirs exactly once), so the host waits for the status here.
-    bool trans_done = false;   // the transition counts of this chunk are already in the staged gradient
-    if (ov) {
-      if (ci + 1 == n_chunks) {
-        HIPCHK(h, hipEventSynchronize(h->ev_status));
-        latch_decode(h->h_latch, latch);
-        if (latch[0] == SCRF_ERR_NUMERIC && wave_path(h, true)) return SCRF_OK;   // the caller reruns; nothing committed, nothing sent
-      }
-      launch_frame_rows(cb.st, bv, u0, u1, l.D, nfr, cb.xrow_next, 1);
-      if (fast) launch_expf_mfma(cb.st, h->kn, cb.XI, l.L * l.L, cb.X, l.F, cb.xrow_next, nfr, l, scrf_spec_trans(l), cb.rpc_t, cb.nch_t, cb.slab_t, f32);
-      else launch_expf_gemm(cb.st, cb.XI, l.L * l.L, cb.X, l.F, cb.xrow_next, nfr, l, 1, cb.rpc_t, cb.nch_t, cb.slab_t);
-      launch_reduce_slabs(cb.st, cb.slab_t, cb.nch_t, l.L * l.L, l, scrf_spec_trans(l), cb.grad);
-      if (ci + 1 == n_chunks) {
-        hipLaunchKernelGGL(k_commit_part, dim3((l.lambda_len + 255) / 256), dim3(256), 0, h->stream, h->d_grad, h->d_stage, l.lambda_len,
-                           l.stride, l.nsf, 1, h->d_sums, h->d_sums_stage, h->d_latch);
-        HIPCHK(h, hipEventRecord(h->ev_fork, h->stream));
-        HIPCHK(h, hipStreamWaitEvent(h->stream2, h->ev_fork, 0));
-        rc = allreduce_block(h, h->stream2, 1);
-        if (rc != SCRF_OK) return rc;
-        HIPCHK(h, hipEventRecord(h->ev_join, h->stream2));
-        h->early_done = true;
-      }
-      trans_done = true;   // the state part (fused or dense) follows below, under the transition block's all-reduce
-    }
-    bool side = false;   // part of the count work runs on the second stream (below)
-    uint32_t t_max = 0;   // longest utterance of the chunk (hybrid path: k_lin_z5's segments, here and at the reduction)
-    if (cb.hybrid) for (uint64_t u = u0; u < u1; u++) t_max = std::max(t_max, b->T[u]);
-    {
-      PhaseTimer tm(h, PH_EXPF, cb.st);
-      uint32_t nl = 1;
-      if (cb.fused) {
-        const uint32_t W0 = b->recipe[0].in_width;
-        ScrfFusedArgs fa = fused_args(h, b, u0, cb.expf_plan.tile_list);
-        // Side stream (round 4): the per-frame count contraction k_ztf, its reduction and the transition counts A^T B
-        // need Z / the recursion's vectors, not R's contraction -- they run on the engine's second stream UNDER
-        // k_expf_fused_ws, whose one workgroup per CU leaves 80 registers per SIMD lane and the wave slots for a narrow
-        // k_ztf (one output tile per wavefront).  The two sides add into disjoint weights; the streams join before the
-        // commit.  Off while kernels are timed one by one (scrf_enable_timing) and with SCRF_SIDE=0.
-        // The second stream was forked behind k_post_z (run_dp) and holds the check kernels already: no second fork.
-        side = side_pre;   // (cb.z_ready holds: run_dp took the branch that forks)
-        if (side) {
-          launch_ztf(h->stream2, cb.Z, (cb.la ? 6 : 5) * l.L, b->d_frames[0] + b->frame_off[u0] * W0, W0, nfr, cb.rpc_l, cb.nch_l, cb.slab_l, 1);
-          launch_reduce_slabs(h->stream2, cb.slab_l, cb.nch_l, (cb.la ? 6 : 5) * l.L, l, spec_samples(W0), cb.grad);
-          launch_atb(h->stream2, l, cb.fA, cb.fB, nfr, cb.rpc_atb, cb.nch_atb, cb.slab_atb, h->d_m0, cb.grad, cb.lin ? cb.dl.gsd : nullptr);
-          HIPCHK(h, hipEventRecord(h->ev_join, h->stream2));
-        }
-        {
-          PhaseTimer tk(h, PH_K_EXPF, cb.st);
-          KT_RUN("k_expf_fused", cb.st, launch_expf_fused(cb.st, h->kn, fa, l, cb.R, b->tile_off[cb.expf_plan.tile_list][u1] - b->tile_off[cb.expf_plan.tile_list][u0], cb.slab_s, cb.slab_d, f32, cb.la ? 1 : 0));
-          tk.stop(1);
-        }
-        if (!cb.z_ready) KT_RUN("k_lin_z", cb.st, launch_lin_z(cb.st, l, bv, u0, (uint32_t)nutt, cb.R, cb.Z));
-        if (!side && pframe_supported(W0))   // (side: k_ztf ran on the second stream)
-          KT_RUN("k_ztf", cb.st, launch_ztf(cb.st, cb.Z, (cb.la ? 6 : 5) * l.L, b->d_frames[0] + b->frame_off[u0] * W0, W0, nfr, cb.rpc_l, cb.nch_l, cb.slab_l));
-        else if (!side)
-          KT_RUN("k_expf_mfma(samples)", cb.st, launch_expf_mfma(cb.st, h->kn, cb.Z, (cb.la ? 6 : 5) * l.L, b->d_frames[0] + b->frame_off[u0] * W0, W0, nullptr, nfr, l,
-                           spec_samples(W0), cb.rpc_l, cb.nch_l, cb.slab_l));
-        nl += 2;
-      } else if (cb.hybrid) {
-        const uint32_t W0 = b->recipe[0].in_width;
-        {
-          PhaseTimer tk(h, PH_K_EXPF, cb.st);
-          // [avg | max | min] only: the one-hot duration and bias counts are sums of R (k_lin_z5), and 3 W columns are one
-          // 384-column tile of the count kernel where 3 W + D + 1 were two
-          KT_RUN("k_expf_mfma(state)", cb.st, launch_expf_mfma(cb.st, h->kn, cb.R, l.L, cb.X, hybrid_row_floats(l, W0), nullptr, nseg, l, spec_stats_x(l, W0), cb.rpc_s, cb.nch_s, cb.slab_s, f32));
-          tk.stop(1);
-        }
-        KT_RUN("k_lin_z5", cb.st, launch_lin_z5(cb.st, l, bv, u0, (uint32_t)nutt, t_max, nfr, cb.R, cb.Z, cb.slab_d));
-        if (pframe_supported(W0))
-          KT_RUN("k_ztf", cb.st, launch_ztf(cb.st, cb.Z, 5 * l.L, b->d_frames[0] + b->frame_off[u0] * W0, W0, nfr, cb.rpc_l, cb.nch_l, cb.slab_l));
-        else
-          KT_RUN("k_expf_mfma(samples)", cb.st, launch_expf_mfma(cb.st, h->kn, cb.Z, 5 * l.L, b->d_frames[0] + b->frame_off[u0] * W0, W0, nullptr, nfr, l,
-                           spec_samples(W0), cb.rpc_l, cb.nch_l, cb.slab_l));
-        nl += 2;
-      } else if (sparse(h)) {
-        // inverted index of the chunk's windows, per-index sums of R, bias sums; then the transition counts of the
-        // next node's first window (the dense path's xrow_next) over Y - xi
-        PhaseTimer tk(h, PH_K_EXPF, cb.st);
-        KT_RUN("sparse state counts", cb.st, launch_sp_counts(cb.st, cb.X, l.F, nullptr, nseg, cb.R, l, 0, cb.spx[0], cb.grad));
-        tk.stop(1);
-        if (l.use_tf) {
-          launch_frame_rows(cb.st, bv, u0, u1, l.D, nfr, cb.xrow_next, 1);
-          KT_RUN("sparse transition counts", cb.st, launch_sp_counts(cb.st, cb.X, l.F, cb.xrow_next, nfr, cb.XI, l, 1, cb.spx[1], cb.grad));
-          nl += 2;
-        }
-      } else {
-        PhaseTimer tk(h, PH_K_EXPF, cb.st);
-        if (fast) KT_RUN("k_expf_mfma(state)", cb.st, launch_expf_mfma(cb.st, h->kn, cb.R, l.L, cb.X, l.F, nullptr, nseg, l, scrf_spec_state(l), cb.rpc_s, cb.nch_s, cb.slab_s, f32));
-        else KT_RUN("k_expf_gemm(state)", cb.st, launch_expf_gemm(cb.st, cb.R, l.L, cb.X, l.F, nullptr, nseg, l, 0, cb.rpc_s, cb.nch_s, cb.slab_s));
-        tk.stop(1);
-      }
-      if (!sparse(h) && segtrans(h)) {
-        // transition counts of the segment's own window: XI2 rows are windows, no row map
-        if (fast) KT_RUN("k_expf_mfma(trans)", cb.st, launch_expf_mfma(cb.st, h->kn, cb.XI, l.L * l.L, cb.X, l.F, nullptr, nseg, l, scrf_spec_trans(l), cb.rpc_t, cb.nch_t, cb.slab_t, f32));
-        else KT_RUN("k_expf_gemm(trans)", cb.st, launch_expf_gemm(cb.st, cb.XI, l.L * l.L, cb.X, l.F, nullptr, nseg, l, 1, cb.rpc_t, cb.nch_t, cb.slab_t));
-        nl += 1;
-      } else if (!sparse(h) && l.use_tf && !trans_done) {
-        launch_frame_rows(cb.st, bv, u0, u1, l.D, nfr, cb.xrow_next, 1);
-        if (fast) KT_RUN("k_expf_mfma(trans)", cb.st, launch_expf_mfma(cb.st, h->kn, cb.XI, l.L * l.L, cb.X, l.F, cb.xrow_next, nfr, l, scrf_spec_trans(l), cb.rpc_t, cb.nch_t, cb.slab_t, f32));
-        else KT_RUN("k_expf_gemm(trans)", cb.st, launch_expf_gemm(cb.st, cb.XI, l.L * l.L, cb.X, l.F, cb.xrow_next, nfr, l, 1, cb.rpc_t, cb.nch_t, cb.slab_t));
-        nl += 2;
-      }
-      tm.stop(nl);
-    }
-    {
-      PhaseTimer tm(h, PH_REDUCE, cb.st);
-      KernelTimer kt(h, "reductions (k_reduce_slabs, k_atb, k_batch_sums)", cb.st);
-      if (cb.fused) {
-        const uint32_t W0 = b->recipe[0].in_width;
-        const ScrfFusedExpfPlan& plan = cb.expf_plan;
-        if (plan.ndur) {
-          // dense groups [avg |] max | min at columns (5 + g0) W ..; one-hot duration + bias counts from their own slab
-          launch_reduce_slabs(cb.st, cb.slab_s, cb.nch_s, l.L, l, ScrfGemmSpec{0, 0, plan.ncol, 0, 0.0, (5 + plan.g0) * W0, 0}, cb.grad);
-          launch_reduce_slabs(cb.st, cb.slab_d, cb.nch_s, l.L, l, ScrfGemmSpec{0, 0, l.D, (uint32_t)l.use_sb, l.sbv, 8 * W0, 0}, cb.grad);
-        } else launch_reduce_slabs(cb.st, cb.slab_s, cb.nch_s, l.L, l, spec_dense(l, W0), cb.grad);
-        if (!side) launch_reduce_slabs(cb.st, cb.slab_l, cb.nch_l, (cb.la ? 6 : 5) * l.L, l, spec_samples(W0), cb.grad);
-      } else if (cb.hybrid) {
-        const uint32_t W0 = b->recipe[0].in_width;
-        int seg_len = 0;
-        const uint32_t nblk_d = (uint32_t)nutt * lin_z5_segments((uint32_t)nutt, l.L, l.D, t_max, &seg_len);
-        launch_reduce_slabs(cb.st, cb.slab_s, cb.nch_s, l.L, l, spec_stats_x(l, W0), cb.grad);
-        launch_reduce_slabs(cb.st, cb.slab_d, nblk_d, l.L, l, ScrfGemmSpec{0, 0, l.D, (uint32_t)l.use_sb, l.sbv, 8 * W0, 0}, cb.grad);
-        launch_reduce_slabs(cb.st, cb.slab_l, cb.nch_l, 5 * l.L, l, spec_samples(W0), cb.grad);
-      } else if (!sparse(h)) launch_reduce_slabs(cb.st, cb.slab_s, cb.nch_s, l.L, l, scrf_spec_state(l), cb.grad);
-      if (side) HIPCHK(h, hipStreamWaitEvent(cb.st, h->ev_join, 0));   // the side stream's weights are in
-      else if (trans_done || (sparse(h) && l.use_tf)) {}
-      else if (l.use_tf || segtrans(h)) launch_reduce_slabs(cb.st, cb.slab_t, cb.nch_t, l.L * l.L, l, scrf_spec_trans(l), cb.grad);
-      else if (cb.wave) launch_atb(cb.st, l, cb.fA, cb.fB, nfr, cb.rpc_atb, cb.nch_atb, cb.slab_atb, h->d_m0, cb.grad,
-                                   cb.lin ? cb.dl.gsd : nullptr);
-      else launch_reduce_xiacc(cb.st, cb.xi_acc, (uint32_t)nutt, l, cb.grad);
-      launch_batch_sums(cb.st, b->d_numer + u0, b->d_zx + u0, (uint32_t)nutt, cb.sums);
-      kt.stop(4);
-      tm.stop(3);
-    }
-    HIPCHK(h, hipGetLastError());
+  for (size_t ci = 0; ci < plan.n_chunks(); ci++) {
+    bool redo = false;
+    RCCHK(fb_chunk(h, b, plan, ci, nd, latch, &redo));
+    if (redo) return SCRF_OK;
   }
-  if (use2) {
+  if (plan.use2) {
     // join: lane 1's partial gradient and sums are added once, in a fixed order
     HIPCHK(h, hipEventRecord(h->ev_join, h->stream2));
     HIPCHK(h, hipStreamWaitEvent(h->stream, h->ev_join, 0));
     launch_add(h->stream, h->d_stage, h->d_grad2, l.lambda_len);
     launch_add(h->stream, h->d_sums_stage, h->d_sums2, 3);
-    int rc = queue_status(h, b);
-    if (rc != SCRF_OK) return rc;
+    RCCHK(queue_status(h, b));
   }
   if (!l.use_tf && wave_path(h, true)) launch_add_trans_counts(h->stream, b->d_trans_counts, l, h->d_stage);
-  if (h->early_done)   // the transition block was committed (and sent) before the state contraction
-    hipLaunchKernelGGL(k_commit_part, dim3((l.lambda_len + 255) / 256), dim3(256), 0, h->stream, h->d_grad, h->d_stage, l.lambda_len,
-                       l.stride, l.nsf, 0, h->d_sums, h->d_sums_stage, h->d_latch);
-  else
-  hipLaunchKernelGGL(k_commit, dim3((l.lambda_len + 255) / 256), dim3(256), 0, h->stream, h->d_grad, h->d_stage, l.lambda_len,
-                     h->d_sums, h->d_sums_stage, h->d_latch);
-  HIPCHK(h, hipGetLastError());
-  HIPCHK(h, hipEventSynchronize(h->ev_status));
-  latch_decode(h->h_latch, latch);
-  return SCRF_OK;
+  return fb_commit(h, latch);
 }
 
 // One pass over a batch and, where it raised NUMERIC on the wavefront kernels, a second one.  The wavefront recursions take
@@ -2271,9 +2405,7 @@ extern "C" int scrf_fb_batch(scrf_handle h, scrf_batch b, double* numer, double*
   if (!b->d_labels) return fail(h, SCRF_ERR_INVALID, "scrf_fb_batch: the batch carries no labels");
   CallTimer call(h);
   int latch[2] = {0, 0};
-  bool used_lin = false;
-  int rc = run_with_redo(h, latch, [&] { return fb_run(h, b, latch, &used_lin); });
-  if (rc != SCRF_OK) return rc;
+  RCCHK(run_with_redo(h, latch, [&] { return stdseg(h) || nstate(h) ? fb_run_small(h, b, latch) : fb_run(h, b, latch); }));
   call.stop();
   if (latch[0] != 0) return fail(h, latch[0], "utterance %d: %s", latch[1], status_text(latch[0]));
   if (numer || zx) {
@@ -2292,14 +2424,55 @@ static const char* model_type_name(uint32_t mt) {
   return mt == SCRF_STDFRAME ? "stdframe" : mt == SCRF_STDSEG ? "stdseg" : mt == SCRF_STDSEG_NO_DUR ? "stdseg_no_dur"
          : mt == SCRF_STDSEG_NO_DUR_NO_TRANSFTR ? "stdseg_no_dur_no_transftr" : "stdseg_no_dur_no_segtransftr";
 }
-// the models the posterior pass serves: one transition matrix per frame (or one in all), one state per label
-static int post_model_ok(scrf_handle h, const char* fn) {
+// a device array of the handle with room for n elements: grown on demand once the stream has drained, kept until scrf_destroy
+template <class Tp, class Cap>
+static int grow_device(scrf_handle h, Tp** p, Cap* cap, size_t n) {
+  if (n <= *cap) return SCRF_OK;
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  hipFree(*p); *p = nullptr; *cap = 0;
+  HIPCHK(h, hipMalloc((void**)p, sizeof(Tp) * n));
+  *cap = (Cap)n;
+  return SCRF_OK;
+}
+
+// The entry points that serve one transition matrix per frame (or one in all) and one state per label refuse the other
+// models here; `what` names what the entry point computes.
+static int model_ok(scrf_handle h, const char* fn, const char* what) {
   if (h->cfg.model_type == SCRF_STDSEG || h->cfg.model_type == SCRF_STDSEG_NO_DUR)
-    return fail(h, SCRF_ERR_INVALID, "%s: posterior output is not built for the \"%s\" CRF model; use \"stdframe\", "
-                "\"stdseg_no_dur_no_transftr\" or \"stdseg_no_dur_no_segtransftr\"", fn, model_type_name(h->cfg.model_type));
+    return fail(h, SCRF_ERR_INVALID, "%s: %s is not built for the \"%s\" CRF model; use \"stdframe\", "
+                "\"stdseg_no_dur_no_transftr\" or \"stdseg_no_dur_no_segtransftr\"", fn, what, model_type_name(h->cfg.model_type));
   if (h->cfg.num_states > 1)
-    return fail(h, SCRF_ERR_INVALID, "%s: posterior output is built for crf_states = 1 only (this \"%s\" model has crf_states = %u)",
-                fn, model_type_name(h->cfg.model_type), h->cfg.num_states);
+    return fail(h, SCRF_ERR_INVALID, "%s: %s is built for crf_states = 1 only (this \"%s\" model has crf_states = %u)",
+                fn, what, model_type_name(h->cfg.model_type), h->cfg.num_states);
+  return SCRF_OK;
+}
+
+// The chunk driver of the label-free passes (scrf_posteriors_batch, scrf_transcript_batch): scores and the recursion of the
+// handle's precision, chunk by chunk on the engine stream; body(cb, u0, u1, &nl) queues the pass's own kernels behind the
+// recursion and adds their launches to nl.  Nothing that needs labels or feeds the gradient runs: no true scores, numerator,
+// xi, R, counts, staging or commit.  latch[2]: as fb_commit's.
+template <class Body>
+static int label_free_run(scrf_handle h, scrf_batch b, Need nd, int latch[2], Body body) {
+  HIPCHK(h, hipMemsetAsync(b->d_status, 0, sizeof(int) * b->U, h->stream));
+  hipLaunchKernelGGL(k_latch_reset, dim3(1), dim3(1), 0, h->stream, h->d_latch);
+  set_batch_form(h, b, &nd);   // the batch forms of scrf_fb_batch
+  if (!h->lay.use_tf) ensure_m0(h, h->stream);
+  if (sparse(h)) relay_sparse_lambda(h, h->stream);
+  for (uint32_t u0 = 0; u0 < b->U;) {
+    const uint32_t u1 = plan_chunk(h, b, u0, nd);
+    ChunkBufs cb;
+    RCCHK(score_chunk(h, b, u0, u1, nd, &cb, SCORE_PASS));
+    PhaseTimer tm(h, PH_FB, cb.st);
+    uint32_t nl = 0;
+    RCCHK(run_dp(h, b, u0, u1, cb, DpOpts::recursion_only(), &nl));
+    RCCHK(body(cb, u0, u1, &nl));
+    tm.stop(nl);
+    HIPCHK(h, hipGetLastError());
+    u0 = u1;
+  }
+  RCCHK(queue_status(h, b));
+  HIPCHK(h, hipEventSynchronize(h->ev_status));
+  latch_decode(h->h_latch, latch);
   return SCRF_OK;
 }
 
@@ -2310,68 +2483,60 @@ struct PostOut {
   const uint32_t *q_u = nullptr, *q_e = nullptr, *q_lab = nullptr;
   const uint64_t* lab_off = nullptr;   // host
 };
-
-// scores, the recursion of the handle's precision and the posterior-output kernels, chunk by chunk on the engine stream.
-// Nothing that needs labels or feeds the gradient runs: no true scores, numerator, xi, R, counts, staging or commit.
-static int post_run(scrf_handle h, scrf_batch b, const PostOut& po, int latch[2]) {
-  const ScrfLayout& l = h->lay;
-  HIPCHK(h, hipMemsetAsync(b->d_status, 0, sizeof(int) * b->U, h->stream));
-  hipLaunchKernelGGL(k_latch_reset, dim3(1), dim3(1), 0, h->stream, h->d_latch);
-  const bool fast = h->cfg.train_precision >= SCRF_PREC_FAST;
-  const int f32 = h->cfg.train_precision == SCRF_PREC_FAST32;
-  const int frame_model = h->cfg.model_type == SCRF_STDFRAME || h->frame_mass;
-  Need nd{true, false, true, false};
-  nd.ponly = true;
-  nd.plog = !fast;   // SCRF_PREC_EXACT: the log-domain recursion and k_post_occ_log
-  set_batch_form(h, b, &nd);   // the batch forms of scrf_fb_batch
-  ScrfBatchView bv = b->view();
-  if (!l.use_tf) ensure_m0(h, h->stream);
-  if (sparse(h)) relay_sparse_lambda(h, h->stream);
-  for (uint32_t u0 = 0; u0 < b->U;) {
-    const uint32_t u1 = plan_chunk(h, b, u0, nd);
-    ChunkBufs cb;
-    int rc = carve(h, b, u0, u1, nd, &cb, 0);
-    if (rc != SCRF_OK) return rc;
-    cb.lamT_ready = sparse(h);
-    const uint64_t nutt = u1 - u0, nfr = b->frame_off[u1] - b->frame_off[u0];
-    rc = run_scores(h, b, u0, u1, cb, fast, f32);
-    if (rc != SCRF_OK) return rc;
-    PhaseTimer tm(h, PH_FB, cb.st);
-    uint32_t nl = 0;
-    rc = run_dp(h, b, u0, u1, cb, false, &nl, true);
-    if (rc != SCRF_OK) return rc;
-    double* occ = po.occ ? po.occ + b->frame_off[u0] * l.L : nullptr;
-    if (cb.lin) {
-      uint32_t t_max = 0;   // the longest utterance of the chunk: a launch of few utterances splits each into frame segments
-      for (uint64_t u = u0; u < u1; u++) t_max = std::max(t_max, b->T[u]);
-      uint32_t nz = 1;
-      KT_RUN("k_post_occ", cb.st, nz = launch_post_occ(cb.st, l, bv, u0, (uint32_t)nutt, t_max, nfr, cb.S, cb.smax, cb.dl, b->d_zx, b->d_status, occ,
-                      cb.mass_part, cb.mass_s, h->kn.postocc_split ? 1 : 0));
-      if (nz > 1) h->n_post_split++; else h->n_post_whole++;
-      if (post_occ_groups(l) > 1) nl++;   // k_sum_groups
-      KT_RUN("k_mass_check", cb.st, launch_mass_check(cb.st, bv, b->d_frame_u, u0, nfr, l.L, frame_model, 1, cb.dl.a, cb.dl.ga, cb.dl.b, cb.dl.gb,
-                        b->d_zx, cb.mass_s, b->d_status));
-    } else {
-      KT_RUN("k_post_occ_log", cb.st, launch_post_occ_log(cb.st, l, bv, b->d_frame_u, u0, nfr, cb.AD, cb.beta, b->d_zx, b->d_status, occ, cb.mass_s));
-      KT_RUN("k_mass_check", cb.st, launch_mass_check(cb.st, bv, b->d_frame_u, u0, nfr, l.L, frame_model, 0, cb.alpha, nullptr, cb.beta, nullptr,
-                        b->d_zx, cb.mass_s, b->d_status));
-    }
-    nl += 2;
-    if (po.end) HIPCHK(h, hipMemcpyAsync(po.end + b->frame_off[u0], cb.mass_s, sizeof(double) * nfr, hipMemcpyDeviceToDevice, cb.st));
-    if (po.seg) {
-      const uint64_t q0 = po.lab_off[u0], nq = po.lab_off[u1] - q0;
-      KT_RUN("k_seg_post", cb.st, launch_seg_post(cb.st, l, bv, u0, po.q_u, po.q_e, po.q_lab, q0, nq, cb.lin ? 1 : 0, cb.lin ? cb.S : cb.AD, cb.smax,
-                      cb.dl, cb.beta, b->d_zx, po.seg));
-      nl++;
-    }
-    tm.stop(nl);
-    HIPCHK(h, hipGetLastError());
-    u0 = u1;
+// The result buffer of a posterior / transcript call (the handle's, scrf_abi.h), carved as [occ | end | n_extra doubles |
+// seg | the queries q]: *po receives the parts the caller wants, *extra the extra doubles; the queries are uploaded.
+static int post_out_carve(scrf_handle h, scrf_batch b, bool occ, bool end, bool seg, const std::vector<uint32_t>& q, uint64_t nq,
+                          const uint64_t* lab_off, uint64_t n_extra, PostOut* po, double** extra) {
+  const uint64_t nF = b->frame_off[b->U];
+  const size_t by_occ = occ ? pad256(sizeof(double) * nF * h->lay.L) : 0, by_end = end ? pad256(sizeof(double) * nF) : 0;
+  const size_t by_seg = pad256(sizeof(double) * nq), by_q = pad256(sizeof(uint32_t) * 3 * nq), by_x = pad256(sizeof(double) * n_extra);
+  RCCHK(grow_device(h, &h->post_buf, &h->post_cap, by_occ + by_end + by_x + by_seg + by_q + 256));
+  char* pb = h->post_buf;
+  if (occ) po->occ = (double*)pb;
+  pb += by_occ;
+  if (end) po->end = (double*)pb;
+  pb += by_end;
+  if (extra) *extra = (double*)pb;
+  pb += by_x;
+  if (seg && nq) {
+    po->seg = (double*)pb;
+    uint32_t* dq = (uint32_t*)(pb + by_seg);
+    HIPCHK(h, hipMemcpyAsync(dq, q.data(), sizeof(uint32_t) * 3 * nq, hipMemcpyHostToDevice, h->stream));
+    po->q_u = dq; po->q_e = dq + nq; po->q_lab = dq + 2 * nq;
+    po->lab_off = lab_off;
   }
-  int rc = queue_status(h, b);
-  if (rc != SCRF_OK) return rc;
-  HIPCHK(h, hipEventSynchronize(h->ev_status));
-  latch_decode(h->h_latch, latch);
+  return SCRF_OK;
+}
+
+// the posterior-output kernels of a chunk, behind its recursion: the free occupancy walk, the mass check, the segment queries
+static int post_chunk(scrf_handle h, scrf_batch b, const PostOut& po, ChunkBufs& cb, uint32_t u0, uint32_t u1, uint32_t* nl) {
+  const ScrfLayout& l = h->lay;
+  const uint32_t nutt = u1 - u0;
+  const uint64_t nfr = b->frame_off[u1] - b->frame_off[u0];
+  ScrfBatchView bv = b->view();
+  double* occ = po.occ ? po.occ + b->frame_off[u0] * l.L : nullptr;
+  if (cb.lin) {
+    const uint32_t t_max = longest_utt(b, u0, u1);
+    uint32_t nz = 1;
+    KT_RUN("k_post_occ", cb.st, nz = launch_post_occ(cb.st, l, bv, u0, nutt, t_max, nfr, cb.S, cb.smax, cb.dl, b->d_zx, b->d_status, occ,
+                    cb.mass_part, cb.mass_s, h->kn.postocc_split ? 1 : 0));
+    if (nz > 1) h->n_post_split++; else h->n_post_whole++;
+    if (post_occ_groups(l) > 1) *nl += 1;   // k_sum_groups
+    KT_RUN("k_mass_check", cb.st, launch_mass_check(cb.st, bv, b->d_frame_u, u0, nfr, l.L, frame_mass_model(h), 1, cb.dl.a, cb.dl.ga, cb.dl.b, cb.dl.gb,
+                      b->d_zx, cb.mass_s, b->d_status));
+  } else {   // SCRF_PREC_EXACT, or the redo of a pass that raised NUMERIC
+    KT_RUN("k_post_occ_log", cb.st, launch_post_occ_log(cb.st, l, bv, b->d_frame_u, u0, nfr, cb.AD, cb.beta, b->d_zx, b->d_status, occ, cb.mass_s));
+    KT_RUN("k_mass_check", cb.st, launch_mass_check(cb.st, bv, b->d_frame_u, u0, nfr, l.L, frame_mass_model(h), 0, cb.alpha, nullptr, cb.beta, nullptr,
+                      b->d_zx, cb.mass_s, b->d_status));
+  }
+  *nl += 2;
+  if (po.end) HIPCHK(h, hipMemcpyAsync(po.end + b->frame_off[u0], cb.mass_s, sizeof(double) * nfr, hipMemcpyDeviceToDevice, cb.st));
+  if (po.seg) {
+    const uint64_t q0 = po.lab_off[u0], nq = po.lab_off[u1] - q0;
+    KT_RUN("k_seg_post", cb.st, launch_seg_post(cb.st, l, bv, u0, po.q_u, po.q_e, po.q_lab, q0, nq, cb.lin ? 1 : 0, cb.lin ? cb.S : cb.AD, cb.smax,
+                    cb.dl, cb.beta, b->d_zx, po.seg));
+    *nl += 1;
+  }
   return SCRF_OK;
 }
 
@@ -2409,41 +2574,20 @@ static int seg_queries(scrf_handle h, scrf_batch b, const char* fn, const uint32
 extern "C" int scrf_posteriors_batch(scrf_handle h, scrf_batch b, double* zx, double* frame_post, double* end_post,
                                      const uint32_t* seg_labels, const uint64_t* lab_off, double* seg_post) {
   if (!h || !b) return SCRF_ERR_INVALID;
-  int rc = post_model_ok(h, "scrf_posteriors_batch");
-  if (rc != SCRF_OK) return rc;
+  RCCHK(model_ok(h, "scrf_posteriors_batch", "posterior output"));
   HIPCHK(h, hipSetDevice(h->device));
   const ScrfLayout& l = h->lay;
   const uint64_t nF = b->frame_off[b->U];
   std::vector<uint32_t> q;   // [3][nq]: utterance, end frame, label value
   uint64_t nq = 0;
-  rc = seg_queries(h, b, "scrf_posteriors_batch", seg_labels, lab_off, seg_post != nullptr, &q, &nq);
-  if (rc != SCRF_OK) return rc;
-  const size_t by_occ = frame_post ? pad256(sizeof(double) * nF * l.L) : 0, by_end = end_post ? pad256(sizeof(double) * nF) : 0;
-  const size_t by_seg = pad256(sizeof(double) * nq), by_q = pad256(sizeof(uint32_t) * 3 * nq);
-  const size_t need = by_occ + by_end + by_seg + by_q + 256;
-  if (need > h->post_cap) {   // grown on demand, kept until scrf_destroy (scrf_abi.h)
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    hipFree(h->post_buf); h->post_buf = nullptr; h->post_cap = 0;
-    HIPCHK(h, hipMalloc((void**)&h->post_buf, need));
-    h->post_cap = need;
-  }
+  RCCHK(seg_queries(h, b, "scrf_posteriors_batch", seg_labels, lab_off, seg_post != nullptr, &q, &nq));
   PostOut po;
-  char* pb = h->post_buf;
-  if (frame_post) po.occ = (double*)pb;
-  pb += by_occ;
-  if (end_post) po.end = (double*)pb;
-  pb += by_end;
-  if (seg_post && nq) {
-    po.seg = (double*)pb;
-    uint32_t* dq = (uint32_t*)(pb + by_seg);
-    HIPCHK(h, hipMemcpyAsync(dq, q.data(), sizeof(uint32_t) * 3 * nq, hipMemcpyHostToDevice, h->stream));
-    po.q_u = dq; po.q_e = dq + nq; po.q_lab = dq + 2 * nq;
-    po.lab_off = lab_off;
-  }
+  RCCHK(post_out_carve(h, b, frame_post, end_post, seg_post, q, nq, lab_off, 0, &po, nullptr));
   CallTimer call(h);
   int latch[2] = {0, 0};
-  rc = run_with_redo(h, latch, [&] { return post_run(h, b, po, latch); });   // the redo runs k_post_occ_log
-  if (rc != SCRF_OK) return rc;
+  RCCHK(run_with_redo(h, latch, [&] {   // the redo runs k_post_occ_log
+    return label_free_run(h, b, Need::posterior(prec_fast(h)), latch, [&](ChunkBufs& cb, uint32_t u0, uint32_t u1, uint32_t* nl) { return post_chunk(h, b, po, cb, u0, u1, nl); });
+  }));
   call.stop();
   if (latch[0] != 0) return fail(h, latch[0], "utterance %d: %s", latch[1], status_text(latch[0]));
   if (zx) HIPCHK(h, hipMemcpyAsync(zx, b->d_zx, sizeof(double) * b->U, hipMemcpyDeviceToHost, h->stream));
@@ -2464,8 +2608,7 @@ extern "C" int scrf_add_grad(scrf_handle h, const double* g, uint32_t n) {
     g = h->xbuf.data();
     n = h->lay.lambda_len;
   }
-  int rc = ensure_scratch(h, sizeof(double) * n);
-  if (rc != SCRF_OK) return rc;
+  RCCHK(ensure_scratch(h, sizeof(double) * n));
   HIPCHK(h, hipMemcpyAsync(h->scratch, g, sizeof(double) * n, hipMemcpyHostToDevice, h->stream));
   launch_add(h->stream, h->d_grad, (const double*)h->scratch, n);
   HIPCHK(h, hipStreamSynchronize(h->stream));
@@ -2505,13 +2648,11 @@ static int read_zx(scrf_handle h, scrf_batch b, uint32_t u, double* Zx) {
 // Second attempt: the workgroup kernel (reference LogMath) when the wavefront recursion gave up.  A label out of range
 // does not stop a hook that reads no label.
 static int hook_fb(scrf_handle h, scrf_batch b, uint32_t u, const char* fn, ChunkBufs* cb) {
-  const Need nd{true, false, true, false};
   for (;;) {
     *cb = ChunkBufs();
-    int rc = carve(h, b, u, u + 1, nd, cb);
-    if (rc == SCRF_OK) rc = run_scores(h, b, u, u + 1, *cb);
+    int rc = score_chunk(h, b, u, u + 1, Need::recursion(), cb);
     if (rc == SCRF_OK && hipMemsetAsync(b->d_status, 0, sizeof(int) * b->U, h->stream) != hipSuccess) rc = fail(h, SCRF_ERR_HIP, "%s: memset failed", fn);
-    if (rc == SCRF_OK) rc = run_dp(h, b, u, u + 1, *cb, false, nullptr);
+    if (rc == SCRF_OK) rc = run_dp(h, b, u, u + 1, *cb, DpOpts(), nullptr);
     int st = 0;
     if (rc == SCRF_OK && hipMemcpyAsync(&st, b->d_status + u, sizeof(int), hipMemcpyDeviceToHost, h->stream) != hipSuccess) rc = fail(h, SCRF_ERR_HIP, "%s: status copy failed", fn);
     if (rc == SCRF_OK && hipStreamSynchronize(h->stream) != hipSuccess) rc = fail(h, SCRF_ERR_HIP, "%s: synchronize failed", fn);
@@ -2535,16 +2676,11 @@ struct DevBuf {
 };
 
 extern "C" int scrf_windows(scrf_handle h, scrf_batch b, uint32_t u, float* out) {
-  int rc = check_u(h, b, u, "scrf_windows");
-  if (rc != SCRF_OK) return rc;
+  RCCHK(check_u(h, b, u, "scrf_windows"));
   if (!out) return SCRF_ERR_INVALID;
   HIPCHK(h, hipSetDevice(h->device));
-  Need nd{false, false, false, false};
   ChunkBufs cb;
-  rc = carve(h, b, u, u + 1, nd, &cb);
-  if (rc != SCRF_OK) return rc;
-  rc = run_scores(h, b, u, u + 1, cb);
-  if (rc != SCRF_OK) return rc;
+  RCCHK(score_chunk(h, b, u, u + 1, Need::scores(), &cb));
   uint64_t nseg = b->seg_off[u + 1] - b->seg_off[u];
   HIPCHK(h, hipMemcpyAsync(out, cb.X, sizeof(float) * nseg * h->lay.F, hipMemcpyDeviceToHost, h->stream));
   HIPCHK(h, hipStreamSynchronize(h->stream));
@@ -2553,28 +2689,20 @@ extern "C" int scrf_windows(scrf_handle h, scrf_batch b, uint32_t u, float* out)
 
 static int copy_M(scrf_handle h, const ChunkBufs& cb, uint32_t T, double* M) {
   const size_t LL = (size_t)h->lay.L * h->lay.L;
-  if (cb.m_per_frame == 2) {   // STDSEG_NO_DUR: one matrix per window
-    HIPCHK(h, hipMemcpyAsync(M, cb.M, sizeof(double) * scrf_seg_base(T, h->lay.D) * LL, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-  } else if (cb.m_per_frame) {
-    HIPCHK(h, hipMemcpyAsync(M, cb.M, sizeof(double) * T * LL, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-  } else {
-    HIPCHK(h, hipMemcpyAsync(M, cb.M, sizeof(double) * LL, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    for (uint32_t t = 1; t < T; t++) memcpy(M + t * LL, M, sizeof(double) * LL);
-  }
+  // matrices on the device: one per window (STDSEG_NO_DUR), one per frame, or one in all (copied out T times)
+  const size_t n = cb.m_per_frame == 2 ? scrf_seg_base(T, h->lay.D) : cb.m_per_frame ? T : 1;
+  HIPCHK(h, hipMemcpyAsync(M, cb.M, sizeof(double) * n * LL, hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  if (!cb.m_per_frame) for (uint32_t t = 1; t < T; t++) memcpy(M + t * LL, M, sizeof(double) * LL);
   return SCRF_OK;
 }
 
 extern "C" int scrf_scores(scrf_handle h, scrf_batch b, uint32_t u, double* S, double* M) {
-  int rc = check_u(h, b, u, "scrf_scores");
-  if (rc != SCRF_OK) return rc;
+  RCCHK(check_u(h, b, u, "scrf_scores"));
   HIPCHK(h, hipSetDevice(h->device));
   if (nstate(h)) {   // S [T][nLabs]; M [T][2*nLabs + P*P]: self transitions | c -> c+1 | end state of p -> start state of q
     SmallBufs sm;
-    rc = hook_small_chunk(h, b, u, &sm);
-    if (rc != SCRF_OK) return rc;
+    RCCHK(hook_small_chunk(h, b, u, &sm));
     const NstateBufs& nb = sm.ns;
     const uint64_t T = b->T[u], L = h->lay.L, P = L / h->lay.K, w = 2 * L + P * P;
     if (S) HIPCHK(h, hipMemcpyAsync(S, nb.S, sizeof(double) * T * L, hipMemcpyDeviceToHost, h->stream));
@@ -2588,8 +2716,7 @@ extern "C" int scrf_scores(scrf_handle h, scrf_batch b, uint32_t u, double* S, d
   }
   if (stdseg(h)) {   // S [N_seg][nActualLabs], M [N_seg][nLabs][nActualLabs]
     SmallBufs sm;
-    rc = hook_small_chunk(h, b, u, &sm);
-    if (rc != SCRF_OK) return rc;
+    RCCHK(hook_small_chunk(h, b, u, &sm));
     const StdsegBufs& sb = sm.sg;
     const uint64_t ns = b->seg_off[u + 1] - b->seg_off[u];
     const uint32_t La = stdseg_La(h);
@@ -2598,12 +2725,8 @@ extern "C" int scrf_scores(scrf_handle h, scrf_batch b, uint32_t u, double* S, d
     HIPCHK(h, hipStreamSynchronize(h->stream));
     return SCRF_OK;
   }
-  Need nd{false, false, false, false};
   ChunkBufs cb;
-  rc = carve(h, b, u, u + 1, nd, &cb);
-  if (rc != SCRF_OK) return rc;
-  rc = run_scores(h, b, u, u + 1, cb);
-  if (rc != SCRF_OK) return rc;
+  RCCHK(score_chunk(h, b, u, u + 1, Need::scores(), &cb));
   uint64_t nseg = b->seg_off[u + 1] - b->seg_off[u];
   if (S) HIPCHK(h, hipMemcpyAsync(S, cb.S, sizeof(double) * nseg * h->lay.L, hipMemcpyDeviceToHost, h->stream));
   HIPCHK(h, hipStreamSynchronize(h->stream));
@@ -2613,35 +2736,19 @@ extern "C" int scrf_scores(scrf_handle h, scrf_batch b, uint32_t u, double* S, d
 
 extern "C" int scrf_forward_backward(scrf_handle h, scrf_batch b, uint32_t u, uint32_t prec, double* alpha_dur,
                                      double* alpha, double* beta, double* zx) {
-  int rc = check_u(h, b, u, "scrf_forward_backward");
-  if (rc != SCRF_OK) return rc;
+  RCCHK(check_u(h, b, u, "scrf_forward_backward"));
   if (prec != SCRF_PREC_EXACT) return fail(h, SCRF_ERR_INVALID, "scrf_forward_backward: the node-value hook runs at SCRF_PREC_EXACT only");
   HIPCHK(h, hipSetDevice(h->device));
-  if (nstate(h)) {   // alpha, beta: [T][nLabs]; alpha_dur is not written
+  if (nstate(h) || stdseg(h)) {
+    // n-state: alpha, beta [T][nLabs], alpha_dur is not written; STDSEG: alpha_dur and beta, the nodes' alpha / beta over full
+    // labels [N_seg][nActualLabs], `alpha` is not written
     SmallBufs sm;
-    rc = hook_small_chunk(h, b, u, &sm);
-    if (rc != SCRF_OK) return rc;
-    const NstateBufs& nb = sm.ns;
-    const uint64_t n = (uint64_t)b->T[u] * h->lay.L;
+    RCCHK(hook_small_chunk(h, b, u, &sm));
+    const uint64_t n = nstate(h) ? (uint64_t)b->T[u] * h->lay.L : (b->seg_off[u + 1] - b->seg_off[u]) * stdseg_La(h);
+    double* a_out = nstate(h) ? alpha : alpha_dur;
     int st = 0;
-    if (alpha) HIPCHK(h, hipMemcpyAsync(alpha, nb.alpha, sizeof(double) * n, hipMemcpyDeviceToHost, h->stream));
-    if (beta) HIPCHK(h, hipMemcpyAsync(beta, nb.beta, sizeof(double) * n, hipMemcpyDeviceToHost, h->stream));
-    if (zx) HIPCHK(h, hipMemcpyAsync(zx, b->d_zx + u, sizeof(double), hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(h, hipMemcpyAsync(&st, b->d_status + u, sizeof(int), hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    if (st != SCRF_OK) return fail(h, st, "utterance %u: numeric failure in forward-backward", u);
-    return SCRF_OK;
-  }
-  if (stdseg(h)) {   // alpha_dur and beta: the nodes' alpha / beta over full labels, [N_seg][nActualLabs]; `alpha` is not written
-    SmallBufs sm;
-    rc = hook_small_chunk(h, b, u, &sm);
-    if (rc != SCRF_OK) return rc;
-    const StdsegBufs& sb = sm.sg;
-    const uint64_t ns = b->seg_off[u + 1] - b->seg_off[u];
-    const uint32_t La = stdseg_La(h);
-    int st = 0;
-    if (alpha_dur) HIPCHK(h, hipMemcpyAsync(alpha_dur, sb.alpha, sizeof(double) * ns * La, hipMemcpyDeviceToHost, h->stream));
-    if (beta) HIPCHK(h, hipMemcpyAsync(beta, sb.beta, sizeof(double) * ns * La, hipMemcpyDeviceToHost, h->stream));
+    if (a_out) HIPCHK(h, hipMemcpyAsync(a_out, nstate(h) ? sm.ns.alpha : sm.sg.alpha, sizeof(double) * n, hipMemcpyDeviceToHost, h->stream));
+    if (beta) HIPCHK(h, hipMemcpyAsync(beta, nstate(h) ? sm.ns.beta : sm.sg.beta, sizeof(double) * n, hipMemcpyDeviceToHost, h->stream));
     if (zx) HIPCHK(h, hipMemcpyAsync(zx, b->d_zx + u, sizeof(double), hipMemcpyDeviceToHost, h->stream));
     HIPCHK(h, hipMemcpyAsync(&st, b->d_status + u, sizeof(int), hipMemcpyDeviceToHost, h->stream));
     HIPCHK(h, hipStreamSynchronize(h->stream));
@@ -2652,8 +2759,7 @@ extern "C" int scrf_forward_backward(scrf_handle h, scrf_batch b, uint32_t u, ui
   const uint64_t nseg = b->seg_off[u + 1] - b->seg_off[u];
   const uint32_t T = b->T[u];
   ChunkBufs cb;
-  rc = hook_fb(h, b, u, "scrf_forward_backward", &cb);
-  if (rc != SCRF_OK) return rc;
+  RCCHK(hook_fb(h, b, u, "scrf_forward_backward", &cb));
   if (alpha_dur) HIPCHK(h, hipMemcpyAsync(alpha_dur, cb.AD, sizeof(double) * nseg * l.L, hipMemcpyDeviceToHost, h->stream));
   if (alpha) HIPCHK(h, hipMemcpyAsync(alpha, cb.alpha, sizeof(double) * T * l.L, hipMemcpyDeviceToHost, h->stream));
   if (beta) HIPCHK(h, hipMemcpyAsync(beta, cb.beta, sizeof(double) * T * l.L, hipMemcpyDeviceToHost, h->stream));
@@ -2663,17 +2769,14 @@ extern "C" int scrf_forward_backward(scrf_handle h, scrf_batch b, uint32_t u, ui
 }
 
 extern "C" int scrf_seg_posteriors(scrf_handle h, scrf_batch b, uint32_t u, double* gamma) {
-  int rc = check_u(h, b, u, "scrf_seg_posteriors");
-  if (rc != SCRF_OK) return rc;
+  RCCHK(check_u(h, b, u, "scrf_seg_posteriors"));
   if (!gamma) return SCRF_ERR_INVALID;
-  rc = post_model_ok(h, "scrf_seg_posteriors");
-  if (rc != SCRF_OK) return rc;
+  RCCHK(model_ok(h, "scrf_seg_posteriors", "posterior output"));
   HIPCHK(h, hipSetDevice(h->device));
   const ScrfLayout& l = h->lay;
   const uint64_t nseg = b->seg_off[u + 1] - b->seg_off[u];
   ChunkBufs cb;
-  rc = hook_fb(h, b, u, "scrf_seg_posteriors", &cb);
-  if (rc != SCRF_OK) return rc;
+  RCCHK(hook_fb(h, b, u, "scrf_seg_posteriors", &cb));
   launch_gamma_log(h->stream, l, b->T[u], cb.AD, cb.beta, b->d_zx + u, cb.AD);
   HIPCHK(h, hipMemcpyAsync(gamma, cb.AD, sizeof(double) * nseg * l.L, hipMemcpyDeviceToHost, h->stream));
   HIPCHK(h, hipStreamSynchronize(h->stream));
@@ -2686,8 +2789,7 @@ extern "C" int scrf_seg_posteriors(scrf_handle h, scrf_batch b, uint32_t u, doub
 // ---------------------------------------------------------------------------------------------
 extern "C" int scrf_lattice_arcs(scrf_handle h, scrf_batch b, uint32_t u, int norm, scrf_arc* arcs, uint64_t* n_arcs,
                                  uint32_t* n_states, int32_t* final_state) {
-  int rc = check_u(h, b, u, "scrf_lattice_arcs");
-  if (rc != SCRF_OK) return rc;
+  RCCHK(check_u(h, b, u, "scrf_lattice_arcs"));
   HIPCHK(h, hipSetDevice(h->device));
   if (nstate(h)) {   // decoders/CRF_LatticeBuilder.h nStateBuildLattice
     const uint32_t T = b->T[u], L = h->lay.L;
@@ -2697,11 +2799,10 @@ extern "C" int scrf_lattice_arcs(scrf_handle h, scrf_batch b, uint32_t u, int no
     if (final_state) *final_state = (int32_t)(L * T + 1);
     if (!arcs) return SCRF_OK;
     SmallBufs sm;
-    rc = hook_small_chunk(h, b, u, &sm);
-    if (rc != SCRF_OK) return rc;
+    RCCHK(hook_small_chunk(h, b, u, &sm));
     const NstateBufs& nb = sm.ns;
     double Zx = 0.0;
-    if (norm && (rc = read_zx(h, b, u, &Zx)) != SCRF_OK) return rc;
+    if (norm) RCCHK(read_zx(h, b, u, &Zx));
     const float final_w = norm ? (float)Zx : 0.0f;
     DevBuf<scrf_arc> d_arcs;
     HIPCHK(h, d_arcs.alloc(na));
@@ -2719,11 +2820,10 @@ extern "C" int scrf_lattice_arcs(scrf_handle h, scrf_batch b, uint32_t u, int no
     if (final_state) *final_state = (int32_t)(1 + ns * La);
     if (!arcs) return SCRF_OK;
     SmallBufs sm;
-    rc = hook_small_chunk(h, b, u, &sm);
-    if (rc != SCRF_OK) return rc;
+    RCCHK(hook_small_chunk(h, b, u, &sm));
     const StdsegBufs& sb = sm.sg;
     double Zx = 0.0;
-    if (norm && (rc = read_zx(h, b, u, &Zx)) != SCRF_OK) return rc;
+    if (norm) RCCHK(read_zx(h, b, u, &Zx));
     const float final_w = norm ? (float)(-Zx) : -0.0f;
     std::vector<uint64_t> off;
     stdseg_row_arc_offsets(T, La, h->lay.D, &off);
@@ -2749,21 +2849,15 @@ extern "C" int scrf_lattice_arcs(scrf_handle h, scrf_batch b, uint32_t u, int no
   if (n_states) *n_states = (frame_model || segtrans(h)) ? l.L * T + 2 : (uint32_t)scrf_node_start_state(T, l.L) + 1;
   if (final_state) *final_state = (frame_model || segtrans(h)) ? (int32_t)(l.L * T + 1) : scrf_node_start_state(T, l.L);
   if (!arcs) return SCRF_OK;
-  Need nd{norm != 0, false, false, false};
   ChunkBufs cb;
-  rc = carve(h, b, u, u + 1, nd, &cb);
-  if (rc != SCRF_OK) return rc;
-  rc = run_scores(h, b, u, u + 1, cb);
-  if (rc != SCRF_OK) return rc;
+  RCCHK(score_chunk(h, b, u, u + 1, Need::alpha_sum(norm != 0), &cb));
   float final_w = frame_model ? 0.0f : -0.0f;
   if (norm) {
     // Zx = -computeAlphaSum(): final arcs carry -Zx (segmental, :371,397) / Zx (frame, CRF_LatticeBuilder.h:191-198)
     HIPCHK(h, hipMemsetAsync(b->d_status, 0, sizeof(int) * b->U, h->stream));
-    rc = run_dp(h, b, u, u + 1, cb, false, nullptr);
-    if (rc != SCRF_OK) return rc;
+    RCCHK(run_dp(h, b, u, u + 1, cb, DpOpts(), nullptr));
     double Zx = 0.0;
-    rc = read_zx(h, b, u, &Zx);
-    if (rc != SCRF_OK) return rc;
+    RCCHK(read_zx(h, b, u, &Zx));
     final_w = frame_model ? (float)Zx : (float)(-Zx);
   }
   DevBuf<scrf_arc> d_arcs;
@@ -2808,12 +2902,7 @@ extern "C" int scrf_lattice_arcs(scrf_handle h, scrf_batch b, uint32_t u, int no
 extern "C" int scrf_lattice_prune_batch(scrf_handle h, scrf_batch b, double beam, uint64_t* arc_off, double* best_cost) {
   if (!h || !b || !arc_off) return SCRF_ERR_INVALID;
   h->lp_batch = nullptr;   // whatever happens, the previous result is gone
-  if (h->cfg.model_type == SCRF_STDSEG || h->cfg.model_type == SCRF_STDSEG_NO_DUR)
-    return fail(h, SCRF_ERR_INVALID, "scrf_lattice_prune_batch: the lattice beam is not built for the \"%s\" CRF model; use \"stdframe\", "
-                "\"stdseg_no_dur_no_transftr\" or \"stdseg_no_dur_no_segtransftr\"", model_type_name(h->cfg.model_type));
-  if (h->cfg.num_states > 1)
-    return fail(h, SCRF_ERR_INVALID, "scrf_lattice_prune_batch: the lattice beam is built for crf_states = 1 only (this \"%s\" model has crf_states = %u)",
-                model_type_name(h->cfg.model_type), h->cfg.num_states);
+  RCCHK(model_ok(h, "scrf_lattice_prune_batch", "the lattice beam"));
   if (!(beam > 0.0) || !std::isfinite(beam))
     return fail(h, SCRF_ERR_INVALID, "scrf_lattice_prune_batch: the beam must be finite and > 0 (got %g)", beam);
   const ScrfLayout& l = h->lay;
@@ -2823,32 +2912,22 @@ extern "C" int scrf_lattice_prune_batch(scrf_handle h, scrf_batch b, double beam
   const bool frame_model = h->cfg.model_type == SCRF_STDFRAME;
   const uint32_t U = b->U;
   const size_t by_best = pad256(sizeof(double) * U), need_meta = by_best + pad256(sizeof(uint64_t) * (U + 1));
-  if (need_meta > h->lp_meta_cap) {
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    hipFree(h->lp_meta); h->lp_meta = nullptr; h->lp_meta_cap = 0;
-    HIPCHK(h, hipMalloc((void**)&h->lp_meta, need_meta));
-    h->lp_meta_cap = need_meta;
-  }
+  RCCHK(grow_device(h, &h->lp_meta, &h->lp_meta_cap, need_meta));
   double* d_best = (double*)h->lp_meta;
   uint64_t* d_uoff = (uint64_t*)(h->lp_meta + by_best);
   CallTimer call(h);
   h->n_lp_calls++;
-  Need nd{false, false, false, false};
-  nd.lat = true;
+  const Need nd = Need::lattice();
   ScrfBatchView bv = b->view();
   uint64_t total = 0;   // kept arcs of the chunks done
   for (uint32_t u0 = 0; u0 < U;) {
     const uint32_t u1 = plan_chunk(h, b, u0, nd);
     ChunkBufs cb;
-    int rc = carve(h, b, u0, u1, nd, &cb);
-    if (rc != SCRF_OK) return rc;
-    rc = run_scores(h, b, u0, u1, cb);
-    if (rc != SCRF_OK) return rc;
+    RCCHK(score_chunk(h, b, u0, u1, nd, &cb));
     h->n_lp_chunks++;
     const uint32_t nutt = u1 - u0;
     const uint64_t nfr = b->frame_off[u1] - b->frame_off[u0], n_nodes = nfr + nutt;
-    uint32_t t_max = 0;
-    for (uint32_t u = u0; u < u1; u++) t_max = std::max(t_max, b->T[u]);
+    const uint32_t t_max = longest_utt(b, u0, u1);
     cb.lat.best = d_best;
     KT_RUN("k_lat_sweep", cb.st, launch_lat_sweep(cb.st, l, bv, u0, nutt, cb.S, cb.M, cb.m_per_frame, frame_model, cb.lat));
     KT_RUN("k_lat_count", cb.st, launch_lat_count(cb.st, l, bv, u0, nutt, t_max, cb.S, cb.M, cb.m_per_frame, frame_model, cb.lat, beam, cb.lat_counts));
@@ -2925,10 +3004,8 @@ static int decode_chunks(scrf_handle h, scrf_batch b, const Need& nd, Search&& s
     if (fast) {
       const uint32_t u1 = plan_chunk(h, b, u0, ndf);
       ChunkBufs cb;
-      rc = carve(h, b, u0, u1, ndf, &cb);
-      if (rc != SCRF_OK) break;
-      ensure_m0(h, cb.st);
-      rc = run_scores(h, b, u0, u1, cb);
+      ensure_m0(h, h->stream);
+      rc = score_chunk(h, b, u0, u1, ndf, &cb);
       if (rc != SCRF_OK) break;
       uint32_t n_fix = 0;
       HIPCHK(h, hipMemcpyAsync(&n_fix, cb.fix_cnt, sizeof(uint32_t), hipMemcpyDeviceToHost, h->stream));
@@ -2949,9 +3026,7 @@ static int decode_chunks(scrf_handle h, scrf_batch b, const Need& nd, Search&& s
     do {
       const uint32_t u1 = std::min(fast ? u_end : b->U, plan_chunk(h, b, u0, nd));
       ChunkBufs cb;
-      rc = carve(h, b, u0, u1, nd, &cb);
-      if (rc != SCRF_OK) break;
-      rc = run_scores(h, b, u0, u1, cb);
+      rc = score_chunk(h, b, u0, u1, nd, &cb);
       if (rc != SCRF_OK) break;
       PhaseTimer tm(h, PH_VIT);
       search(cb, u0, u1, false);
@@ -3027,7 +3102,7 @@ extern "C" int scrf_viterbi_batch(scrf_handle h, scrf_batch b, uint32_t* seg_lab
     const uint32_t n_lab = nstate(h) ? l.L : stdseg_La(h);
     HIPCHK(h, hipMemsetAsync(b->d_status, 0, sizeof(int) * b->U, h->stream));
     for (uint32_t u0 = 0; u0 < b->U;) {
-      const uint32_t u1 = nstate(h) ? nstate_plan_chunk(h, b, u0, true) : stdseg_plan_chunk(h, b, u0, true);
+      const uint32_t u1 = small_plan_chunk(h, b, u0, true);
       SmallBufs sm;
       rc = run_small_chunk(h, b, u0, u1, &sm);
       if (rc != SCRF_OK) break;
@@ -3046,7 +3121,7 @@ extern "C" int scrf_viterbi_batch(scrf_handle h, scrf_batch b, uint32_t* seg_lab
     }
   }
   else
-    rc = decode_chunks(h, b, Need{false, false, false, true}, [&](const ChunkBufs& cb, uint32_t u0, uint32_t u1, bool fast) {
+    rc = decode_chunks(h, b, Need::viterbi(), [&](const ChunkBufs& cb, uint32_t u0, uint32_t u1, bool fast) {
       if (fast && viterbi_fast_supported(l))
         launch_viterbi_fast(h->stream, h->kn, l, b->view(), u0, u1 - u0, cb.Wn, cb.M, cb.bp_b, cb.bp_e, d_lab, d_n, d_cost);
       else if (fast)
@@ -3064,18 +3139,8 @@ extern "C" int scrf_viterbi_batch(scrf_handle h, scrf_batch b, uint32_t* seg_lab
 // uploaded once per call into buffers kept across calls (scrf_align_batch, scrf_transcript_batch)
 static int upload_transcripts(scrf_handle h, uint32_t U, const uint32_t* phones, const uint64_t* phone_off, const uint64_t* cell_off) {
   const uint64_t NP = phone_off[U];
-  if (NP > h->al_cap_ph) {
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    hipFree(h->al_ph); h->al_ph = nullptr; h->al_cap_ph = 0;
-    HIPCHK(h, hipMalloc((void**)&h->al_ph, sizeof(uint32_t) * NP));
-    h->al_cap_ph = NP;
-  }
-  if (U + 1 > h->al_cap_u) {
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    hipFree(h->al_off); h->al_off = nullptr; h->al_cap_u = 0;
-    HIPCHK(h, hipMalloc((void**)&h->al_off, sizeof(uint64_t) * 2 * (U + 1)));
-    h->al_cap_u = U + 1;
-  }
+  RCCHK(grow_device(h, &h->al_ph, &h->al_cap_ph, NP));
+  RCCHK(grow_device(h, &h->al_off, &h->al_cap_off, 2 * ((size_t)U + 1)));   // two offset arrays
   if (NP) HIPCHK(h, hipMemcpyAsync(h->al_ph, phones, sizeof(uint32_t) * NP, hipMemcpyHostToDevice, h->stream));
   HIPCHK(h, hipMemcpyAsync(h->al_off, phone_off, sizeof(uint64_t) * (U + 1), hipMemcpyHostToDevice, h->stream));
   HIPCHK(h, hipMemcpyAsync(h->al_off + (U + 1), cell_off, sizeof(uint64_t) * (U + 1), hipMemcpyHostToDevice, h->stream));
@@ -3089,12 +3154,7 @@ static int upload_transcripts(scrf_handle h, uint32_t U, const uint32_t* phones,
 extern "C" int scrf_align_batch(scrf_handle h, scrf_batch b, const uint32_t* phones, const uint64_t* phone_off, int mode,
                                 uint32_t* seg_labels, uint64_t max_labels, uint64_t* lab_off, float* cost) {
   if (!h || !b || !phone_off || !seg_labels || !lab_off) return SCRF_ERR_INVALID;
-  if (h->cfg.model_type == SCRF_STDSEG || h->cfg.model_type == SCRF_STDSEG_NO_DUR)
-    return fail(h, SCRF_ERR_INVALID, "scrf_align_batch: forced alignment is not built for the \"%s\" CRF model; use \"stdframe\", "
-                "\"stdseg_no_dur_no_transftr\" or \"stdseg_no_dur_no_segtransftr\"", model_type_name(h->cfg.model_type));
-  if (h->cfg.num_states > 1)
-    return fail(h, SCRF_ERR_INVALID, "scrf_align_batch: forced alignment is built for crf_states = 1 only (this \"%s\" model has crf_states = %u)",
-                model_type_name(h->cfg.model_type), h->cfg.num_states);
+  RCCHK(model_ok(h, "scrf_align_batch", "forced alignment"));
   if (mode != SCRF_ALIGN_ONE && mode != SCRF_ALIGN_RUNS)
     return fail(h, SCRF_ERR_INVALID, "scrf_align_batch: unknown mode %d (SCRF_ALIGN_ONE = 0, SCRF_ALIGN_RUNS = 1)", mode);
   const ScrfLayout& l = h->lay;
@@ -3123,14 +3183,10 @@ extern "C" int scrf_align_batch(scrf_handle h, scrf_batch b, const uint32_t* pho
   HIPCHK(h, hipSetDevice(h->device));
   const bool frame_model = h->cfg.model_type == SCRF_STDFRAME;
   CallTimer call(h);
-  int rc = decode_result_room(h, b);
-  if (rc != SCRF_OK) return rc;
-  rc = upload_transcripts(h, U, phones, phone_off, h->al_bp_off.data());
-  if (rc != SCRF_OK) return rc;
+  RCCHK(decode_result_room(h, b));
+  RCCHK(upload_transcripts(h, U, phones, phone_off, h->al_bp_off.data()));
   h->n_al_calls++;
-  Need nd{false, false, false, false};
-  nd.align = true;
-  rc = decode_chunks(h, b, nd, [&](const ChunkBufs& cb, uint32_t u0, uint32_t u1, bool fast) {
+  RCCHK(decode_chunks(h, b, Need::alignment(), [&](const ChunkBufs& cb, uint32_t u0, uint32_t u1, bool fast) {
     const ScrfAlignArgs aa{h->al_ph, h->al_off, h->al_off + (U + 1), cb.al_bp, mode};
     uint64_t k_max = 0;   // over the transcripts that fit
     for (uint32_t u = u0; u < u1; u++)
@@ -3147,8 +3203,7 @@ extern "C" int scrf_align_batch(scrf_handle h, scrf_batch b, const uint32_t* pho
       KT_RUN("k_align_group", h->stream, launch_align_group(h->stream, l, b->view(), u0, u1 - u0, (uint32_t)k_max, S, Wn, cb.M, cb.m_per_frame,
                                                             frame_model, aa, h->dec_lab, h->dec_n, h->dec_cost));
     }
-  });
-  if (rc != SCRF_OK) return rc;
+  }));
   return decode_result_fetch(h, b, "scrf_align_batch", call, seg_labels, max_labels, lab_off, cost);
 }
 
@@ -3162,70 +3217,36 @@ extern "C" int scrf_align_stats(scrf_handle h, uint64_t* n_calls, uint64_t* n_ch
 }
 
 // ---------------------------------------------------------------------------------------------
-// transcript scoring: post_run's chunk loop, score stage and free recursion (for Zx); the sums over the
+// transcript scoring: label_free_run's chunk loop, score stage and free recursion (for Zx); the sums over the
 // alignments of each transcript in place of the free occupancy walk
 // ---------------------------------------------------------------------------------------------
-struct TransOut {
+struct TransOut : PostOut {
   double* log_num = nullptr;   // [U], always formed (the segment queries read it)
-  double* occ = nullptr;       // [sum T][L]
-  double* end = nullptr;       // [sum T]
-  double* seg = nullptr;       // [n queries]
-  const uint32_t *q_u = nullptr, *q_e = nullptr, *q_lab = nullptr;
-  const uint64_t* lab_off = nullptr;   // host
 };
 
-// The free occupancy walk (k_post_occ*) does not run, so the per-frame state mass k_mass_check compares is not formed and
-// that check is skipped here; the recursion's own checks (an emptied vector, a transition sum below DBL_MIN) still raise
-// SCRF_ERR_NUMERIC, and so does a fitting transcript whose sum is not finite.
-static int transcript_run(scrf_handle h, scrf_batch b, const uint64_t* phone_off, int mode, const TransOut& to, int latch[2]) {
+// The transcript kernels of a chunk, behind its recursion.  The free occupancy walk (k_post_occ*) does not run, so the
+// per-frame state mass k_mass_check compares is not formed and that check is skipped here; the recursion's own checks (an
+// emptied vector, a transition sum below DBL_MIN) still raise SCRF_ERR_NUMERIC, and so does a fitting transcript whose sum
+// is not finite.
+static int transcript_chunk(scrf_handle h, scrf_batch b, const uint64_t* phone_off, int mode, const TransOut& to, ChunkBufs& cb, uint32_t u0,
+                            uint32_t u1, uint32_t* nl) {
   const ScrfLayout& l = h->lay;
   const uint32_t U = b->U;
-  HIPCHK(h, hipMemsetAsync(b->d_status, 0, sizeof(int) * U, h->stream));
-  hipLaunchKernelGGL(k_latch_reset, dim3(1), dim3(1), 0, h->stream, h->d_latch);
-  const bool fast = h->cfg.train_precision >= SCRF_PREC_FAST;
-  const int f32 = h->cfg.train_precision == SCRF_PREC_FAST32;
-  Need nd{true, false, true, false};
-  nd.ponly = true;
-  nd.plog = !fast;
-  nd.trans = true;
-  set_batch_form(h, b, &nd);
   ScrfBatchView bv = b->view();
-  if (!l.use_tf) ensure_m0(h, h->stream);
-  if (sparse(h)) relay_sparse_lambda(h, h->stream);
-  for (uint32_t u0 = 0; u0 < U;) {
-    const uint32_t u1 = plan_chunk(h, b, u0, nd);
-    ChunkBufs cb;
-    int rc = carve(h, b, u0, u1, nd, &cb, 0);
-    if (rc != SCRF_OK) return rc;
-    cb.lamT_ready = sparse(h);
-    rc = run_scores(h, b, u0, u1, cb, fast, f32);
-    if (rc != SCRF_OK) return rc;
-    PhaseTimer tm(h, PH_FB, cb.st);
-    uint32_t nl = 0;
-    rc = run_dp(h, b, u0, u1, cb, false, &nl, true);
-    if (rc != SCRF_OK) return rc;
-    uint64_t k_max = 0;   // over the transcripts that fit
-    for (uint32_t u = u0; u < u1; u++)
-      if (h->tr_cell_off[u + 1] > h->tr_cell_off[u]) k_max = std::max(k_max, phone_off[u + 1] - phone_off[u]);
-    const ScrfTransArgs ta{h->al_ph, h->al_off, h->al_off + (U + 1), h->tr_inv, h->tr_inv + phone_off[U], cb.tr_aB, cb.tr_bE,
-                           mode, cb.lin ? 1 : 0, to.seg ? 1 : 0};
-    h->n_tr_chunks++;
-    KT_RUN("k_transcript", cb.st, launch_transcript(cb.st, l, bv, u0, u1 - u0, k_max, cb.S, cb.smax, cb.M, cb.m_per_frame, ta, b->d_status,
-                                                    to.log_num, to.occ, to.end));
-    nl++;
-    if (to.seg) {
-      const uint64_t q0 = to.lab_off[u0], nq = to.lab_off[u1] - q0;
-      KT_RUN("k_transcript_seg", cb.st, launch_transcript_seg(cb.st, l, bv, u0, to.q_u, to.q_e, to.q_lab, q0, nq, cb.S, cb.smax, ta, to.log_num, to.seg));
-      nl++;
-    }
-    tm.stop(nl);
-    HIPCHK(h, hipGetLastError());
-    u0 = u1;
+  uint64_t k_max = 0;   // over the transcripts that fit
+  for (uint32_t u = u0; u < u1; u++)
+    if (h->tr_cell_off[u + 1] > h->tr_cell_off[u]) k_max = std::max(k_max, phone_off[u + 1] - phone_off[u]);
+  const ScrfTransArgs ta{h->al_ph, h->al_off, h->al_off + (U + 1), h->tr_inv, h->tr_inv + phone_off[U], cb.tr_aB, cb.tr_bE,
+                         mode, cb.lin ? 1 : 0, to.seg ? 1 : 0};
+  h->n_tr_chunks++;
+  KT_RUN("k_transcript", cb.st, launch_transcript(cb.st, l, bv, u0, u1 - u0, k_max, cb.S, cb.smax, cb.M, cb.m_per_frame, ta, b->d_status,
+                                                  to.log_num, to.occ, to.end));
+  *nl += 1;
+  if (to.seg) {
+    const uint64_t q0 = to.lab_off[u0], nq = to.lab_off[u1] - q0;
+    KT_RUN("k_transcript_seg", cb.st, launch_transcript_seg(cb.st, l, bv, u0, to.q_u, to.q_e, to.q_lab, q0, nq, cb.S, cb.smax, ta, to.log_num, to.seg));
+    *nl += 1;
   }
-  int rc = queue_status(h, b);
-  if (rc != SCRF_OK) return rc;
-  HIPCHK(h, hipEventSynchronize(h->ev_status));
-  latch_decode(h->h_latch, latch);
   return SCRF_OK;
 }
 
@@ -3234,8 +3255,7 @@ extern "C" int scrf_transcript_batch(scrf_handle h, scrf_batch b, const uint32_t
                                      const uint32_t* seg_labels, const uint64_t* lab_off, double* seg_post) {
   if (!h || !b || !phone_off) return SCRF_ERR_INVALID;
   const char* fn = "scrf_transcript_batch";
-  int rc = post_model_ok(h, fn);
-  if (rc != SCRF_OK) return rc;
+  RCCHK(model_ok(h, fn, "posterior output"));
   const ScrfLayout& l = h->lay;
   if (l.D > 0x7fff) return fail(h, SCRF_ERR_INVALID, "%s: maximum duration %u is not served (at most %u, as scrf_align_batch)", fn, l.D, 0x7fffu);
   if (mode != SCRF_ALIGN_ONE && mode != SCRF_ALIGN_RUNS)
@@ -3266,8 +3286,7 @@ extern "C" int scrf_transcript_batch(scrf_handle h, scrf_batch b, const uint32_t
   }
   std::vector<uint32_t> q;   // [3][nq]: utterance, end frame, label value
   uint64_t nq = 0;
-  rc = seg_queries(h, b, fn, seg_labels, lab_off, seg_post != nullptr, &q, &nq);
-  if (rc != SCRF_OK) return rc;
+  RCCHK(seg_queries(h, b, fn, seg_labels, lab_off, seg_post != nullptr, &q, &nq));
   const uint64_t n_inv = NP + (uint64_t)U * (l.L + 1);
   h->tr_inv_h.assign(n_inv, 0);
   for (uint32_t u = 0; u < U; u++) {
@@ -3282,44 +3301,20 @@ extern "C" int scrf_transcript_batch(scrf_handle h, scrf_batch b, const uint32_t
     ioff[0] = 0;
   }
   HIPCHK(h, hipSetDevice(h->device));
-  const size_t by_occ = frame_post ? pad256(sizeof(double) * nF * l.L) : 0, by_end = end_post ? pad256(sizeof(double) * nF) : 0;
-  const size_t by_seg = pad256(sizeof(double) * nq), by_q = pad256(sizeof(uint32_t) * 3 * nq), by_ln = pad256(sizeof(double) * U);
-  const size_t need = by_occ + by_end + by_seg + by_q + by_ln + 256;
-  if (need > h->post_cap) {   // the posterior buffer of the handle, grown on demand and kept (scrf_abi.h)
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    hipFree(h->post_buf); h->post_buf = nullptr; h->post_cap = 0;
-    HIPCHK(h, hipMalloc((void**)&h->post_buf, need));
-    h->post_cap = need;
-  }
-  if (n_inv > h->tr_cap_inv) {
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    hipFree(h->tr_inv); h->tr_inv = nullptr; h->tr_cap_inv = 0;
-    HIPCHK(h, hipMalloc((void**)&h->tr_inv, sizeof(uint32_t) * n_inv));
-    h->tr_cap_inv = n_inv;
-  }
   TransOut to;
-  char* pb = h->post_buf;
-  if (frame_post) to.occ = (double*)pb;
-  pb += by_occ;
-  if (end_post) to.end = (double*)pb;
-  pb += by_end;
-  to.log_num = (double*)pb;
-  pb += by_ln;
-  if (seg_post && nq) {
-    to.seg = (double*)pb;
-    uint32_t* dq = (uint32_t*)(pb + by_seg);
-    HIPCHK(h, hipMemcpyAsync(dq, q.data(), sizeof(uint32_t) * 3 * nq, hipMemcpyHostToDevice, h->stream));
-    to.q_u = dq; to.q_e = dq + nq; to.q_lab = dq + 2 * nq;
-    to.lab_off = lab_off;
-  }
+  RCCHK(grow_device(h, &h->tr_inv, &h->tr_cap_inv, n_inv));
+  RCCHK(post_out_carve(h, b, frame_post, end_post, seg_post, q, nq, lab_off, U, &to, &to.log_num));
   if (n_inv) HIPCHK(h, hipMemcpyAsync(h->tr_inv, h->tr_inv_h.data(), sizeof(uint32_t) * n_inv, hipMemcpyHostToDevice, h->stream));
-  rc = upload_transcripts(h, U, phones, phone_off, h->tr_cell_off.data());   // ends with a synchronize: q may go
-  if (rc != SCRF_OK) return rc;
+  RCCHK(upload_transcripts(h, U, phones, phone_off, h->tr_cell_off.data()));   // ends with a synchronize: q may go
   CallTimer call(h);
   h->n_tr_calls++;
   const uint64_t fb0 = h->n_lin_fallback;
   int latch[2] = {0, 0};
-  rc = run_with_redo(h, latch, [&] { return transcript_run(h, b, phone_off, mode, to, latch); });
+  const int rc = run_with_redo(h, latch, [&] {
+    return label_free_run(h, b, Need::transcript(prec_fast(h)), latch, [&](ChunkBufs& cb, uint32_t u0, uint32_t u1, uint32_t* nl) {
+      return transcript_chunk(h, b, phone_off, mode, to, cb, u0, u1, nl);
+    });
+  });
   if (h->n_lin_fallback != fb0) h->n_tr_redone++;
   if (rc != SCRF_OK) return rc;
   call.stop();
