@@ -17,6 +17,7 @@
 #include <vector>
 
 #include "scrf_kernels.h"
+#include "scrf_own.h"
 
 // ---------------------------------------------------------------------------------------------
 // RCCL, bound lazily (so that loading the library never drags a second RCCL into a process
@@ -66,7 +67,107 @@ static bool rccl_load(std::string* why) {
 enum { SCRF_NCCL_DOUBLE = 8, SCRF_NCCL_SUM = 0 };  // ncclFloat64, ncclSum (rccl.h)
 
 // ---------------------------------------------------------------------------------------------
-struct scrf_engine_s {
+// What the handle owns (scrf_own.h).  These types, like the owning ones, lie in namespace scrf_eng: whatever of them the
+// library exports carries that name.
+namespace scrf_eng {
+
+// Batch arrays (scrf_batch_create / scrf_batch_destroy) come from a pool and are uploaded on a stream of their own:
+// a trainer that makes one batch per minibatch used to synchronise the device at every destroy (hipFree) and to wait
+// for the previous minibatch's kernels at every upload.  A freed block carries the epoch of its destroy call; the
+// engine stream's event of that epoch says when the last kernel that could read it has finished, and only then is the
+// block handed out again (otherwise a fresh one is allocated).  SCRF_BATCH_POOL=0: hipMalloc / hipFree as before.
+struct BatchPool {
+  struct Block { void* p; size_t cap; uint64_t epoch; };
+  std::vector<Block> free;
+  std::unordered_map<void*, size_t> live;    // blocks held by batches
+  Stream up_stream;
+  Event ev[8];
+  uint64_t epoch = 0, done = 0;              // destroy calls so far / epochs known to be finished
+  size_t bytes = 0;                          // bytes sitting in `free`
+  BatchPool() = default;
+  BatchPool(const BatchPool&) = delete;
+  BatchPool& operator=(const BatchPool&) = delete;
+  ~BatchPool() {   // (scrf_destroy has drained the streams)
+    for (auto& bl : free) hipFree(bl.p);
+    for (auto& kv : live) hipFree(kv.first);
+  }
+};
+
+// The per-feature state of the handle: each struct owns its buffers and its counters.
+// k_tile_tables: row records / row bases / rowmap of a steady-state score tile.  The tables depend on (D, TB, la) alone:
+// launched when that key changes or the buffer moves, on `stream`; a call on another stream waits for `ev`
+struct TileTables {
+  DevArray<char> tab;
+  uint32_t key[3] = {0, 0, 0};
+  bool valid = false;
+  hipStream_t stream = nullptr;
+  Event ev;
+};
+
+// result buffers of scrf_viterbi_batch and scrf_align_batch, kept across calls (a hipMalloc / hipFree pair per call is a
+// device-wide synchronisation each) and their pinned host images (the labels come back in one asynchronous copy)
+struct DecodeOut {
+  DevArray<uint32_t> lab, n;      // [sum T], [U]
+  DevArray<float> cost;           // [U]
+  PinnedArray<uint32_t> hlab, hn;
+  PinnedArray<float> hcost;
+  uint64_t n_fix = 0, n_fallback = 0;   // entries recomputed / chunks sent back to the EXACT path
+  hipError_t reserve(size_t n_frames, size_t n_utts) {   // room for the results of one batch
+    hipError_t e = lab.reserve(n_frames);
+    if (e == hipSuccess) e = hlab.reserve(n_frames);
+    if (e == hipSuccess) e = n.reserve(n_utts);
+    if (e == hipSuccess) e = cost.reserve(n_utts);
+    if (e == hipSuccess) e = hn.reserve(n_utts);
+    if (e == hipSuccess) e = hcost.reserve(n_utts);
+    return e;
+  }
+};
+
+// result of scrf_lattice_prune_batch: the kept arcs of the whole batch, back to back, outside the scratch
+// budget; grows geometrically, kept across calls.  One result, tied to the batch and the weights it was computed from
+struct PrunedLattice {
+  DevArray<scrf_arc> arcs;
+  DevArray<char> meta;          // best [U] doubles | utterance offsets [U + 1]
+  scrf_batch batch = nullptr;   // the batch of the valid result, or nullptr
+  std::vector<uint64_t> off;    // [U + 1] host image of the offsets
+  uint64_t n_calls = 0, n_chunks = 0;
+};
+
+// scrf_align_batch: the transcripts of the call on the device (phones | phone_off, back-pointer offsets),
+// kept across calls; bp_off is the host image chunk_layout sizes a chunk's back pointers with.
+// scrf_transcript_batch: the transcripts go into ph / off as well; inv holds each transcript's positions
+// sorted by label and where each label's start (inv_pos [sum K] | inv_off [U][L + 1]); cell_off is the host image
+// chunk_layout sizes a chunk's forward / backward cells with
+struct Transcripts {
+  DevArray<uint32_t> ph, inv;
+  DevArray<uint64_t> off;
+  std::vector<uint64_t> bp_off, cell_off;
+  std::vector<uint32_t> inv_h;
+  uint64_t n_al_calls = 0, n_al_chunks = 0, n_al_wave = 0, n_al_group = 0;   // calls; searches launched, and by which kernel
+  uint64_t n_tr_calls = 0, n_tr_chunks = 0, n_tr_redone = 0;   // calls; chunks swept (both passes of a redone call); calls redone
+};
+
+// HIP-event times of the last timed call: per phase (scrf_last_timing) and per kernel (scrf_kernel_timing)
+struct KTime { std::string name; double ms; uint32_t n; };
+struct Timing {
+  bool on = false;
+  std::vector<KTime> ktimes;
+  Event kev[2];
+  Event ev[SCRF_N_PHASES + 1][2];
+  float ms[SCRF_N_PHASES] = {};
+  uint32_t nlaunch[SCRF_N_PHASES] = {};
+};
+
+}  // namespace scrf_eng
+using namespace scrf_eng;
+
+// Everything the handle holds of the device is a member of an owning type: a new buffer is one member, reserved where it is
+// first needed, and scrf_destroy never hears of it.  Who waits for what before a buffer of the handle is dropped for a larger
+// one (DevArray::reserve itself waits for nothing):
+//   ensure_scratch                               both streams
+//   reserve_drained (post_buf, lp.meta, tx.*)    the engine stream
+//   dec.*, rtab.tab, d_pack                      nothing
+struct __attribute__((visibility("hidden"))) scrf_engine_s {   // (hidden: its constructor and destructor are not for export)
   scrf_config cfg;
   ScrfKnobs kn;   // the SCRF_* environment switches as scrf_create found them (scrf_knobs.h, DESIGN.md "Knobs")
   ScrfLayout lay;
@@ -80,72 +181,44 @@ struct scrf_engine_s {
   double mask_w = 0.0;
   std::vector<double> xbuf;
   int device = 0;
-  hipStream_t stream = nullptr;
-  bool own_stream = false;
-  double* d_lambda = nullptr;
-  double* d_lambda_acc = nullptr;
-  double* d_gsa = nullptr;
-  double* d_grad = nullptr;
-  bool own_grad = true;
-  double* d_m0 = nullptr;     // [L*L] time-invariant transition scores (bias-only transitions)
-  double* d_e0 = nullptr;     // exp(M0 - shift), its transpose and the shift (linear-domain DP)
-  double* d_et0 = nullptr;
-  double* d_msh0 = nullptr;
+  Stream stream;              // the engine's own, or the caller's (scrf_set_stream)
+  DevArray<double> d_lambda, d_lambda_acc, d_gsa;
+  DevArray<double> d_grad;    // the engine's own, or the caller's (scrf_set_grad_buffer)
+  DevArray<double> d_m0;      // [L*L] time-invariant transition scores (bias-only transitions)
+  DevArray<double> d_e0, d_et0, d_msh0;   // exp(M0 - shift), its transpose and the shift (linear-domain DP)
   bool m0_valid = false;
-  double* d_sums = nullptr;   // {numer, zx, n_utts, active}
+  DevArray<double> d_sums;    // {numer, zx, n_utts, active}
   // a batch's gradient and sums are built in a staging buffer and committed to d_grad / d_sums by a kernel
   // that is a no-op when an utterance of the batch failed (d_latch): a failed scrf_fb_batch leaves the
   // gradient as it was, and a NUMERIC failure of the linear-domain recursion can be redone in the log domain
-  double* d_stage = nullptr;
+  DevArray<double> d_stage;
   // sparse maps (scrf_sparse.hip): lambda re-laid index-major per call, [0] state block, [1] transition block
-  double* d_lamT[2] = {nullptr, nullptr};
-  double* d_sums_stage = nullptr;
-  int* d_latch = nullptr;     // {status code, utterance} of the first failed utterance of the batch in flight
-  int* h_latch = nullptr;     // pinned copy, valid once ev_status has completed
-  double* h_sums = nullptr;   // pinned image of the batch sums (scrf_queue_batch_sums / scrf_take_batch_sums)
-  hipEvent_t ev_sums = nullptr;
+  DevArray<double> d_lamT[2];
+  DevArray<double> d_sums_stage;
+  DevArray<int> d_latch;      // {status code, utterance} of the first failed utterance of the batch in flight
+  PinnedArray<int> h_latch;   // pinned copy, valid once ev_status has completed
+  PinnedArray<double> h_sums; // pinned image of the batch sums (scrf_queue_batch_sums / scrf_take_batch_sums)
+  Event ev_sums;
   bool sums_queued = false;
-  hipEvent_t ev_status = nullptr;
+  Event ev_status;
   uint64_t n_lin_fallback = 0;   // batches redone through the log-domain recursion
-  char* scratch = nullptr;
-  size_t scratch_cap = 0;
   // second lane: alternate chunks of a batch run on a second stream so that the VALU-bound DP
   // kernels of one chunk overlap the MFMA-bound contractions of the other
-  hipStream_t stream2 = nullptr;
-  // Batch arrays (scrf_batch_create / scrf_batch_destroy) come from a pool and are uploaded on a stream of their own:
-  // a trainer that makes one batch per minibatch used to synchronise the device at every destroy (hipFree) and to wait
-  // for the previous minibatch's kernels at every upload.  A freed block carries the epoch of its destroy call; the
-  // engine stream's event of that epoch says when the last kernel that could read it has finished, and only then is the
-  // block handed out again (otherwise a fresh one is allocated).  SCRF_BATCH_POOL=0: hipMalloc / hipFree as before.
-  struct PoolBlock { void* p; size_t cap; uint64_t epoch; };
-  std::vector<PoolBlock> pool_free;
-  std::unordered_map<void*, size_t> pool_cap;     // live blocks
-  hipStream_t up_stream = nullptr;
-  hipEvent_t pool_ev[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-  uint64_t pool_epoch = 0, pool_done = 0;         // destroy calls so far / epochs known to be finished
-  size_t pool_bytes = 0;                          // bytes sitting in pool_free
-  char* scratch2 = nullptr;
-  size_t scratch2_cap = 0;
-  double* d_grad2 = nullptr;
-  double* d_sums2 = nullptr;
-  hipEvent_t ev_fork = nullptr, ev_join = nullptr;
+  Stream stream2;
+  DevArray<char> scratch[2];  // the scratch arena of each lane (ensure_scratch)
+  DevArray<double> d_grad2, d_sums2;
+  Event ev_fork, ev_join;
+  BatchPool pool;
   // all-reduce / compute overlap (scrf_fb_batch_allreduce): inside the fused call the transition
   // contraction runs first and the all-reduce of the transition weights (98.7 % of the TIMIT-demo gradient) is issued on
   // the second stream as soon as they are committed, under the state contraction
   bool overlap_comm = false;  // set for the duration of a scrf_fb_batch_allreduce call
   bool early_done = false;    // the transition block of this step has been all-reduced already
   uint64_t n_collectives = 0, n_overlapped = 0;   // scrf_comm_stats
-  double* d_pack = nullptr;   // [L * nsf + 8]: the state weights of every label + the 8 scalars, one small message
-  void* d_rtab = nullptr;       // k_tile_tables: row records / row bases / rowmap of a steady-state score tile
-  size_t rtab_bytes = 0;
-  // the tables depend on (D, TB, la) alone: launched when that key changes or the buffer moves, on rtab_stream;
-  // a call on another stream waits for ev_rtab
-  uint32_t rtab_key[3] = {0, 0, 0};
-  bool rtab_valid = false;
-  hipStream_t rtab_stream = nullptr;
-  hipEvent_t ev_rtab = nullptr;
-  double* d_dtab = nullptr;     // k_dur_table: duration weight + bias per output block, for the fused score kernel
-  double* d_sl_tab = nullptr;   // STDSEG, bias-only transitions: E, E^T (nLabs^2 each) and max M (scrf_stdseg_lin.hip)
+  DevArray<double> d_pack;    // [L * nsf + 8]: the state weights of every label + the 8 scalars, one small message
+  TileTables rtab;
+  DevArray<double> d_dtab;      // k_dur_table: duration weight + bias per output block, for the fused score kernel
+  DevArray<double> d_sl_tab;    // STDSEG, bias-only transitions: E, E^T (nLabs^2 each) and max M (scrf_stdseg_lin.hip)
   bool frame_mass = false;   // posterior-mass self-checks with the frame model's bounds (scrf_set_frame_mass_check)
   uint64_t n_post_split = 0, n_post_whole = 0;   // k_post_occ launches in frame segments / in one piece (scrf_posterior_stats)
   // the workgroup-per-utterance log-domain recursion (k_fb: column-wise max-shifted log-sum-exp, the
@@ -154,50 +227,14 @@ struct scrf_engine_s {
   bool force_fb = false;
   // decode from the fused score kernel's float arc weights + reference-order fix-ups (bit-identical
   // to the EXACT path by a rounding-error bound, ScrfDecodeOut; kn.fast_decode)
-  double* d_w1 = nullptr;
-  uint64_t n_decode_fix = 0, n_decode_fallback = 0;   // entries recomputed / chunks sent back to the EXACT path
-  // result buffers of scrf_viterbi_batch, kept across calls (a hipMalloc / hipFree pair per call is a device-wide
-  // synchronisation each) and their pinned host images (the labels come back in one asynchronous copy)
-  uint32_t *dec_lab = nullptr, *dec_n = nullptr, *dec_hlab = nullptr, *dec_hn = nullptr;
-  float *dec_cost = nullptr, *dec_hcost = nullptr;
-  uint64_t dec_cap_f = 0, dec_cap_u = 0;
+  DevArray<double> d_w1;
+  DecodeOut dec;
   // result arrays of scrf_posteriors_batch (whole batch: chunking stays invisible), kept across calls like the decode buffers
-  char* post_buf = nullptr;
-  size_t post_cap = 0;
-  // result of scrf_lattice_prune_batch: the kept arcs of the whole batch, back to back, outside the scratch
-  // budget; grows geometrically, kept across calls.  One result, tied to the batch and the weights it was computed from
-  scrf_arc* lp_arcs = nullptr;
-  uint64_t lp_cap = 0;             // arcs
-  char* lp_meta = nullptr;         // best [U] doubles | utterance offsets [U + 1]
-  size_t lp_meta_cap = 0;
-  scrf_batch lp_batch = nullptr;   // the batch of the valid result, or nullptr
-  std::vector<uint64_t> lp_off;    // [U + 1] host image of the offsets
-  uint64_t n_lp_calls = 0, n_lp_chunks = 0;
-  // scrf_align_batch: the transcripts of the call on the device (phones | phone_off, back-pointer offsets),
-  // kept across calls; al_bp_off is the host image chunk_layout sizes a chunk's back pointers with
-  uint32_t* al_ph = nullptr;
-  uint64_t* al_off = nullptr;
-  uint64_t al_cap_ph = 0, al_cap_off = 0;
-  std::vector<uint64_t> al_bp_off;
-  uint64_t n_al_calls = 0, n_al_chunks = 0, n_al_wave = 0, n_al_group = 0;   // calls; searches launched, and by which kernel
-  // scrf_transcript_batch: the transcripts go into al_ph / al_off; tr_inv holds each transcript's positions
-  // sorted by label and where each label's start (inv_pos [sum K] | inv_off [U][L + 1]); tr_cell_off is the host image
-  // chunk_layout sizes a chunk's forward / backward cells with
-  uint32_t* tr_inv = nullptr;
-  uint64_t tr_cap_inv = 0;
-  std::vector<uint64_t> tr_cell_off;
-  std::vector<uint32_t> tr_inv_h;
-  uint64_t n_tr_calls = 0, n_tr_chunks = 0, n_tr_redone = 0;   // calls; chunks swept (both passes of a redone call); calls redone
+  DevArray<char> post_buf;
+  PrunedLattice lp;
+  Transcripts tx;
   std::string err;
-  // per-kernel HIP-event times of the last timed call (scrf_kernel_timing)
-  struct KTime { std::string name; double ms; uint32_t n; };
-  std::vector<KTime> ktimes;
-  hipEvent_t kev[2] = {nullptr, nullptr};
-  bool timing = false;
-  hipEvent_t ev[SCRF_N_PHASES + 1][2];
-  bool ev_ok = false;
-  float ms[SCRF_N_PHASES];
-  uint32_t nlaunch[SCRF_N_PHASES];
+  Timing tm;
   scrf_nccl_comm comm = nullptr;
   int rank = 0, nranks = 1;
 };
@@ -207,6 +244,8 @@ struct scrf_batch_s {
   int mode = 0;  // 0 = windows resident, 1 = frames + recipe
   std::vector<uint32_t> T;
   std::vector<uint64_t> frame_off, seg_off, arc_off;
+  // every device array below is a view into one of these blocks of the engine's pool (upload); they are what the batch owns
+  std::vector<void*> blocks;
   uint32_t* d_T = nullptr;
   uint64_t* d_frame_off = nullptr;
   uint64_t* d_seg_off = nullptr;
@@ -379,64 +418,61 @@ extern "C" int scrf_create(const scrf_config* cfg, scrf_handle* out) {
   h->device = cfg->device_id;
   if (h->cfg.scratch_bytes == 0) h->cfg.scratch_bytes = 8ull << 30;
   h->kn = scrf_knobs_read(scrf_env);
-  memset(h->ms, 0, sizeof(h->ms));
-  memset(h->nlaunch, 0, sizeof(h->nlaunch));
+  // a failing call leaves through scrf_destroy, like a finished engine: what was made before it is given back
 #define CRCHK(call)                                                                          \
   do {                                                                                       \
     hipError_t e_ = (call);                                                                  \
     if (e_ != hipSuccess) {                                                                  \
       fail(nullptr, SCRF_ERR_HIP, "scrf_create: %s failed: %s", #call, hipGetErrorString(e_)); \
-      delete h;                                                                              \
+      scrf_destroy(h);                                                                       \
       return SCRF_ERR_HIP;                                                                   \
     }                                                                                        \
   } while (0)
   CRCHK(hipSetDevice(h->device));
-  CRCHK(hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking));
-  h->own_stream = true;
-  size_t nb = sizeof(double) * lay.lambda_len;
-  CRCHK(hipMalloc((void**)&h->d_lambda, nb));
-  CRCHK(hipMalloc((void**)&h->d_lambda_acc, nb));
-  CRCHK(hipMalloc((void**)&h->d_gsa, nb));
-  CRCHK(hipMalloc((void**)&h->d_grad, nb));
-  CRCHK(hipMalloc((void**)&h->d_m0, sizeof(double) * lay.L * lay.L));
-  CRCHK(hipMalloc((void**)&h->d_w1, sizeof(double) * lay.L));
-  if (lay.D <= 40) CRCHK(hipMalloc((void**)&h->d_dtab, sizeof(double) * fused_dur_table_doubles(lay)));
+  CRCHK(h->stream.create(hipStreamNonBlocking));
+  const size_t n_lam = lay.lambda_len, LL = (size_t)lay.L * lay.L, nb = sizeof(double) * n_lam;
+  CRCHK(h->d_lambda.reserve(n_lam));
+  CRCHK(h->d_lambda_acc.reserve(n_lam));
+  CRCHK(h->d_gsa.reserve(n_lam));
+  CRCHK(h->d_grad.reserve(n_lam));
+  CRCHK(h->d_m0.reserve(LL));
+  CRCHK(h->d_w1.reserve(lay.L));
+  if (lay.D <= 40) CRCHK(h->d_dtab.reserve(fused_dur_table_doubles(lay)));
   if (cfg->map_type >= SCRF_STDSPARSE) {
-    if (lay.nsfe + lay.use_sb) CRCHK(hipMalloc((void**)&h->d_lamT[0], sizeof(double) * ((size_t)lay.nsfe + lay.use_sb) * lay.L));
-    if (lay.ntfe + lay.use_tb) CRCHK(hipMalloc((void**)&h->d_lamT[1], sizeof(double) * ((size_t)lay.ntfe + lay.use_tb) * lay.L * lay.L));
+    CRCHK(h->d_lamT[0].reserve(((size_t)lay.nsfe + lay.use_sb) * lay.L));
+    CRCHK(h->d_lamT[1].reserve(((size_t)lay.ntfe + lay.use_tb) * LL));
   }
-  if (cfg->model_type == SCRF_STDSEG && !lay.use_tf) CRCHK(hipMalloc((void**)&h->d_sl_tab, sizeof(double) * (2 * (size_t)lay.L * lay.L + 8)));
-  CRCHK(hipMalloc((void**)&h->d_e0, sizeof(double) * lay.L * lay.L));
-  CRCHK(hipMalloc((void**)&h->d_et0, sizeof(double) * lay.L * lay.L));
-  CRCHK(hipMalloc((void**)&h->d_msh0, sizeof(double)));
-  CRCHK(hipMalloc((void**)&h->d_sums, sizeof(double) * 8));
-  CRCHK(hipMalloc((void**)&h->d_stage, nb));
-  CRCHK(hipMalloc((void**)&h->d_sums_stage, sizeof(double) * 4));
-  CRCHK(hipMalloc((void**)&h->d_latch, sizeof(int) * 2));
-  CRCHK(hipHostMalloc((void**)&h->h_latch, sizeof(int) * 2, hipHostMallocDefault));
+  if (cfg->model_type == SCRF_STDSEG && !lay.use_tf) CRCHK(h->d_sl_tab.reserve(2 * LL + 8));
+  CRCHK(h->d_e0.reserve(LL));
+  CRCHK(h->d_et0.reserve(LL));
+  CRCHK(h->d_msh0.reserve(1));
+  CRCHK(h->d_sums.reserve(8));
+  CRCHK(h->d_stage.reserve(n_lam));
+  CRCHK(h->d_sums_stage.reserve(4));
+  CRCHK(h->d_latch.reserve(2));
+  CRCHK(h->h_latch.reserve(2));
   h->h_latch[0] = h->h_latch[1] = 0;
-  CRCHK(hipHostMalloc((void**)&h->h_sums, sizeof(double) * 4, hipHostMallocDefault));
-  CRCHK(hipEventCreateWithFlags(&h->ev_sums, hipEventDisableTiming));
-  CRCHK(hipEventCreateWithFlags(&h->ev_status, hipEventDisableTiming));
-  CRCHK(hipEventCreate(&h->kev[0]));
-  CRCHK(hipEventCreate(&h->kev[1]));
-  CRCHK(hipMalloc((void**)&h->d_grad2, nb));
-  CRCHK(hipMalloc((void**)&h->d_sums2, sizeof(double) * 4));
-  CRCHK(hipStreamCreateWithFlags(&h->stream2, hipStreamNonBlocking));
-  CRCHK(hipStreamCreateWithFlags(&h->up_stream, hipStreamNonBlocking));
-  CRCHK(hipEventCreateWithFlags(&h->ev_fork, hipEventDisableTiming));
-  CRCHK(hipEventCreateWithFlags(&h->ev_join, hipEventDisableTiming));
-  CRCHK(hipEventCreateWithFlags(&h->ev_rtab, hipEventDisableTiming));
+  CRCHK(h->h_sums.reserve(4));
+  CRCHK(h->ev_sums.create(hipEventDisableTiming));
+  CRCHK(h->ev_status.create(hipEventDisableTiming));
+  CRCHK(h->tm.kev[0].create());
+  CRCHK(h->tm.kev[1].create());
+  CRCHK(h->d_grad2.reserve(n_lam));
+  CRCHK(h->d_sums2.reserve(4));
+  CRCHK(h->stream2.create(hipStreamNonBlocking));
+  CRCHK(h->pool.up_stream.create(hipStreamNonBlocking));
+  CRCHK(h->ev_fork.create(hipEventDisableTiming));
+  CRCHK(h->ev_join.create(hipEventDisableTiming));
+  CRCHK(h->rtab.ev.create(hipEventDisableTiming));
   CRCHK(hipMemsetAsync(h->d_lambda, 0, nb, h->stream));
   CRCHK(hipMemsetAsync(h->d_lambda_acc, 0, nb, h->stream));
   CRCHK(hipMemsetAsync(h->d_gsa, 0, nb, h->stream));
   CRCHK(hipMemsetAsync(h->d_grad, 0, nb, h->stream));
   CRCHK(hipMemsetAsync(h->d_sums, 0, sizeof(double) * 8, h->stream));
   for (int i = 0; i <= SCRF_N_PHASES; i++) {
-    CRCHK(hipEventCreate(&h->ev[i][0]));
-    CRCHK(hipEventCreate(&h->ev[i][1]));
+    CRCHK(h->tm.ev[i][0].create());
+    CRCHK(h->tm.ev[i][1].create());
   }
-  h->ev_ok = true;
   CRCHK(hipStreamSynchronize(h->stream));
   if (h->shadow) {
     std::vector<double> z(h->xlay.lambda_len, 0.0);
@@ -450,39 +486,10 @@ extern "C" int scrf_create(const scrf_config* cfg, scrf_handle* out) {
 extern "C" int scrf_destroy(scrf_handle h) {
   if (!h) return SCRF_OK;
   hipSetDevice(h->device);
-  if (h->stream) hipStreamSynchronize(h->stream);
+  // nothing is released while a stream may still use it; the members give back what they own (scrf_own.h)
+  for (hipStream_t s : {h->stream.get(), h->stream2.get(), h->pool.up_stream.get()})
+    if (s) hipStreamSynchronize(s);
   if (h->comm && g_rccl.CommDestroy) g_rccl.CommDestroy(h->comm);
-  hipFree(h->d_lambda); hipFree(h->d_lambda_acc); hipFree(h->d_gsa);
-  if (h->own_grad) hipFree(h->d_grad);
-  hipFree(h->d_grad2); hipFree(h->d_sums2); hipFree(h->scratch2);
-  hipFree(h->d_stage); hipFree(h->d_sums_stage); hipFree(h->d_latch);
-  hipFree(h->d_lamT[0]); hipFree(h->d_lamT[1]);
-  if (h->h_latch) hipHostFree(h->h_latch);
-  if (h->h_sums) hipHostFree(h->h_sums);
-  if (h->ev_sums) hipEventDestroy(h->ev_sums);
-  if (h->ev_status) hipEventDestroy(h->ev_status);
-  if (h->kev[0]) hipEventDestroy(h->kev[0]);
-  if (h->kev[1]) hipEventDestroy(h->kev[1]);
-  if (h->stream2) { hipStreamSynchronize(h->stream2); hipStreamDestroy(h->stream2); }
-  if (h->up_stream) { hipStreamSynchronize(h->up_stream); hipStreamDestroy(h->up_stream); }
-  for (auto& bl : h->pool_free) hipFree(bl.p);   // (the engine stream was synchronised above)
-  for (auto& kv : h->pool_cap) hipFree(kv.first);
-  for (int i = 0; i < 8; i++) if (h->pool_ev[i]) hipEventDestroy(h->pool_ev[i]);
-  if (h->ev_fork) hipEventDestroy(h->ev_fork);
-  if (h->ev_join) hipEventDestroy(h->ev_join);
-  if (h->ev_rtab) hipEventDestroy(h->ev_rtab);
-  hipFree(h->dec_lab); hipFree(h->dec_n); hipFree(h->dec_cost);
-  hipFree(h->al_ph); hipFree(h->al_off);
-  hipFree(h->tr_inv);
-  hipFree(h->post_buf);
-  hipFree(h->lp_arcs); hipFree(h->lp_meta);
-  if (h->dec_hlab) hipHostFree(h->dec_hlab);
-  if (h->dec_hn) hipHostFree(h->dec_hn);
-  if (h->dec_hcost) hipHostFree(h->dec_hcost);
-  hipFree(h->d_w1); hipFree(h->d_dtab); hipFree(h->d_rtab); hipFree(h->d_pack); hipFree(h->d_sl_tab); hipFree(h->d_m0); hipFree(h->d_e0); hipFree(h->d_et0); hipFree(h->d_msh0); hipFree(h->d_sums); hipFree(h->scratch);
-  if (h->ev_ok)
-    for (int i = 0; i <= SCRF_N_PHASES; i++) { hipEventDestroy(h->ev[i][0]); hipEventDestroy(h->ev[i][1]); }
-  if (h->own_stream && h->stream) hipStreamDestroy(h->stream);
   delete h;
   return SCRF_OK;
 }
@@ -493,13 +500,8 @@ extern "C" int scrf_set_stream(scrf_handle h, void* s) {
   if (!h) return SCRF_ERR_INVALID;
   HIPCHK(h, hipSetDevice(h->device));
   HIPCHK(h, hipStreamSynchronize(h->stream));
-  if (h->own_stream) { hipStreamDestroy(h->stream); h->own_stream = false; }
-  if (s) {
-    h->stream = (hipStream_t)s;
-  } else {
-    HIPCHK(h, hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking));
-    h->own_stream = true;
-  }
+  if (s) h->stream.borrow((hipStream_t)s);
+  else HIPCHK(h, h->stream.create(hipStreamNonBlocking));
   return SCRF_OK;
 }
 
@@ -559,7 +561,7 @@ static int vec_io(scrf_handle h, double* dev, const double* in, double* out, uin
 }
 extern "C" int scrf_set_lambda(scrf_handle h, const double* v, uint32_t n) {
   int rc = vec_io(h, h ? h->d_lambda : nullptr, v, nullptr, n, "scrf_set_lambda");
-  if (rc == SCRF_OK) { h->m0_valid = false; h->lp_batch = nullptr; }
+  if (rc == SCRF_OK) { h->m0_valid = false; h->lp.batch = nullptr; }
   return rc;
 }
 extern "C" int scrf_get_lambda(scrf_handle h, double* v, uint32_t n) { return vec_io(h, h ? h->d_lambda : nullptr, nullptr, v, n, "scrf_get_lambda"); }
@@ -593,13 +595,11 @@ extern "C" int scrf_set_grad_buffer(scrf_handle h, void* dptr) {
   HIPCHK(h, hipSetDevice(h->device));
   HIPCHK(h, hipStreamSynchronize(h->stream));
   if (dptr) {
-    if (h->own_grad) hipFree(h->d_grad);
-    h->d_grad = (double*)dptr;
-    h->own_grad = false;
-  } else if (!h->own_grad) {
-    HIPCHK(h, hipMalloc((void**)&h->d_grad, sizeof(double) * h->lay.lambda_len));
+    h->d_grad.borrow((double*)dptr, h->lay.lambda_len);
+  } else if (!h->d_grad.owned()) {
+    h->d_grad.reset();
+    HIPCHK(h, h->d_grad.reserve(h->lay.lambda_len));
     HIPCHK(h, hipMemsetAsync(h->d_grad, 0, sizeof(double) * h->lay.lambda_len, h->stream));
-    h->own_grad = true;
   }
   return SCRF_OK;
 }
@@ -651,34 +651,28 @@ struct Arena {
 };
 
 static int ensure_scratch(scrf_handle h, size_t bytes, int lane = 0) {
-  char*& buf = lane ? h->scratch2 : h->scratch;
-  size_t& cap = lane ? h->scratch2_cap : h->scratch_cap;
-  if (bytes <= cap) return SCRF_OK;
+  if (bytes <= h->scratch[lane].cap()) return SCRF_OK;
   HIPCHK(h, hipStreamSynchronize(h->stream));
   HIPCHK(h, hipStreamSynchronize(h->stream2));
-  if (buf) hipFree(buf);
-  buf = nullptr;
-  cap = 0;
-  hipError_t e = hipMalloc((void**)&buf, bytes);
+  hipError_t e = h->scratch[lane].reserve(bytes);
   if (e != hipSuccess) return fail(h, SCRF_ERR_HIP, "scratch allocation of %zu bytes failed: %s", bytes, hipGetErrorString(e));
-  cap = bytes;
   return SCRF_OK;
 }
 
 // ---------------------------------------------------------------------------------------------
 // batches
 // ---------------------------------------------------------------------------------------------
-// ---- the batch-array pool (see the handle) ----
+// ---- the batch-array pool (BatchPool, above the handle) ----
 static size_t pool_class(size_t bytes) {   // size classes: powers of two from 64 KB (a minibatch's arrays vary in size from step to step)
   size_t c = 64u << 10;
   while (c < bytes) c *= 2;
   return c;
 }
 static void pool_poll(scrf_handle h) {   // which destroy epochs have finished on the device
-  while (h->pool_done < h->pool_epoch) {
-    hipEvent_t ev = h->pool_ev[(h->pool_done + 1) % 8];
+  while (h->pool.done < h->pool.epoch) {
+    hipEvent_t ev = h->pool.ev[(h->pool.done + 1) % 8];
     if (!ev || hipEventQuery(ev) != hipSuccess) break;
-    h->pool_done++;
+    h->pool.done++;
   }
 }
 static int pool_alloc(scrf_handle h, size_t bytes, void** out) {
@@ -686,57 +680,60 @@ static int pool_alloc(scrf_handle h, size_t bytes, void** out) {
   if (!h->kn.pool_on()) { HIPCHK(h, hipMalloc(out, bytes)); return SCRF_OK; }
   const size_t cap = pool_class(bytes);
   pool_poll(h);
-  for (size_t i = 0; i < h->pool_free.size(); i++) {
-    const auto& bl = h->pool_free[i];
-    if (bl.cap == cap && bl.epoch <= h->pool_done) {
+  for (size_t i = 0; i < h->pool.free.size(); i++) {
+    const auto& bl = h->pool.free[i];
+    if (bl.cap == cap && bl.epoch <= h->pool.done) {
       *out = bl.p;
-      h->pool_bytes -= bl.cap;
-      h->pool_free[i] = h->pool_free.back();
-      h->pool_free.pop_back();
-      h->pool_cap[*out] = cap;
+      h->pool.bytes -= bl.cap;
+      h->pool.free[i] = h->pool.free.back();
+      h->pool.free.pop_back();
+      h->pool.live[*out] = cap;
       return SCRF_OK;
     }
   }
   HIPCHK(h, hipMalloc(out, cap));
-  h->pool_cap[*out] = cap;
+  h->pool.live[*out] = cap;
   return SCRF_OK;
 }
 static void pool_release(scrf_handle h, void* p) {   // inside a destroy call: the block carries the epoch being closed
   if (!p) return;
-  auto it = h ? h->pool_cap.find(p) : decltype(h->pool_cap.find(p))();
-  if (!h || !h->kn.pool_on() || it == h->pool_cap.end()) { hipFree(p); return; }
-  h->pool_free.push_back({p, it->second, h->pool_epoch + 1});
-  h->pool_bytes += it->second;
-  h->pool_cap.erase(it);
+  auto it = h ? h->pool.live.find(p) : decltype(h->pool.live.find(p))();
+  if (!h || !h->kn.pool_on() || it == h->pool.live.end()) { hipFree(p); return; }
+  h->pool.free.push_back({p, it->second, h->pool.epoch + 1});
+  h->pool.bytes += it->second;
+  h->pool.live.erase(it);
 }
 static void pool_close_epoch(scrf_handle h) {   // after the releases of one destroy call
-  const uint64_t e = h->pool_epoch + 1;
-  hipEvent_t& ev = h->pool_ev[e % 8];
-  if (ev) { hipEventSynchronize(ev); if (h->pool_done < e - 8 && e >= 8) h->pool_done = e - 8; }   // the slot's old epoch (e - 8) is long past
-  else hipEventCreateWithFlags(&ev, hipEventDisableTiming);
+  const uint64_t e = h->pool.epoch + 1;
+  Event& ev = h->pool.ev[e % 8];
+  if (ev) { hipEventSynchronize(ev); if (h->pool.done < e - 8 && e >= 8) h->pool.done = e - 8; }   // the slot's old epoch (e - 8) is long past
+  else ev.create(hipEventDisableTiming);
   hipEventRecord(ev, h->stream);
-  h->pool_epoch = e;
+  h->pool.epoch = e;
   // keep the pool bounded: beyond 8 GiB of idle blocks, give the finished ones back
-  if (h->pool_bytes > ((size_t)8 << 30)) {
+  if (h->pool.bytes > ((size_t)8 << 30)) {
     pool_poll(h);
-    for (size_t i = 0; i < h->pool_free.size();) {
-      if (h->pool_free[i].epoch <= h->pool_done) {
-        h->pool_bytes -= h->pool_free[i].cap;
-        hipFree(h->pool_free[i].p);
-        h->pool_free[i] = h->pool_free.back();
-        h->pool_free.pop_back();
+    for (size_t i = 0; i < h->pool.free.size();) {
+      if (h->pool.free[i].epoch <= h->pool.done) {
+        h->pool.bytes -= h->pool.free[i].cap;
+        hipFree(h->pool.free[i].p);
+        h->pool.free[i] = h->pool.free.back();
+        h->pool.free.pop_back();
       } else i++;
     }
   }
 }
 
-static hipStream_t upload_stream(scrf_handle h) { return (h->kn.pool_on() && h->kn.pool_up()) ? h->up_stream : h->stream; }
+static hipStream_t upload_stream(scrf_handle h) { return (h->kn.pool_on() && h->kn.pool_up()) ? h->pool.up_stream.get() : h->stream.get(); }
+// A device array of batch `b`: a block of the pool, recorded in b->blocks (scrf_batch_destroy gives those back), with `src`
+// queued into it on the upload stream.  *d is the typed view the kernels read.
 template <class Tp>
-static int upload(scrf_handle h, Tp** d, const Tp* src, size_t n) {
+static int upload(scrf_handle h, scrf_batch b, Tp** d, const Tp* src, size_t n) {
   *d = nullptr;
   if (n == 0) n = 1;
   void* p = nullptr;
   RCCHK(pool_alloc(h, sizeof(Tp) * n, &p));
+  b->blocks.push_back(p);
   *d = (Tp*)p;
   if (src) HIPCHK(h, hipMemcpyAsync(*d, src, sizeof(Tp) * n, hipMemcpyHostToDevice, upload_stream(h)));
   return SCRF_OK;
@@ -752,16 +749,10 @@ static uint64_t shadow_num_arcs(scrf_handle h, uint32_t T) {
 extern "C" int scrf_batch_destroy(scrf_handle h, scrf_batch b) {
   if (!b) return SCRF_OK;
   if (h) hipSetDevice(h->device);
-  if (h && h->lp_batch == b) h->lp_batch = nullptr;
+  if (h && h->lp.batch == b) h->lp.batch = nullptr;
   if (h && !h->kn.pool_on()) hipStreamSynchronize(h->stream);
   // (pool: no synchronisation here -- the blocks wait in the pool until the engine stream has passed this point)
-#define BFREE(p) pool_release(h, (void*)(p))
-  BFREE(b->d_T); BFREE(b->d_frame_off); BFREE(b->d_seg_off); BFREE(b->d_arc_off);
-  BFREE(b->d_labels); BFREE(b->d_next_lab); BFREE(b->d_prev_lab); BFREE(b->d_trans_counts); BFREE(b->d_windows); BFREE(b->d_frame_u); BFREE(b->d_xm_f);
-  for (int s = 0; s < SCRF_MAX_STREAMS; s++) { BFREE(b->d_frames[s]); BFREE(b->d_sframe_off[s]); }
-  BFREE(b->d_numer); BFREE(b->d_zx); BFREE(b->d_status);
-  BFREE(b->d_tiles[0]); BFREE(b->d_tiles[1]); BFREE(b->d_tiles[2]);
-#undef BFREE
+  for (void* p : b->blocks) pool_release(h, p);
   if (h && h->kn.pool_on()) pool_close_epoch(h);
   delete b;
   return SCRF_OK;
@@ -787,7 +778,13 @@ extern "C" int scrf_batch_create(scrf_handle h, const scrf_utt* utts, uint32_t n
     if (tot != lay.F)
       return fail(h, SCRF_ERR_INVALID, "scrf_batch_create: joined window width %u != num_feas %u", tot, lay.F);
   }
-  scrf_batch b = new scrf_batch_s();
+  // built inside a guard: every early return below destroys the half-built batch, blocks taken so far included
+  struct Guard {
+    scrf_handle h;
+    scrf_batch b;
+    ~Guard() { if (b) scrf_batch_destroy(h, b); }
+  } guard{h, new scrf_batch_s()};
+  scrf_batch b = guard.b;
   b->U = n;
   b->mode = by_windows ? 0 : 1;
   b->n_streams = by_windows ? 0 : n_streams;
@@ -796,9 +793,9 @@ extern "C" int scrf_batch_create(scrf_handle h, const scrf_utt* utts, uint32_t n
   bool have_labels = utts[0].labels != nullptr;
   for (uint32_t u = 0; u < n; u++) {
     const scrf_utt& q = utts[u];
-    if ((q.windows != nullptr) != by_windows) { scrf_batch_destroy(h, b); return fail(h, SCRF_ERR_INVALID, "scrf_batch_create: utterance %u mixes window and frame input", u); }
-    if ((q.labels != nullptr) != have_labels) { scrf_batch_destroy(h, b); return fail(h, SCRF_ERR_INVALID, "scrf_batch_create: labels given for some utterances only"); }
-    if (q.T == 0) { scrf_batch_destroy(h, b); return fail(h, SCRF_ERR_EMPTY, "scrf_batch_create: utterance %u: No features read from this sentence.", u); }
+    if ((q.windows != nullptr) != by_windows) return fail(h, SCRF_ERR_INVALID, "scrf_batch_create: utterance %u mixes window and frame input", u);
+    if ((q.labels != nullptr) != have_labels) return fail(h, SCRF_ERR_INVALID, "scrf_batch_create: labels given for some utterances only");
+    if (q.T == 0) return fail(h, SCRF_ERR_EMPTY, "scrf_batch_create: utterance %u: No features read from this sentence.", u);
     b->T[u] = q.T;
     b->frame_off[u + 1] = b->frame_off[u] + q.T;
     b->seg_off[u + 1] = b->seg_off[u] + scrf_seg_base(q.T, lay.D);
@@ -811,23 +808,21 @@ extern "C" int scrf_batch_create(scrf_handle h, const scrf_utt* utts, uint32_t n
     b->arc_off[u + 1] = b->arc_off[u] + na;
   }
   const uint64_t NF = b->frame_off[n], NS = b->seg_off[n];
-  int rc;
-#define BCHK(x) do { rc = (x); if (rc != SCRF_OK) { scrf_batch_destroy(h, b); return rc; } } while (0)
-#define BSYNC() do { hipError_t e_ = hipStreamSynchronize(upload_stream(h)); if (e_ != hipSuccess) { scrf_batch_destroy(h, b); return fail(h, SCRF_ERR_HIP, "scrf_batch_create: %s", hipGetErrorString(e_)); } } while (0)
-  BCHK(upload(h, &b->d_T, b->T.data(), n));
-  BCHK(upload(h, &b->d_frame_off, b->frame_off.data(), n + 1));
-  BCHK(upload(h, &b->d_seg_off, b->seg_off.data(), n + 1));
-  BCHK(upload(h, &b->d_arc_off, b->arc_off.data(), n + 1));
+#define BSYNC() do { hipError_t e_ = hipStreamSynchronize(upload_stream(h)); if (e_ != hipSuccess) return fail(h, SCRF_ERR_HIP, "scrf_batch_create: %s", hipGetErrorString(e_)); } while (0)
+  RCCHK(upload(h, b, &b->d_T, b->T.data(), n));
+  RCCHK(upload(h, b, &b->d_frame_off, b->frame_off.data(), n + 1));
+  RCCHK(upload(h, b, &b->d_seg_off, b->seg_off.data(), n + 1));
+  RCCHK(upload(h, b, &b->d_arc_off, b->arc_off.data(), n + 1));
   {
     std::vector<uint32_t> fu(NF);
     for (uint32_t u = 0; u < n; u++) std::fill(fu.begin() + b->frame_off[u], fu.begin() + b->frame_off[u + 1], u);
-    BCHK(upload(h, &b->d_frame_u, fu.data(), NF));
+    RCCHK(upload(h, b, &b->d_frame_u, fu.data(), NF));
     BSYNC();
   }
   if (have_labels) {
     std::vector<uint32_t> lab(NF);
     for (uint32_t u = 0; u < n; u++) memcpy(&lab[b->frame_off[u]], utts[u].labels, sizeof(uint32_t) * utts[u].T);
-    BCHK(upload(h, &b->d_labels, lab.data(), NF));
+    RCCHK(upload(h, b, &b->d_labels, lab.data(), NF));
     std::vector<uint32_t> nxt(NF), cnt((size_t)lay.L * lay.L, 0);
     for (uint32_t u = 0; u < n; u++) {
       uint32_t cur = SCRF_LAB_BAD;
@@ -847,7 +842,7 @@ extern "C" int scrf_batch_create(scrf_handle h, const scrf_utt* utts, uint32_t n
         }
       }
     }
-    BCHK(upload(h, &b->d_next_lab, nxt.data(), NF));
+    RCCHK(upload(h, b, &b->d_next_lab, nxt.data(), NF));
     if (h->cfg.model_type == SCRF_STDSEG_NO_DUR || h->cfg.model_type == SCRF_STDSEG) {
       std::vector<uint32_t> prv(NF);
       for (uint32_t u = 0; u < n; u++) {
@@ -858,17 +853,17 @@ extern "C" int scrf_batch_create(scrf_handle h, const scrf_utt* utts, uint32_t n
           if (lab[f] != SCRF_LAB_BAD) cur = lab[f];
         }
       }
-      BCHK(upload(h, &b->d_prev_lab, prv.data(), NF));
+      RCCHK(upload(h, b, &b->d_prev_lab, prv.data(), NF));
     }
-    BCHK(upload(h, &b->d_trans_counts, cnt.data(), cnt.size()));
+    RCCHK(upload(h, b, &b->d_trans_counts, cnt.data(), cnt.size()));
     BSYNC();
   }
   if (by_windows) {
-    BCHK(upload<float>(h, &b->d_windows, nullptr, NS * lay.F + 64));  // tail pad: wide loads may over-read 12 B
+    RCCHK(upload<float>(h, b, &b->d_windows, nullptr, NS * lay.F + 64));  // tail pad: wide loads may over-read 12 B
     for (uint32_t u = 0; u < n; u++) {
       hipError_t e = hipMemcpyAsync(b->d_windows + b->seg_off[u] * lay.F, utts[u].windows,
                                     sizeof(float) * (b->seg_off[u + 1] - b->seg_off[u]) * lay.F, hipMemcpyHostToDevice, upload_stream(h));
-      if (e != hipSuccess) { scrf_batch_destroy(h, b); return fail(h, SCRF_ERR_HIP, "window upload failed: %s", hipGetErrorString(e)); }
+      if (e != hipSuccess) return fail(h, SCRF_ERR_HIP, "window upload failed: %s", hipGetErrorString(e));
     }
   } else {
     for (uint32_t s = 0; s < n_streams; s++) {
@@ -877,16 +872,16 @@ extern "C" int scrf_batch_create(scrf_handle h, const scrf_utt* utts, uint32_t n
       const uint32_t pad = recipes[s].left_ctx + recipes[s].right_ctx;
       std::vector<uint64_t> so(n + 1, 0);
       for (uint32_t u = 0; u < n; u++) {
-        if (!utts[u].frames[s]) { scrf_batch_destroy(h, b); return fail(h, SCRF_ERR_INVALID, "scrf_batch_create: utterance %u has no frames for stream %u", u, s); }
+        if (!utts[u].frames[s]) return fail(h, SCRF_ERR_INVALID, "scrf_batch_create: utterance %u has no frames for stream %u", u, s);
         so[u + 1] = so[u] + utts[u].T + pad;
       }
-      BCHK(upload(h, &b->d_sframe_off[s], so.data(), n + 1));
-      BCHK(upload<float>(h, &b->d_frames[s], nullptr, so[n] * recipes[s].in_width + 64));  // tail pad: wide loads may over-read 12 B
+      RCCHK(upload(h, b, &b->d_sframe_off[s], so.data(), n + 1));
+      RCCHK(upload<float>(h, b, &b->d_frames[s], nullptr, so[n] * recipes[s].in_width + 64));  // tail pad: wide loads may over-read 12 B
       BSYNC();
       for (uint32_t u = 0; u < n; u++) {
         hipError_t e = hipMemcpyAsync(b->d_frames[s] + so[u] * recipes[s].in_width, utts[u].frames[s],
                                       sizeof(float) * (so[u + 1] - so[u]) * recipes[s].in_width, hipMemcpyHostToDevice, upload_stream(h));
-        if (e != hipSuccess) { scrf_batch_destroy(h, b); return fail(h, SCRF_ERR_HIP, "frame upload failed: %s", hipGetErrorString(e)); }
+        if (e != hipSuccess) return fail(h, SCRF_ERR_HIP, "frame upload failed: %s", hipGetErrorString(e));
       }
     }
   }
@@ -922,7 +917,7 @@ extern "C" int scrf_batch_create(scrf_handle h, const scrf_utt* utts, uint32_t n
         m = nextafterf(m, INFINITY);   // |sbv| was rounded to float
         std::fill(xm.begin() + b->frame_off[u], xm.begin() + b->frame_off[u + 1], m);
       }
-      BCHK(upload(h, &b->d_xm_f, xm.data(), NF));
+      RCCHK(upload(h, b, &b->d_xm_f, xm.data(), NF));
       BSYNC();
     }
     // score tiles: the windows of TB whole frames; expected-count tiles: those of TBE whole frames (<= 64 windows)
@@ -957,16 +952,16 @@ extern "C" int scrf_batch_create(scrf_handle h, const scrf_utt* utts, uint32_t n
         }
         b->tile_off[k][u + 1] = td.size();
       }
-      BCHK(upload(h, &b->d_tiles[k], td.data(), td.size()));
+      RCCHK(upload(h, b, &b->d_tiles[k], td.data(), td.size()));
       BSYNC();
     }
   }
-  BCHK(upload<double>(h, &b->d_numer, nullptr, n));
-  BCHK(upload<double>(h, &b->d_zx, nullptr, n));
-  BCHK(upload<int>(h, &b->d_status, nullptr, n));
-#undef BCHK
+  RCCHK(upload<double>(h, b, &b->d_numer, nullptr, n));
+  RCCHK(upload<double>(h, b, &b->d_zx, nullptr, n));
+  RCCHK(upload<int>(h, b, &b->d_status, nullptr, n));
   BSYNC();
 #undef BSYNC
+  guard.b = nullptr;
   *out = b;
   return SCRF_OK;
 }
@@ -1312,10 +1307,10 @@ static void chunk_layout(scrf_handle h, scrf_batch b, uint32_t u0, uint32_t u1, 
     cb->lat_counts = a.take<uint32_t>(nfr + nutt);
     cb->lat_node_off = a.take<uint64_t>(nfr + nutt + 1);
   }
-  if (nd.align) cb->al_bp = a.take<uint16_t>(h->al_bp_off[u1] - h->al_bp_off[u0]);
+  if (nd.align) cb->al_bp = a.take<uint16_t>(h->tx.bp_off[u1] - h->tx.bp_off[u0]);
   if (nd.trans) {
-    cb->tr_aB = a.take<double>(h->tr_cell_off[u1] - h->tr_cell_off[u0]);
-    cb->tr_bE = a.take<double>(h->tr_cell_off[u1] - h->tr_cell_off[u0]);
+    cb->tr_aB = a.take<double>(h->tx.cell_off[u1] - h->tx.cell_off[u0]);
+    cb->tr_bE = a.take<double>(h->tx.cell_off[u1] - h->tx.cell_off[u0]);
   }
 }
 
@@ -1343,10 +1338,10 @@ static uint32_t plan_chunk(scrf_handle h, scrf_batch b, uint32_t u0, const Need&
 
 static int carve(scrf_handle h, scrf_batch b, uint32_t u0, uint32_t u1, const Need& nd, ChunkBufs* cb, int lane = 0) {
   RCCHK(ensure_scratch(h, chunk_size(h, b, u0, u1, nd, cb), lane));
-  Arena a{lane ? h->scratch2 : h->scratch, lane ? h->scratch2_cap : h->scratch_cap, 0};
-  cb->st = lane ? h->stream2 : h->stream;
-  cb->grad = lane ? h->d_grad2 : h->d_grad;
-  cb->sums = lane ? h->d_sums2 : h->d_sums;
+  Arena a{h->scratch[lane], h->scratch[lane].cap(), 0};
+  cb->st = lane ? h->stream2.get() : h->stream.get();
+  cb->grad = lane ? h->d_grad2.get() : h->d_grad.get();
+  cb->sums = lane ? h->d_sums2.get() : h->d_sums.get();
   chunk_layout(h, b, u0, u1, nd, a, cb);
   if (a.off > a.cap) return fail(h, SCRF_ERR_INVALID, "internal: scratch arena overflow");
   return SCRF_OK;
@@ -1357,16 +1352,16 @@ struct PhaseTimer {
   int ph;
   hipStream_t st;
   PhaseTimer(scrf_handle h_, int p, hipStream_t s_ = nullptr) : h(h_), ph(p), st(s_ ? s_ : h_->stream) {
-    if (h->timing) hipEventRecord(h->ev[ph][0], st);
+    if (h->tm.on) hipEventRecord(h->tm.ev[ph][0], st);
   }
   void stop(uint32_t launches) {
-    if (!h->timing) return;
-    hipEventRecord(h->ev[ph][1], st);
-    hipEventSynchronize(h->ev[ph][1]);
+    if (!h->tm.on) return;
+    hipEventRecord(h->tm.ev[ph][1], st);
+    hipEventSynchronize(h->tm.ev[ph][1]);
     float ms = 0;
-    hipEventElapsedTime(&ms, h->ev[ph][0], h->ev[ph][1]);
-    h->ms[ph] += ms;
-    h->nlaunch[ph] += launches;
+    hipEventElapsedTime(&ms, h->tm.ev[ph][0], h->tm.ev[ph][1]);
+    h->tm.ms[ph] += ms;
+    h->tm.nlaunch[ph] += launches;
   }
 };
 
@@ -1377,17 +1372,17 @@ struct KernelTimer {
   const char* name;
   hipStream_t st;
   KernelTimer(scrf_handle h_, const char* n, hipStream_t s_) : h(h_), name(n), st(s_) {
-    if (h->timing) hipEventRecord(h->kev[0], st);
+    if (h->tm.on) hipEventRecord(h->tm.kev[0], st);
   }
   void stop(uint32_t launches = 1) {
-    if (!h->timing) return;
-    hipEventRecord(h->kev[1], st);
-    hipEventSynchronize(h->kev[1]);
+    if (!h->tm.on) return;
+    hipEventRecord(h->tm.kev[1], st);
+    hipEventSynchronize(h->tm.kev[1]);
     float ms = 0;
-    hipEventElapsedTime(&ms, h->kev[0], h->kev[1]);
-    for (auto& k : h->ktimes)
+    hipEventElapsedTime(&ms, h->tm.kev[0], h->tm.kev[1]);
+    for (auto& k : h->tm.ktimes)
       if (k.name == name) { k.ms += ms; k.n += launches; return; }
-    h->ktimes.push_back({name, ms, launches});
+    h->tm.ktimes.push_back({name, ms, launches});
   }
 };
 #define KT_RUN(name, st, ...) do { KernelTimer kt_(h, name, st); __VA_ARGS__; kt_.stop(); } while (0)
@@ -1397,15 +1392,15 @@ struct KernelTimer {
 struct CallTimer {
   scrf_handle h;
   explicit CallTimer(scrf_handle h_) : h(h_) {
-    if (!h->timing) return;
-    memset(h->ms, 0, sizeof(h->ms)); memset(h->nlaunch, 0, sizeof(h->nlaunch)); h->ktimes.clear();
-    hipEventRecord(h->ev[SCRF_N_PHASES][0], h->stream);
+    if (!h->tm.on) return;
+    memset(h->tm.ms, 0, sizeof(h->tm.ms)); memset(h->tm.nlaunch, 0, sizeof(h->tm.nlaunch)); h->tm.ktimes.clear();
+    hipEventRecord(h->tm.ev[SCRF_N_PHASES][0], h->stream);
   }
   void stop() {
-    if (!h->timing) return;
-    hipEventRecord(h->ev[SCRF_N_PHASES][1], h->stream);
-    hipEventSynchronize(h->ev[SCRF_N_PHASES][1]);
-    hipEventElapsedTime(&h->ms[PH_ALL], h->ev[SCRF_N_PHASES][0], h->ev[SCRF_N_PHASES][1]);
+    if (!h->tm.on) return;
+    hipEventRecord(h->tm.ev[SCRF_N_PHASES][1], h->stream);
+    hipEventSynchronize(h->tm.ev[SCRF_N_PHASES][1]);
+    hipEventElapsedTime(&h->tm.ms[PH_ALL], h->tm.ev[SCRF_N_PHASES][0], h->tm.ev[SCRF_N_PHASES][1]);
   }
 };
 
@@ -1475,20 +1470,17 @@ static int run_scores(scrf_handle h, scrf_batch b, uint32_t u0, uint32_t u1, Chu
       launch_dur_table(cb.st, l, W0, h->d_lambda, h->d_dtab);
       fa.dtab = h->d_dtab;
       const size_t nb = fused_tile_table_bytes(l.D, fa.TB);
-      if (nb > h->rtab_bytes) {
-        hipFree(h->d_rtab); h->d_rtab = nullptr; h->rtab_bytes = 0; h->rtab_valid = false;
-        HIPCHK(h, hipMalloc(&h->d_rtab, nb));
-        h->rtab_bytes = nb;
-      }
+      if (nb > h->rtab.tab.cap()) h->rtab.valid = false;   // the buffer moves
+      HIPCHK(h, h->rtab.tab.reserve(nb));
       const uint32_t key[3] = {l.D, fa.TB, (cb.la && !cb.Wn) ? 1u : 0u};
-      if (!h->rtab_valid || memcmp(key, h->rtab_key, sizeof(key)) != 0) {
-        launch_tile_tables(cb.st, key[0], key[1], (int)key[2], h->d_rtab);
-        HIPCHK(h, hipEventRecord(h->ev_rtab, cb.st));
-        memcpy(h->rtab_key, key, sizeof(key));
-        h->rtab_valid = true;
-        h->rtab_stream = cb.st;
-      } else if (cb.st != h->rtab_stream) HIPCHK(h, hipStreamWaitEvent(cb.st, h->ev_rtab, 0));
-      if (h->kn.rtab) fa.rtab = h->d_rtab;
+      if (!h->rtab.valid || memcmp(key, h->rtab.key, sizeof(key)) != 0) {
+        launch_tile_tables(cb.st, key[0], key[1], (int)key[2], h->rtab.tab);
+        HIPCHK(h, hipEventRecord(h->rtab.ev, cb.st));
+        memcpy(h->rtab.key, key, sizeof(key));
+        h->rtab.valid = true;
+        h->rtab.stream = cb.st;
+      } else if (cb.st != h->rtab.stream) HIPCHK(h, hipStreamWaitEvent(cb.st, h->rtab.ev, 0));
+      if (h->kn.rtab) fa.rtab = h->rtab.tab;
       fa.dma = h->kn.scores_dma ? 1 : 0;
     }
     // per-frame projections of the five sampled blocks, then the dense part + gather
@@ -1769,7 +1761,7 @@ static int run_dp(scrf_handle h, scrf_batch b, uint32_t u0, uint32_t u1, ChunkBu
 // ---------------------------------------------------------------------------------------------
 // latch[0]: non-zero iff an utterance failed (what k_commit tests); latch[1]: min over the failed utterances of
 // (utterance << 8 | code), so the LOWEST failing utterance is the one reported, whichever thread gets there first --
-// the order in which the reference's per-utterance loop would have thrown.  fb_latch_reset arms it.
+// the order in which the reference's per-utterance loop would have thrown.  latch_reset arms it.
 #define SCRF_LATCH_IDLE 0x7fffffff
 __global__ void k_latch_status(const int* __restrict__ status, uint32_t n, int* __restrict__ latch) {
   const uint32_t u = blockIdx.x * blockDim.x + threadIdx.x;
@@ -1784,6 +1776,8 @@ __global__ void k_latch_reset(int* __restrict__ latch) {
   latch[0] = 0;
   latch[1] = SCRF_LATCH_IDLE;
 }
+// arms the latch on the engine stream, at the head of a pass (training or label-free)
+static void latch_reset(scrf_handle h) { hipLaunchKernelGGL(k_latch_reset, dim3(1), dim3(1), 0, h->stream, h->d_latch.get()); }
 // {code, utterance} from the pinned copy of the latch
 static void latch_decode(const int* h_latch, int out[2]) {
   out[0] = out[1] = 0;
@@ -1852,7 +1846,7 @@ struct SmallPipe {
   // carves the chunk on the engine's scratch and queues its window vectors (batches made from frames)
   int begin_chunk(scrf_handle h, scrf_batch b, uint32_t u0, uint32_t u1, bool post, Bufs* sb) const {
     RCCHK(ensure_scratch(h, chunk_size(h, b, u0, u1, post)));
-    Arena a{h->scratch, h->scratch_cap, 0};
+    Arena a{h->scratch[0], h->scratch[0].cap(), 0};
     layout(h, b, u0, u1, post, a, sb);
     if (a.off > a.cap) return fail(h, SCRF_ERR_INVALID, "internal: scratch arena overflow");
     if (b->mode == 1) launch_chunk_windows(h, b, u0, u1, h->stream, sb->X);
@@ -2069,7 +2063,7 @@ static bool two_block_reduce(scrf_handle h) { return h->comm && h->lay.use_tf &&
 // arms the status latch and clears the staging gradient and sums
 static int fb_begin(scrf_handle h, scrf_batch b) {
   HIPCHK(h, hipMemsetAsync(b->d_status, 0, sizeof(int) * b->U, h->stream));
-  hipLaunchKernelGGL(k_latch_reset, dim3(1), dim3(1), 0, h->stream, h->d_latch);
+  latch_reset(h);
   HIPCHK(h, hipMemsetAsync(h->d_stage, 0, sizeof(double) * h->lay.lambda_len, h->stream));
   HIPCHK(h, hipMemsetAsync(h->d_sums_stage, 0, sizeof(double) * 4, h->stream));
   return SCRF_OK;
@@ -2122,7 +2116,7 @@ struct FbPlan {
 static FbPlan fb_plan(scrf_handle h, scrf_batch b, const Need& nd) {
   FbPlan p;
   p.cuts.push_back(0);
-  const bool two_lanes = h->kn.lanes > 1 && !h->timing && b->U >= 64;
+  const bool two_lanes = h->kn.lanes > 1 && !h->tm.on && b->U >= 64;
   const uint32_t cap = two_lanes ? (b->U + 3) / 4 : b->U;
   for (uint32_t u0 = 0; u0 < b->U;) {
     const uint32_t u1 = std::min(plan_chunk(h, b, u0, nd), u0 + cap);
@@ -2144,8 +2138,8 @@ static FbRoute fb_route(scrf_handle h, scrf_batch b, const ChunkBufs& cb, const 
   rt.lane = plan.lane(ci);
   rt.two_lanes = plan.use2;
   rt.last = ci + 1 == plan.n_chunks();
-  rt.overlap = h->overlap_comm && h->kn.comm_overlap && two_block_reduce(h) && !plan.use2 && !h->timing && !sparse(h);
-  rt.side = h->kn.side && !plan.use2 && !h->timing && !rt.overlap && cb.fused && cb.lin && cb.wave && !h->lay.use_tf && !segtrans(h) &&
+  rt.overlap = h->overlap_comm && h->kn.comm_overlap && two_block_reduce(h) && !plan.use2 && !h->tm.on && !sparse(h);
+  rt.side = h->kn.side && !plan.use2 && !h->tm.on && !rt.overlap && cb.fused && cb.lin && cb.wave && !h->lay.use_tf && !segtrans(h) &&
             pframe_supported(b->recipe[0].in_width) && cb.expf_plan.ws;
   return rt;
 }
@@ -2424,14 +2418,11 @@ static const char* model_type_name(uint32_t mt) {
   return mt == SCRF_STDFRAME ? "stdframe" : mt == SCRF_STDSEG ? "stdseg" : mt == SCRF_STDSEG_NO_DUR ? "stdseg_no_dur"
          : mt == SCRF_STDSEG_NO_DUR_NO_TRANSFTR ? "stdseg_no_dur_no_transftr" : "stdseg_no_dur_no_segtransftr";
 }
-// a device array of the handle with room for n elements: grown on demand once the stream has drained, kept until scrf_destroy
-template <class Tp, class Cap>
-static int grow_device(scrf_handle h, Tp** p, Cap* cap, size_t n) {
-  if (n <= *cap) return SCRF_OK;
-  HIPCHK(h, hipStreamSynchronize(h->stream));
-  hipFree(*p); *p = nullptr; *cap = 0;
-  HIPCHK(h, hipMalloc((void**)p, sizeof(Tp) * n));
-  *cap = (Cap)n;
+// room for n elements in a result array of the handle; the engine stream drains before a smaller one is dropped
+template <class Tp>
+static int reserve_drained(scrf_handle h, DevArray<Tp>& a, size_t n) {
+  if (n > a.cap()) HIPCHK(h, hipStreamSynchronize(h->stream));
+  HIPCHK(h, a.reserve(n));
   return SCRF_OK;
 }
 
@@ -2454,7 +2445,7 @@ static int model_ok(scrf_handle h, const char* fn, const char* what) {
 template <class Body>
 static int label_free_run(scrf_handle h, scrf_batch b, Need nd, int latch[2], Body body) {
   HIPCHK(h, hipMemsetAsync(b->d_status, 0, sizeof(int) * b->U, h->stream));
-  hipLaunchKernelGGL(k_latch_reset, dim3(1), dim3(1), 0, h->stream, h->d_latch);
+  latch_reset(h);
   set_batch_form(h, b, &nd);   // the batch forms of scrf_fb_batch
   if (!h->lay.use_tf) ensure_m0(h, h->stream);
   if (sparse(h)) relay_sparse_lambda(h, h->stream);
@@ -2490,7 +2481,7 @@ static int post_out_carve(scrf_handle h, scrf_batch b, bool occ, bool end, bool 
   const uint64_t nF = b->frame_off[b->U];
   const size_t by_occ = occ ? pad256(sizeof(double) * nF * h->lay.L) : 0, by_end = end ? pad256(sizeof(double) * nF) : 0;
   const size_t by_seg = pad256(sizeof(double) * nq), by_q = pad256(sizeof(uint32_t) * 3 * nq), by_x = pad256(sizeof(double) * n_extra);
-  RCCHK(grow_device(h, &h->post_buf, &h->post_cap, by_occ + by_end + by_x + by_seg + by_q + 256));
+  RCCHK(reserve_drained(h, h->post_buf, by_occ + by_end + by_x + by_seg + by_q + 256));
   char* pb = h->post_buf;
   if (occ) po->occ = (double*)pb;
   pb += by_occ;
@@ -2609,8 +2600,8 @@ extern "C" int scrf_add_grad(scrf_handle h, const double* g, uint32_t n) {
     n = h->lay.lambda_len;
   }
   RCCHK(ensure_scratch(h, sizeof(double) * n));
-  HIPCHK(h, hipMemcpyAsync(h->scratch, g, sizeof(double) * n, hipMemcpyHostToDevice, h->stream));
-  launch_add(h->stream, h->d_grad, (const double*)h->scratch, n);
+  HIPCHK(h, hipMemcpyAsync(h->scratch[0], g, sizeof(double) * n, hipMemcpyHostToDevice, h->stream));
+  launch_add(h->stream, h->d_grad, (const double*)h->scratch[0].get(), n);
   HIPCHK(h, hipStreamSynchronize(h->stream));
   return SCRF_OK;
 }
@@ -2663,17 +2654,6 @@ static int hook_fb(scrf_handle h, scrf_batch b, uint32_t u, const char* fn, Chun
     return SCRF_OK;
   }
 }
-
-// device buffer owned by a scope (the one-off arrays of the hooks and of the small decode paths)
-template <class Tp>
-struct DevBuf {
-  Tp* p = nullptr;
-  DevBuf() = default;
-  DevBuf(const DevBuf&) = delete;
-  DevBuf& operator=(const DevBuf&) = delete;
-  ~DevBuf() { hipFree(p); }
-  hipError_t alloc(size_t n) { return hipMalloc((void**)&p, sizeof(Tp) * n); }
-};
 
 extern "C" int scrf_windows(scrf_handle h, scrf_batch b, uint32_t u, float* out) {
   RCCHK(check_u(h, b, u, "scrf_windows"));
@@ -2804,10 +2784,10 @@ extern "C" int scrf_lattice_arcs(scrf_handle h, scrf_batch b, uint32_t u, int no
     double Zx = 0.0;
     if (norm) RCCHK(read_zx(h, b, u, &Zx));
     const float final_w = norm ? (float)Zx : 0.0f;
-    DevBuf<scrf_arc> d_arcs;
-    HIPCHK(h, d_arcs.alloc(na));
-    launch_ns_arcs(h->stream, h->lay, T, nb.S, nb.TD, nb.TO, nb.TE, final_w, d_arcs.p);
-    hipError_t e = hipMemcpyAsync(arcs, d_arcs.p, sizeof(scrf_arc) * na, hipMemcpyDeviceToHost, h->stream);
+    DevArray<scrf_arc> d_arcs;
+    HIPCHK(h, d_arcs.reserve(na));
+    launch_ns_arcs(h->stream, h->lay, T, nb.S, nb.TD, nb.TO, nb.TE, final_w, d_arcs);
+    hipError_t e = hipMemcpyAsync(arcs, d_arcs, sizeof(scrf_arc) * na, hipMemcpyDeviceToHost, h->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
     if (e != hipSuccess) return fail(h, SCRF_ERR_HIP, "scrf_lattice_arcs: %s", hipGetErrorString(e));
     return SCRF_OK;
@@ -2827,14 +2807,14 @@ extern "C" int scrf_lattice_arcs(scrf_handle h, scrf_batch b, uint32_t u, int no
     const float final_w = norm ? (float)(-Zx) : -0.0f;
     std::vector<uint64_t> off;
     stdseg_row_arc_offsets(T, La, h->lay.D, &off);
-    DevBuf<uint64_t> d_off;
-    DevBuf<scrf_arc> d_arcs;
-    hipError_t e = d_off.alloc(off.size());
-    if (e == hipSuccess) e = d_arcs.alloc(na);
-    if (e == hipSuccess) e = hipMemcpyAsync(d_off.p, off.data(), sizeof(uint64_t) * off.size(), hipMemcpyHostToDevice, h->stream);
+    DevArray<uint64_t> d_off;
+    DevArray<scrf_arc> d_arcs;
+    hipError_t e = d_off.reserve(off.size());
+    if (e == hipSuccess) e = d_arcs.reserve(na);
+    if (e == hipSuccess) e = hipMemcpyAsync(d_off, off.data(), sizeof(uint64_t) * off.size(), hipMemcpyHostToDevice, h->stream);
     if (e == hipSuccess) {
-      launch_stdseg_arcs(h->stream, h->lay, La, T, ns, d_off.p, sb.S, sb.MX, final_w, d_arcs.p);
-      e = hipMemcpyAsync(arcs, d_arcs.p, sizeof(scrf_arc) * na, hipMemcpyDeviceToHost, h->stream);
+      launch_stdseg_arcs(h->stream, h->lay, La, T, ns, d_off, sb.S, sb.MX, final_w, d_arcs);
+      e = hipMemcpyAsync(arcs, d_arcs, sizeof(scrf_arc) * na, hipMemcpyDeviceToHost, h->stream);
     }
     if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
     if (e != hipSuccess) return fail(h, SCRF_ERR_HIP, "scrf_lattice_arcs: %s", hipGetErrorString(e));
@@ -2860,13 +2840,13 @@ extern "C" int scrf_lattice_arcs(scrf_handle h, scrf_batch b, uint32_t u, int no
     RCCHK(read_zx(h, b, u, &Zx));
     final_w = frame_model ? (float)Zx : (float)(-Zx);
   }
-  DevBuf<scrf_arc> d_arcs;
-  HIPCHK(h, d_arcs.alloc(na));
-  if (segtrans(h)) launch_arcs_segtrans(h->stream, l, T, cb.S, cb.M, final_w, d_arcs.p);
-  else launch_arcs(h->stream, l, T, frame_model, cb.S, cb.M, cb.m_per_frame, final_w, d_arcs.p);
+  DevArray<scrf_arc> d_arcs;
+  HIPCHK(h, d_arcs.reserve(na));
+  if (segtrans(h)) launch_arcs_segtrans(h->stream, l, T, cb.S, cb.M, final_w, d_arcs);
+  else launch_arcs(h->stream, l, T, frame_model, cb.S, cb.M, cb.m_per_frame, final_w, d_arcs);
   std::vector<scrf_arc> dense;
   if (h->shadow) dense.resize(na);
-  hipError_t e = hipMemcpyAsync(h->shadow ? dense.data() : arcs, d_arcs.p, sizeof(scrf_arc) * na, hipMemcpyDeviceToHost, h->stream);
+  hipError_t e = hipMemcpyAsync(h->shadow ? dense.data() : arcs, d_arcs, sizeof(scrf_arc) * na, hipMemcpyDeviceToHost, h->stream);
   if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
   if (e != hipSuccess) return fail(h, SCRF_ERR_HIP, "scrf_lattice_arcs: %s", hipGetErrorString(e));
   if (h->shadow) {
@@ -2901,7 +2881,7 @@ extern "C" int scrf_lattice_arcs(scrf_handle h, scrf_batch b, uint32_t u, int no
 // ---------------------------------------------------------------------------------------------
 extern "C" int scrf_lattice_prune_batch(scrf_handle h, scrf_batch b, double beam, uint64_t* arc_off, double* best_cost) {
   if (!h || !b || !arc_off) return SCRF_ERR_INVALID;
-  h->lp_batch = nullptr;   // whatever happens, the previous result is gone
+  h->lp.batch = nullptr;   // whatever happens, the previous result is gone
   RCCHK(model_ok(h, "scrf_lattice_prune_batch", "the lattice beam"));
   if (!(beam > 0.0) || !std::isfinite(beam))
     return fail(h, SCRF_ERR_INVALID, "scrf_lattice_prune_batch: the beam must be finite and > 0 (got %g)", beam);
@@ -2912,11 +2892,11 @@ extern "C" int scrf_lattice_prune_batch(scrf_handle h, scrf_batch b, double beam
   const bool frame_model = h->cfg.model_type == SCRF_STDFRAME;
   const uint32_t U = b->U;
   const size_t by_best = pad256(sizeof(double) * U), need_meta = by_best + pad256(sizeof(uint64_t) * (U + 1));
-  RCCHK(grow_device(h, &h->lp_meta, &h->lp_meta_cap, need_meta));
-  double* d_best = (double*)h->lp_meta;
-  uint64_t* d_uoff = (uint64_t*)(h->lp_meta + by_best);
+  RCCHK(reserve_drained(h, h->lp.meta, need_meta));
+  double* d_best = (double*)h->lp.meta.get();
+  uint64_t* d_uoff = (uint64_t*)(h->lp.meta + by_best);
   CallTimer call(h);
-  h->n_lp_calls++;
+  h->lp.n_calls++;
   const Need nd = Need::lattice();
   ScrfBatchView bv = b->view();
   uint64_t total = 0;   // kept arcs of the chunks done
@@ -2924,7 +2904,7 @@ extern "C" int scrf_lattice_prune_batch(scrf_handle h, scrf_batch b, double beam
     const uint32_t u1 = plan_chunk(h, b, u0, nd);
     ChunkBufs cb;
     RCCHK(score_chunk(h, b, u0, u1, nd, &cb));
-    h->n_lp_chunks++;
+    h->lp.n_chunks++;
     const uint32_t nutt = u1 - u0;
     const uint64_t nfr = b->frame_off[u1] - b->frame_off[u0], n_nodes = nfr + nutt;
     const uint32_t t_max = longest_utt(b, u0, u1);
@@ -2935,54 +2915,45 @@ extern "C" int scrf_lattice_prune_batch(scrf_handle h, scrf_batch b, double beam
     uint64_t kept = 0;   // the chunk's arcs must have room before they are written
     HIPCHK(h, hipMemcpyAsync(&kept, cb.lat_node_off + n_nodes, sizeof(uint64_t), hipMemcpyDeviceToHost, cb.st));
     HIPCHK(h, hipStreamSynchronize(cb.st));
-    if (total + kept > h->lp_cap) {
-      const uint64_t cap = std::max<uint64_t>(std::max<uint64_t>(total + kept, 2 * h->lp_cap), 1u << 16);
-      scrf_arc* na = nullptr;
-      HIPCHK(h, hipMalloc((void**)&na, sizeof(scrf_arc) * cap));
-      hipError_t e = total ? hipMemcpyAsync(na, h->lp_arcs, sizeof(scrf_arc) * total, hipMemcpyDeviceToDevice, cb.st) : hipSuccess;
-      if (e == hipSuccess) e = hipStreamSynchronize(cb.st);
-      if (e != hipSuccess) { hipFree(na); return fail(h, SCRF_ERR_HIP, "scrf_lattice_prune_batch: %s", hipGetErrorString(e)); }
-      hipFree(h->lp_arcs);
-      h->lp_arcs = na; h->lp_cap = cap;
-    }
+    HIPCHK(h, h->lp.arcs.reserve_keep(total + kept, total, cb.st));   // the arcs of the chunks done move with it
     KT_RUN("k_lat_emit", cb.st, launch_lat_emit(cb.st, l, bv, u0, nutt, t_max, cb.S, cb.M, cb.m_per_frame, frame_model, cb.lat, beam, cb.lat_node_off,
-                                                total, h->lp_cap, h->lp_arcs));
+                                                total, h->lp.arcs.cap(), h->lp.arcs));
     HIPCHK(h, hipGetLastError());
     total += kept;
     u0 = u1;
   }
-  h->lp_off.resize(U + 1);
-  HIPCHK(h, hipMemcpyAsync(h->lp_off.data(), d_uoff, sizeof(uint64_t) * (U + 1), hipMemcpyDeviceToHost, h->stream));
+  h->lp.off.resize(U + 1);
+  HIPCHK(h, hipMemcpyAsync(h->lp.off.data(), d_uoff, sizeof(uint64_t) * (U + 1), hipMemcpyDeviceToHost, h->stream));
   if (best_cost) HIPCHK(h, hipMemcpyAsync(best_cost, d_best, sizeof(double) * U, hipMemcpyDeviceToHost, h->stream));
   HIPCHK(h, hipStreamSynchronize(h->stream));
   call.stop();
-  if (h->lp_off[U] != total) return fail(h, SCRF_ERR_INVALID, "scrf_lattice_prune_batch: arc count mismatch (internal)");
-  memcpy(arc_off, h->lp_off.data(), sizeof(uint64_t) * (U + 1));
-  h->lp_batch = b;
+  if (h->lp.off[U] != total) return fail(h, SCRF_ERR_INVALID, "scrf_lattice_prune_batch: arc count mismatch (internal)");
+  memcpy(arc_off, h->lp.off.data(), sizeof(uint64_t) * (U + 1));
+  h->lp.batch = b;
   return SCRF_OK;
 }
 
 extern "C" int scrf_lattice_pruned_arcs(scrf_handle h, scrf_batch b, uint32_t u0, uint32_t n, scrf_arc* arcs, uint64_t cap) {
   if (!h || !b) return SCRF_ERR_INVALID;
-  if (h->lp_batch != b)
+  if (h->lp.batch != b)
     return fail(h, SCRF_ERR_INVALID, "scrf_lattice_pruned_arcs: no valid result for this batch (call scrf_lattice_prune_batch first; new weights, "
                 "another prune call or destroying the batch drop it)");
   if ((uint64_t)u0 + n > b->U) return fail(h, SCRF_ERR_INVALID, "scrf_lattice_pruned_arcs: utterances %u .. %llu of a batch of %u", u0,
                                            (unsigned long long)u0 + n, b->U);
-  const uint64_t a0 = h->lp_off[u0], na = h->lp_off[u0 + n] - a0;
+  const uint64_t a0 = h->lp.off[u0], na = h->lp.off[u0 + n] - a0;
   if (cap < na) return fail(h, SCRF_ERR_INVALID, "scrf_lattice_pruned_arcs: room for %llu arcs, %llu needed", (unsigned long long)cap, (unsigned long long)na);
   if (na == 0) return SCRF_OK;
   if (!arcs) return SCRF_ERR_INVALID;
   HIPCHK(h, hipSetDevice(h->device));
-  HIPCHK(h, hipMemcpyAsync(arcs, h->lp_arcs + a0, sizeof(scrf_arc) * na, hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(h, hipMemcpyAsync(arcs, h->lp.arcs + a0, sizeof(scrf_arc) * na, hipMemcpyDeviceToHost, h->stream));
   HIPCHK(h, hipStreamSynchronize(h->stream));
   return SCRF_OK;
 }
 
 extern "C" int scrf_lattice_prune_stats(scrf_handle h, uint64_t* n_calls, uint64_t* n_chunks) {
   if (!h) return SCRF_ERR_INVALID;
-  if (n_calls) *n_calls = h->n_lp_calls;
-  if (n_chunks) *n_chunks = h->n_lp_chunks;
+  if (n_calls) *n_calls = h->lp.n_calls;
+  if (n_chunks) *n_chunks = h->lp.n_chunks;
   return SCRF_OK;
 }
 
@@ -3010,7 +2981,7 @@ static int decode_chunks(scrf_handle h, scrf_batch b, const Need& nd, Search&& s
       uint32_t n_fix = 0;
       HIPCHK(h, hipMemcpyAsync(&n_fix, cb.fix_cnt, sizeof(uint32_t), hipMemcpyDeviceToHost, h->stream));
       HIPCHK(h, hipStreamSynchronize(h->stream));
-      h->n_decode_fix += n_fix;
+      h->dec.n_fix += n_fix;
       if (n_fix <= cb.fix_cap) {
         PhaseTimer tm(h, PH_VIT);
         launch_decode_fixup(h->stream, b->d_frames[0], b->recipe[0].in_width, b->view(), u0, u1, h->d_lambda, l, cb.fix_cnt,
@@ -3020,7 +2991,7 @@ static int decode_chunks(scrf_handle h, scrf_batch b, const Need& nd, Search&& s
         u0 = u1;
         continue;
       }
-      h->n_decode_fallback++;
+      h->dec.n_fallback++;
       u_end = u1;  // this range again, through the EXACT path
     }
     do {
@@ -3037,42 +3008,17 @@ static int decode_chunks(scrf_handle h, scrf_batch b, const Need& nd, Search&& s
   return rc;
 }
 
-// the result buffers of the decode entry points (dec_*) hold this batch
-static int decode_result_room(scrf_handle h, scrf_batch b) {
-  const uint64_t NF = b->frame_off[b->U];
-  if (NF > h->dec_cap_f) {
-    hipFree(h->dec_lab); h->dec_lab = nullptr;
-    if (h->dec_hlab) hipHostFree(h->dec_hlab);
-    h->dec_hlab = nullptr; h->dec_cap_f = 0;
-    HIPCHK(h, hipMalloc((void**)&h->dec_lab, sizeof(uint32_t) * NF));
-    HIPCHK(h, hipHostMalloc((void**)&h->dec_hlab, sizeof(uint32_t) * NF, hipHostMallocDefault));
-    h->dec_cap_f = NF;
-  }
-  if (b->U > h->dec_cap_u) {
-    hipFree(h->dec_n); hipFree(h->dec_cost); h->dec_n = nullptr; h->dec_cost = nullptr;
-    if (h->dec_hn) hipHostFree(h->dec_hn);
-    if (h->dec_hcost) hipHostFree(h->dec_hcost);
-    h->dec_hn = nullptr; h->dec_hcost = nullptr; h->dec_cap_u = 0;
-    HIPCHK(h, hipMalloc((void**)&h->dec_n, sizeof(uint32_t) * b->U));
-    HIPCHK(h, hipMalloc((void**)&h->dec_cost, sizeof(float) * b->U));
-    HIPCHK(h, hipHostMalloc((void**)&h->dec_hn, sizeof(uint32_t) * b->U, hipHostMallocDefault));
-    HIPCHK(h, hipHostMalloc((void**)&h->dec_hcost, sizeof(float) * b->U, hipHostMallocDefault));
-    h->dec_cap_u = b->U;
-  }
-  return SCRF_OK;
-}
-
 // labels, counts and costs of the whole batch to the caller, through the pinned images; closes the timed region
 static int decode_result_fetch(scrf_handle h, scrf_batch b, const char* fn, CallTimer& call, uint32_t* seg_labels, uint64_t max_labels,
                                uint64_t* lab_off, float* best_cost) {
   const uint64_t NF = b->frame_off[b->U];
-  const uint32_t *lab = h->dec_hlab, *cnt = h->dec_hn;
-  hipError_t e = hipMemcpyAsync(h->dec_hlab, h->dec_lab, sizeof(uint32_t) * NF, hipMemcpyDeviceToHost, h->stream);
-  if (e == hipSuccess) e = hipMemcpyAsync(h->dec_hn, h->dec_n, sizeof(uint32_t) * b->U, hipMemcpyDeviceToHost, h->stream);
-  if (e == hipSuccess && best_cost) e = hipMemcpyAsync(h->dec_hcost, h->dec_cost, sizeof(float) * b->U, hipMemcpyDeviceToHost, h->stream);
+  const uint32_t *lab = h->dec.hlab, *cnt = h->dec.hn;
+  hipError_t e = hipMemcpyAsync(h->dec.hlab, h->dec.lab, sizeof(uint32_t) * NF, hipMemcpyDeviceToHost, h->stream);
+  if (e == hipSuccess) e = hipMemcpyAsync(h->dec.hn, h->dec.n, sizeof(uint32_t) * b->U, hipMemcpyDeviceToHost, h->stream);
+  if (e == hipSuccess && best_cost) e = hipMemcpyAsync(h->dec.hcost, h->dec.cost, sizeof(float) * b->U, hipMemcpyDeviceToHost, h->stream);
   if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
   if (e != hipSuccess) return fail(h, SCRF_ERR_HIP, "%s: %s", fn, hipGetErrorString(e));
-  if (best_cost) memcpy(best_cost, h->dec_hcost, sizeof(float) * b->U);
+  if (best_cost) memcpy(best_cost, h->dec.hcost, sizeof(float) * b->U);
   call.stop();
   uint64_t pos = 0;
   for (uint32_t u = 0; u < b->U; u++) {
@@ -3092,10 +3038,10 @@ extern "C" int scrf_viterbi_batch(scrf_handle h, scrf_batch b, uint32_t* seg_lab
   const ScrfLayout& l = h->lay;
   const bool frame_model = h->cfg.model_type == SCRF_STDFRAME;
   CallTimer call(h);
-  int rc = decode_result_room(h, b);
-  if (rc != SCRF_OK) return rc;
-  uint32_t *d_lab = h->dec_lab, *d_n = h->dec_n;
-  float* d_cost = h->dec_cost;
+  HIPCHK(h, h->dec.reserve(b->frame_off[b->U], b->U));
+  int rc = SCRF_OK;
+  uint32_t *d_lab = h->dec.lab, *d_n = h->dec.n;
+  float* d_cost = h->dec.cost;
   if (nstate(h) || stdseg(h)) {
     // the chunk's scores in the scratch arena (chunks planned with the `post` sizing), path costs and back pointers per
     // (row, label) in buffers of their own
@@ -3107,13 +3053,13 @@ extern "C" int scrf_viterbi_batch(scrf_handle h, scrf_batch b, uint32_t* seg_lab
       rc = run_small_chunk(h, b, u0, u1, &sm);
       if (rc != SCRF_OK) break;
       const uint64_t rows = nstate(h) ? b->frame_off[u1] - b->frame_off[u0] : b->seg_off[u1] - b->seg_off[u0];
-      DevBuf<float> vc;
-      DevBuf<uint16_t> bp;
-      hipError_t e = vc.alloc(rows * n_lab);
-      if (e == hipSuccess) e = bp.alloc(rows * n_lab);
+      DevArray<float> vc;
+      DevArray<uint16_t> bp;
+      hipError_t e = vc.reserve(rows * n_lab);
+      if (e == hipSuccess) e = bp.reserve(rows * n_lab);
       if (e == hipSuccess) {
-        if (nstate(h)) launch_ns_viterbi(h->stream, l, b->view(), u0, u1 - u0, sm.ns.S, sm.ns.TD, sm.ns.TO, sm.ns.TE, vc.p, bp.p, d_lab, d_n, d_cost);
-        else launch_stdseg_viterbi(h->stream, l, n_lab, b->view(), u0, u1 - u0, sm.sg.S, sm.sg.MX, vc.p, bp.p, d_lab, d_n, d_cost);
+        if (nstate(h)) launch_ns_viterbi(h->stream, l, b->view(), u0, u1 - u0, sm.ns.S, sm.ns.TD, sm.ns.TO, sm.ns.TE, vc, bp, d_lab, d_n, d_cost);
+        else launch_stdseg_viterbi(h->stream, l, n_lab, b->view(), u0, u1 - u0, sm.sg.S, sm.sg.MX, vc, bp, d_lab, d_n, d_cost);
         e = hipStreamSynchronize(h->stream);
       }
       if (e != hipSuccess) { rc = fail(h, SCRF_ERR_HIP, "scrf_viterbi_batch: %s", hipGetErrorString(e)); break; }
@@ -3139,11 +3085,11 @@ extern "C" int scrf_viterbi_batch(scrf_handle h, scrf_batch b, uint32_t* seg_lab
 // uploaded once per call into buffers kept across calls (scrf_align_batch, scrf_transcript_batch)
 static int upload_transcripts(scrf_handle h, uint32_t U, const uint32_t* phones, const uint64_t* phone_off, const uint64_t* cell_off) {
   const uint64_t NP = phone_off[U];
-  RCCHK(grow_device(h, &h->al_ph, &h->al_cap_ph, NP));
-  RCCHK(grow_device(h, &h->al_off, &h->al_cap_off, 2 * ((size_t)U + 1)));   // two offset arrays
-  if (NP) HIPCHK(h, hipMemcpyAsync(h->al_ph, phones, sizeof(uint32_t) * NP, hipMemcpyHostToDevice, h->stream));
-  HIPCHK(h, hipMemcpyAsync(h->al_off, phone_off, sizeof(uint64_t) * (U + 1), hipMemcpyHostToDevice, h->stream));
-  HIPCHK(h, hipMemcpyAsync(h->al_off + (U + 1), cell_off, sizeof(uint64_t) * (U + 1), hipMemcpyHostToDevice, h->stream));
+  RCCHK(reserve_drained(h, h->tx.ph, NP));
+  RCCHK(reserve_drained(h, h->tx.off, 2 * ((size_t)U + 1)));   // two offset arrays
+  if (NP) HIPCHK(h, hipMemcpyAsync(h->tx.ph, phones, sizeof(uint32_t) * NP, hipMemcpyHostToDevice, h->stream));
+  HIPCHK(h, hipMemcpyAsync(h->tx.off, phone_off, sizeof(uint64_t) * (U + 1), hipMemcpyHostToDevice, h->stream));
+  HIPCHK(h, hipMemcpyAsync(h->tx.off + (U + 1), cell_off, sizeof(uint64_t) * (U + 1), hipMemcpyHostToDevice, h->stream));
   HIPCHK(h, hipStreamSynchronize(h->stream));   // the host arrays are the caller's (and pageable)
   return SCRF_OK;
 }
@@ -3166,7 +3112,7 @@ extern "C" int scrf_align_batch(scrf_handle h, scrf_batch b, const uint32_t* pho
   // back-pointer cells before each utterance (the chunk planner sizes a chunk with them), the longest transcript the
   // workgroup kernel may meet
   const bool wave_on = h->kn.align_wave && align_wave_supported(l);
-  h->al_bp_off.assign(U + 1, 0);
+  h->tx.bp_off.assign(U + 1, 0);
   for (uint32_t u = 0; u < U; u++) {
     if (phone_off[u + 1] < phone_off[u]) return fail(h, SCRF_ERR_INVALID, "scrf_align_batch: phone_off decreases at utterance %u", u);
     const uint64_t K = phone_off[u + 1] - phone_off[u];
@@ -3178,30 +3124,30 @@ extern "C" int scrf_align_batch(scrf_handle h, scrf_batch b, const uint32_t* pho
     if (fits && (K > 64 || !wave_on) && align_group_smem_bytes(l, K) > 160 * 1024)
       return fail(h, SCRF_ERR_INVALID, "scrf_align_batch: utterance %u's transcript of %llu phones needs (%u + 2) x %llu x 4 = %zu bytes of LDS, "
                   "a workgroup has %d", u, (unsigned long long)K, l.D, (unsigned long long)K, align_group_smem_bytes(l, K), 160 * 1024);
-    h->al_bp_off[u + 1] = h->al_bp_off[u] + (fits ? (uint64_t)b->T[u] * K : 0);
+    h->tx.bp_off[u + 1] = h->tx.bp_off[u] + (fits ? (uint64_t)b->T[u] * K : 0);
   }
   HIPCHK(h, hipSetDevice(h->device));
   const bool frame_model = h->cfg.model_type == SCRF_STDFRAME;
   CallTimer call(h);
-  RCCHK(decode_result_room(h, b));
-  RCCHK(upload_transcripts(h, U, phones, phone_off, h->al_bp_off.data()));
-  h->n_al_calls++;
+  HIPCHK(h, h->dec.reserve(b->frame_off[b->U], b->U));
+  RCCHK(upload_transcripts(h, U, phones, phone_off, h->tx.bp_off.data()));
+  h->tx.n_al_calls++;
   RCCHK(decode_chunks(h, b, Need::alignment(), [&](const ChunkBufs& cb, uint32_t u0, uint32_t u1, bool fast) {
-    const ScrfAlignArgs aa{h->al_ph, h->al_off, h->al_off + (U + 1), cb.al_bp, mode};
+    const ScrfAlignArgs aa{h->tx.ph, h->tx.off, h->tx.off + (U + 1), cb.al_bp, mode};
     uint64_t k_max = 0;   // over the transcripts that fit
     for (uint32_t u = u0; u < u1; u++)
-      if (h->al_bp_off[u + 1] > h->al_bp_off[u]) k_max = std::max(k_max, phone_off[u + 1] - phone_off[u]);
+      if (h->tx.bp_off[u + 1] > h->tx.bp_off[u]) k_max = std::max(k_max, phone_off[u + 1] - phone_off[u]);
     const double* S = fast ? nullptr : cb.S;
     const float* Wn = fast ? cb.Wn : nullptr;
-    h->n_al_chunks++;
+    h->tx.n_al_chunks++;
     if (wave_on && k_max <= 64) {
-      h->n_al_wave++;
+      h->tx.n_al_wave++;
       KT_RUN("k_align_wave", h->stream, launch_align_wave(h->stream, l, b->view(), u0, u1 - u0, S, Wn, cb.M, cb.m_per_frame, frame_model, aa,
-                                                          h->dec_lab, h->dec_n, h->dec_cost));
+                                                          h->dec.lab, h->dec.n, h->dec.cost));
     } else {
-      h->n_al_group++;
+      h->tx.n_al_group++;
       KT_RUN("k_align_group", h->stream, launch_align_group(h->stream, l, b->view(), u0, u1 - u0, (uint32_t)k_max, S, Wn, cb.M, cb.m_per_frame,
-                                                            frame_model, aa, h->dec_lab, h->dec_n, h->dec_cost));
+                                                            frame_model, aa, h->dec.lab, h->dec.n, h->dec.cost));
     }
   }));
   return decode_result_fetch(h, b, "scrf_align_batch", call, seg_labels, max_labels, lab_off, cost);
@@ -3209,10 +3155,10 @@ extern "C" int scrf_align_batch(scrf_handle h, scrf_batch b, const uint32_t* pho
 
 extern "C" int scrf_align_stats(scrf_handle h, uint64_t* n_calls, uint64_t* n_chunks, uint64_t* n_wave, uint64_t* n_group) {
   if (!h) return SCRF_ERR_INVALID;
-  if (n_calls) *n_calls = h->n_al_calls;
-  if (n_chunks) *n_chunks = h->n_al_chunks;
-  if (n_wave) *n_wave = h->n_al_wave;
-  if (n_group) *n_group = h->n_al_group;
+  if (n_calls) *n_calls = h->tx.n_al_calls;
+  if (n_chunks) *n_chunks = h->tx.n_al_chunks;
+  if (n_wave) *n_wave = h->tx.n_al_wave;
+  if (n_group) *n_group = h->tx.n_al_group;
   return SCRF_OK;
 }
 
@@ -3235,10 +3181,10 @@ static int transcript_chunk(scrf_handle h, scrf_batch b, const uint64_t* phone_o
   ScrfBatchView bv = b->view();
   uint64_t k_max = 0;   // over the transcripts that fit
   for (uint32_t u = u0; u < u1; u++)
-    if (h->tr_cell_off[u + 1] > h->tr_cell_off[u]) k_max = std::max(k_max, phone_off[u + 1] - phone_off[u]);
-  const ScrfTransArgs ta{h->al_ph, h->al_off, h->al_off + (U + 1), h->tr_inv, h->tr_inv + phone_off[U], cb.tr_aB, cb.tr_bE,
+    if (h->tx.cell_off[u + 1] > h->tx.cell_off[u]) k_max = std::max(k_max, phone_off[u + 1] - phone_off[u]);
+  const ScrfTransArgs ta{h->tx.ph, h->tx.off, h->tx.off + (U + 1), h->tx.inv, h->tx.inv + phone_off[U], cb.tr_aB, cb.tr_bE,
                          mode, cb.lin ? 1 : 0, to.seg ? 1 : 0};
-  h->n_tr_chunks++;
+  h->tx.n_tr_chunks++;
   KT_RUN("k_transcript", cb.st, launch_transcript(cb.st, l, bv, u0, u1 - u0, k_max, cb.S, cb.smax, cb.M, cb.m_per_frame, ta, b->d_status,
                                                   to.log_num, to.occ, to.end));
   *nl += 1;
@@ -3265,7 +3211,7 @@ extern "C" int scrf_transcript_batch(scrf_handle h, scrf_batch b, const uint32_t
   if (phone_off[0] != 0 || (NP && !phones)) return fail(h, SCRF_ERR_INVALID, "%s: phone_off must start at 0 and phones must be given", fn);
   // the checks of every transcript, the cells before each utterance (the chunk planner sizes a chunk with them) and the
   // inverted lists: per utterance its positions sorted by label (a counting sort: ascending inside a label)
-  h->tr_cell_off.assign(U + 1, 0);
+  h->tx.cell_off.assign(U + 1, 0);
   for (uint32_t u = 0; u < U; u++) {
     if (phone_off[u + 1] < phone_off[u] || phone_off[u + 1] > NP) return fail(h, SCRF_ERR_INVALID, "%s: phone_off decreases at utterance %u", fn, u);
     const uint64_t K = phone_off[u + 1] - phone_off[u];
@@ -3282,18 +3228,18 @@ extern "C" int scrf_transcript_batch(scrf_handle h, scrf_batch b, const uint32_t
     if (fits && transcript_smem_bytes(l, K) + 128 > 160 * 1024)   // + the 16 per-wavefront parts of end[t]
       return fail(h, SCRF_ERR_INVALID, "%s: utterance %u's transcript of %llu phones needs (%u + 2) x %llu x 8 = %zu bytes of LDS, "
                   "a workgroup has %d less 128", fn, u, (unsigned long long)K, l.D, (unsigned long long)K, transcript_smem_bytes(l, K), 160 * 1024);
-    h->tr_cell_off[u + 1] = h->tr_cell_off[u] + (fits ? (uint64_t)b->T[u] * K : 0);
+    h->tx.cell_off[u + 1] = h->tx.cell_off[u] + (fits ? (uint64_t)b->T[u] * K : 0);
   }
   std::vector<uint32_t> q;   // [3][nq]: utterance, end frame, label value
   uint64_t nq = 0;
   RCCHK(seg_queries(h, b, fn, seg_labels, lab_off, seg_post != nullptr, &q, &nq));
   const uint64_t n_inv = NP + (uint64_t)U * (l.L + 1);
-  h->tr_inv_h.assign(n_inv, 0);
+  h->tx.inv_h.assign(n_inv, 0);
   for (uint32_t u = 0; u < U; u++) {
     const uint64_t K = phone_off[u + 1] - phone_off[u];
     const uint32_t* ph = phones + phone_off[u];
-    uint32_t* ioff = h->tr_inv_h.data() + NP + (uint64_t)u * (l.L + 1);
-    uint32_t* ipos = h->tr_inv_h.data() + phone_off[u];
+    uint32_t* ioff = h->tx.inv_h.data() + NP + (uint64_t)u * (l.L + 1);
+    uint32_t* ipos = h->tx.inv_h.data() + phone_off[u];
     for (uint64_t k = 0; k < K; k++) ioff[ph[k] + 1]++;
     for (uint32_t c = 0; c < l.L; c++) ioff[c + 1] += ioff[c];
     for (uint64_t k = 0; k < K; k++) ipos[ioff[ph[k]]++] = (uint32_t)k;   // ioff[c] now = the end of c's list = the start of c + 1's
@@ -3302,12 +3248,12 @@ extern "C" int scrf_transcript_batch(scrf_handle h, scrf_batch b, const uint32_t
   }
   HIPCHK(h, hipSetDevice(h->device));
   TransOut to;
-  RCCHK(grow_device(h, &h->tr_inv, &h->tr_cap_inv, n_inv));
+  RCCHK(reserve_drained(h, h->tx.inv, n_inv));
   RCCHK(post_out_carve(h, b, frame_post, end_post, seg_post, q, nq, lab_off, U, &to, &to.log_num));
-  if (n_inv) HIPCHK(h, hipMemcpyAsync(h->tr_inv, h->tr_inv_h.data(), sizeof(uint32_t) * n_inv, hipMemcpyHostToDevice, h->stream));
-  RCCHK(upload_transcripts(h, U, phones, phone_off, h->tr_cell_off.data()));   // ends with a synchronize: q may go
+  if (n_inv) HIPCHK(h, hipMemcpyAsync(h->tx.inv, h->tx.inv_h.data(), sizeof(uint32_t) * n_inv, hipMemcpyHostToDevice, h->stream));
+  RCCHK(upload_transcripts(h, U, phones, phone_off, h->tx.cell_off.data()));   // ends with a synchronize: q may go
   CallTimer call(h);
-  h->n_tr_calls++;
+  h->tx.n_tr_calls++;
   const uint64_t fb0 = h->n_lin_fallback;
   int latch[2] = {0, 0};
   const int rc = run_with_redo(h, latch, [&] {
@@ -3315,7 +3261,7 @@ extern "C" int scrf_transcript_batch(scrf_handle h, scrf_batch b, const uint32_t
       return transcript_chunk(h, b, phone_off, mode, to, cb, u0, u1, nl);
     });
   });
-  if (h->n_lin_fallback != fb0) h->n_tr_redone++;
+  if (h->n_lin_fallback != fb0) h->tx.n_tr_redone++;
   if (rc != SCRF_OK) return rc;
   call.stop();
   if (latch[0] != 0) return fail(h, latch[0], "%s: utterance %d: %s", fn, latch[1], status_text(latch[0]));
@@ -3330,9 +3276,9 @@ extern "C" int scrf_transcript_batch(scrf_handle h, scrf_batch b, const uint32_t
 
 extern "C" int scrf_transcript_stats(scrf_handle h, uint64_t* n_calls, uint64_t* n_chunks, uint64_t* n_redone) {
   if (!h) return SCRF_ERR_INVALID;
-  if (n_calls) *n_calls = h->n_tr_calls;
-  if (n_chunks) *n_chunks = h->n_tr_chunks;
-  if (n_redone) *n_redone = h->n_tr_redone;
+  if (n_calls) *n_calls = h->tx.n_tr_calls;
+  if (n_chunks) *n_chunks = h->tx.n_tr_chunks;
+  if (n_redone) *n_redone = h->tx.n_tr_redone;
   return SCRF_OK;
 }
 
@@ -3361,8 +3307,8 @@ extern "C" int scrf_set_frame_mass_check(scrf_handle h, int on) {
 
 extern "C" int scrf_decode_stats(scrf_handle h, uint64_t* n_recomputed, uint64_t* n_fallback_chunks) {
   if (!h) return SCRF_ERR_INVALID;
-  if (n_recomputed) *n_recomputed = h->n_decode_fix;
-  if (n_fallback_chunks) *n_fallback_chunks = h->n_decode_fallback;
+  if (n_recomputed) *n_recomputed = h->dec.n_fix;
+  if (n_fallback_chunks) *n_fallback_chunks = h->dec.n_fallback;
   return SCRF_OK;
 }
 
@@ -3480,7 +3426,7 @@ static int allreduce_block(scrf_handle h, hipStream_t st, int part) {
     if (g_rccl.GroupStart && g_rccl.GroupEnd) { const int r2 = g_rccl.GroupEnd(); if (r == 0) r = r2; }
   } else {
     const uint32_t n = l.L * l.nsf + 8;
-    if (!h->d_pack && hipMalloc((void**)&h->d_pack, sizeof(double) * n) != hipSuccess) { scrf_comm_abort(h); return fail(h, SCRF_ERR_HIP, "hipMalloc of the pack buffer failed"); }
+    if (h->d_pack.reserve(n) != hipSuccess) { scrf_comm_abort(h); return fail(h, SCRF_ERR_HIP, "hipMalloc of the pack buffer failed"); }
     hipLaunchKernelGGL(k_pack_state, dim3((n + 255) / 256), dim3(256), 0, st, h->d_grad, h->d_sums, l.L, l.stride, l.nsf, h->d_pack);
     r = g_rccl.AllReduce(h->d_pack, h->d_pack, n, SCRF_NCCL_DOUBLE, SCRF_NCCL_SUM, h->comm, st);
     hipLaunchKernelGGL(k_unpack_state, dim3((n + 255) / 256), dim3(256), 0, st, h->d_pack, l.L, l.stride, l.nsf, h->d_grad, h->d_sums);
@@ -3604,7 +3550,7 @@ extern "C" int scrf_sgd_step(scrf_handle h, double lr_or_eta, int use_adagrad, d
                   use_adagrad, eps);
   HIPCHK(h, hipMemsetAsync(h->d_sums, 0, sizeof(double) * 4, h->stream));
   h->m0_valid = false;
-  h->lp_batch = nullptr;
+  h->lp.batch = nullptr;
   HIPCHK(h, hipGetLastError());
   return SCRF_OK;
 }
@@ -3616,7 +3562,7 @@ extern "C" int scrf_kernel_timing(scrf_handle h, char* buf, size_t cap) {
   if (!h || !buf || cap == 0) return SCRF_ERR_INVALID;
   std::string out;
   char line[256];
-  for (const auto& k : h->ktimes) {
+  for (const auto& k : h->tm.ktimes) {
     snprintf(line, sizeof line, "%s\t%.6f\t%u\n", k.name.c_str(), k.ms, k.n);
     out += line;
   }
@@ -3635,10 +3581,10 @@ extern "C" int scrf_posterior_stats(scrf_handle h, uint64_t* n_split, uint64_t* 
   if (n_whole) *n_whole = h->n_post_whole;
   return SCRF_OK;
 }
-extern "C" int scrf_enable_timing(scrf_handle h, int on) { if (!h) return SCRF_ERR_INVALID; h->timing = on != 0; return SCRF_OK; }
+extern "C" int scrf_enable_timing(scrf_handle h, int on) { if (!h) return SCRF_ERR_INVALID; h->tm.on = on != 0; return SCRF_OK; }
 extern "C" int scrf_last_timing(scrf_handle h, float* ms, uint32_t* n_launch) {
   if (!h) return SCRF_ERR_INVALID;
-  if (ms) memcpy(ms, h->ms, sizeof(h->ms));
-  if (n_launch) memcpy(n_launch, h->nlaunch, sizeof(h->nlaunch));
+  if (ms) memcpy(ms, h->tm.ms, sizeof(h->tm.ms));
+  if (n_launch) memcpy(n_launch, h->tm.nlaunch, sizeof(h->tm.nlaunch));
   return SCRF_OK;
 }

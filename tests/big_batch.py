@@ -39,20 +39,20 @@ def nfr(Ts, counts):
 
 # ---- the plans (restated; the CPU test pins them on values worked out by hand) -----------------------------------------
 def expf_rows_per_chunk(n_seg):
-    """scrf_engine.cpp:1001-1005: about 1024 K-chunks of the state count contraction, multiples of 32 rows, at least 4096"""
+    """expf_rows_per_chunk (scrf_engine.cpp): about 1024 K-chunks of the state count contraction, multiples of 32 rows, at least 4096"""
     rpc = (n_seg + 1023) // 1024
     rpc = (rpc + 31) & ~31
     return max(rpc, 4096)
 
 
 def atb_rows_per_chunk(n_fr):
-    """scrf_engine.cpp:1043-1046: about 4096 K-chunks of the transition-bias contraction, multiples of 4 frames, at least 64"""
+    """atb_rows_per_chunk (scrf_engine.cpp): about 4096 K-chunks of the transition-bias contraction, multiples of 4 frames, at least 64"""
     rpc = ((n_fr + 4095) // 4096 + 3) & ~3
     return max(rpc, 64)
 
 
 def sl_rows_per_chunk(n_fr):
-    """scrf_engine.cpp:1777-1780: at most 256 K-chunks of the STDSEG linear path's contractions, multiples of 32 frames, at
+    """sl_rows_per_chunk (scrf_engine.cpp): at most 256 K-chunks of the STDSEG linear path's contractions, multiples of 32 frames, at
     least 64"""
     rpc = ((n_fr + 255) // 256 + 31) & ~31
     return max(rpc, 64)
@@ -62,9 +62,9 @@ def sl_rows_per_chunk(n_fr):
 EXPF_BREAK = 4096 * 1024         # segments: rows per chunk grow past 4096
 ATB_BREAK = 64 * 4096            # frames: rows per chunk grow past 64
 SL_BREAK = 64 * 256              # frames
-TRANSFRAME_BREAK = 3 * 2048      # frames: transframe_chunks (scrf_engine.cpp:1019-1039) reaches its base of 4 and starts to search
-PLAN_CHUNK_CAP = 65535           # utterances per chunk, plan_chunk (scrf_engine.cpp:1318)
-SL_CHUNK_CAP = 32767             # utterances per chunk, STDSEG linear path (scrf_engine.cpp:1887)
+TRANSFRAME_BREAK = 3 * 2048      # frames: transframe_chunks (scrf_engine.cpp) reaches its base of 4 and starts to search
+PLAN_CHUNK_CAP = 65535           # utterances per chunk, plan_chunk (scrf_engine.cpp)
+SL_CHUNK_CAP = 32767             # utterances per chunk, STDSEG linear path (stdseg_lin_pipe, scrf_engine.cpp)
 
 
 # ---- tiling ---------------------------------------------------------------------------------------------------------
@@ -246,15 +246,15 @@ def array_bytes(name):
             out[a] = ns * L * 8
         elif a == "X":                  # materialised windows [nseg][F] float
             out[a] = ns * orc.window_width(W, D, 0, 0, True) * 4
-        elif a == "X_hybrid":           # [avg | max | min | onehot(d)], padded to 16 bytes (hybrid_row_floats, scrf_engine.cpp:1150)
+        elif a == "X_hybrid":           # [avg | max | min | onehot(d)], padded to 16 bytes (hybrid_row_floats, scrf_engine.cpp)
             out[a] = ns * ((3 * W + D + 3) & ~3) * 4
         elif a == "M":                  # [nfr][L * L] fp64
             out[a] = nf * L * L * 8
-        elif a == "Sd":                 # STDSEG linear path: [D][nfr][La] fp64 (stdseg_lin_layout, scrf_engine.cpp:1791)
+        elif a == "Sd":                 # STDSEG linear path: [D][nfr][La] fp64 (stdseg_lin_layout, scrf_engine.cpp)
             out[a] = D * nf * L * 8
         elif a == "M2":                 # STDSEG_NO_DUR: [nseg][L * L] fp64
             out[a] = ns * L * L * 8
-        elif a == "TE":                 # n-state: [nfr][P * P] fp64 next to five [nfr][L] (nstate_layout, scrf_engine.cpp:1909-1911)
+        elif a == "TE":                 # n-state: [nfr][P * P] fp64 next to five [nfr][L] (nstate_layout, scrf_engine.cpp)
             out[a] = nf * max(kw["P"] * kw["P"], kw["P"] * kw["K"]) * 8
         elif a == "cells":              # transcript scoring: aB and bE, each [sum T * K] fp64 over the chunk's transcripts
             out[a] = 8 * sum(n * T * K for T, K, n in zip(kw["Ts"], TRANSCRIPT_K[name], row["counts"]))
@@ -273,7 +273,7 @@ def lattice_arcs(T, L, D):
 
 def need_bytes(name, prec=EXACT):
     """device memory a case is checked against before its engine is created: the arrays of its one chunk as chunk_layout
-    (scrf_engine.cpp:1162-1306) takes them, rounded up generously (a bound for the free-memory check, not a plan)"""
+    (chunk_layout, scrf_engine.cpp) takes them, rounded up generously (a bound for the free-memory check, not a plan)"""
     row = CASES[name]
     kw = row["kw"]
     ns, nf, nu = case_sizes(name)
