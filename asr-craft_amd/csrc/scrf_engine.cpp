@@ -133,6 +133,20 @@ struct PrunedLattice {
   uint64_t n_calls = 0, n_chunks = 0;
 };
 
+// result of scrf_nbest_batch: the labels of every hypothesis of the batch back to back, where each
+// hypothesis's labels start and its cost, sized by what the searches found; outside the scratch budget, grows geometrically,
+// kept across calls.  One result, tied to the batch and the weights, as the pruned lattice is
+struct NBestResult {
+  DevArray<uint32_t> lab;       // [labels of all hypotheses]
+  DevArray<uint64_t> lab_off;   // [hypotheses + 1]
+  DevArray<float> cost;         // [hypotheses]
+  DevArray<uint64_t> hyp_off;   // [U + 1] hypotheses before each utterance
+  scrf_batch batch = nullptr;   // the batch of the valid result, or nullptr
+  std::vector<uint64_t> off;    // [U + 1] host image of hyp_off
+  uint64_t n_labels = 0;
+  uint64_t n_calls = 0, n_chunks = 0, n_fast_chunks = 0;
+};
+
 // scrf_align_batch: the transcripts of the call on the device (phones | phone_off, back-pointer offsets),
 // kept across calls; bp_off is the host image chunk_layout sizes a chunk's back pointers with.
 // scrf_transcript_batch: the transcripts go into ph / off as well; inv holds each transcript's positions
@@ -165,7 +179,7 @@ using namespace scrf_eng;
 // first needed, and scrf_destroy never hears of it.  Who waits for what before a buffer of the handle is dropped for a larger
 // one (DevArray::reserve itself waits for nothing):
 //   ensure_scratch                               both streams
-//   reserve_drained (post_buf, lp.meta, tx.*)    the engine stream
+//   reserve_drained (post_buf, lp.meta, tx.*, nb.hyp_off)   the engine stream
 //   dec.*, rtab.tab, d_pack                      nothing
 struct __attribute__((visibility("hidden"))) scrf_engine_s {   // (hidden: its constructor and destructor are not for export)
   scrf_config cfg;
@@ -232,6 +246,7 @@ struct __attribute__((visibility("hidden"))) scrf_engine_s {   // (hidden: its c
   // result arrays of scrf_posteriors_batch (whole batch: chunking stays invisible), kept across calls like the decode buffers
   DevArray<char> post_buf;
   PrunedLattice lp;
+  NBestResult nb;
   Transcripts tx;
   std::string err;
   Timing tm;
@@ -561,7 +576,7 @@ static int vec_io(scrf_handle h, double* dev, const double* in, double* out, uin
 }
 extern "C" int scrf_set_lambda(scrf_handle h, const double* v, uint32_t n) {
   int rc = vec_io(h, h ? h->d_lambda : nullptr, v, nullptr, n, "scrf_set_lambda");
-  if (rc == SCRF_OK) { h->m0_valid = false; h->lp.batch = nullptr; }
+  if (rc == SCRF_OK) { h->m0_valid = false; h->lp.batch = nullptr; h->nb.batch = nullptr; }
   return rc;
 }
 extern "C" int scrf_get_lambda(scrf_handle h, double* v, uint32_t n) { return vec_io(h, h ? h->d_lambda : nullptr, nullptr, v, n, "scrf_get_lambda"); }
@@ -750,6 +765,7 @@ extern "C" int scrf_batch_destroy(scrf_handle h, scrf_batch b) {
   if (!b) return SCRF_OK;
   if (h) hipSetDevice(h->device);
   if (h && h->lp.batch == b) h->lp.batch = nullptr;
+  if (h && h->nb.batch == b) h->nb.batch = nullptr;
   if (h && !h->kn.pool_on()) hipStreamSynchronize(h->stream);
   // (pool: no synchronisation here -- the blocks wait in the pool until the engine stream has passed this point)
   for (void* p : b->blocks) pool_release(h, p);
@@ -1099,6 +1115,7 @@ struct ChunkBufs {
   uint64_t* lat_node_off = nullptr; // [nodes + 1]
   uint16_t* al_bp = nullptr;        // forced alignment: sum of T * K back pointers over the chunk's transcripts that fit
   double *tr_aB = nullptr, *tr_bE = nullptr;   // transcript scoring: the same cells, forward (segment start) and backward (segment end) sums
+  ScrfNbestBufs nb = {0, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};   // N-best: back pointers, final lists, offsets
   bool lamT_ready = false;   // sparse maps: h->d_lamT already re-laid for this call (scrf_fb_batch: once, before the lanes fork)
 };
 
@@ -1108,6 +1125,7 @@ struct Need {
   bool fb = false, post = false, beta = false, vit = false;
   bool fused = false, vitfast = false, la = false, hybrid = false;   // the batch's form (set_batch_form, decode_chunks)
   bool ponly = false, plog = false, lat = false, align = false, trans = false;
+  uint32_t nbest = 0;   // scrf_nbest_batch: the list length
   // one constructor per kind of pass, so that no call site depends on the order of the fields
   static Need scores() { return Need(); }                                              // windows and scores only
   static Need recursion() { Need n; n.fb = n.beta = true; return n; }                  // + the log-domain node values (hooks)
@@ -1118,8 +1136,11 @@ struct Need {
   static Need viterbi() { Need n; n.vit = true; return n; }
   static Need lattice() { Need n; n.lat = true; return n; }
   static Need alignment() { Need n; n.align = true; return n; }
+  static Need nbest_of(uint32_t n_best) { Need n; n.nbest = n_best; return n; }
 };
 // trans (scrf_transcript_batch): two doubles per (frame, transcript position) cell of the chunk
+// nbest (scrf_nbest_batch): two 32-bit back pointers per (frame, label, rank), and per (utterance, rank) the final list and
+// the offsets of the backtrace
 // align (scrf_align_batch): the back pointers of the chunk's (frame, transcript position) cells
 // lat (scrf_lattice_prune_batch): four distance arrays over the chunk's frames and the node counts / offsets
 // plog: ponly through the log-domain recursion (SCRF_PREC_EXACT: no FAST precision)
@@ -1308,6 +1329,18 @@ static void chunk_layout(scrf_handle h, scrf_batch b, uint32_t u0, uint32_t u1, 
     cb->lat_node_off = a.take<uint64_t>(nfr + nutt + 1);
   }
   if (nd.align) cb->al_bp = a.take<uint16_t>(h->tx.bp_off[u1] - h->tx.bp_off[u0]);
+  if (nd.nbest) {
+    const size_t n = (size_t)nutt * nd.nbest;
+    cb->nb.N = nd.nbest;
+    cb->nb.bp_b = a.take<uint32_t>(nfr * l.L * nd.nbest);
+    cb->nb.bp_e = a.take<uint32_t>(nfr * l.L * nd.nbest);
+    cb->nb.fin_cost = a.take<float>(n);
+    cb->nb.fin_ptr = a.take<uint32_t>(n);
+    cb->nb.cnt = a.take<uint32_t>(n);
+    cb->nb.lab_pos = a.take<uint64_t>(n + 1);
+    cb->nb.hyp_pos = a.take<uint64_t>(n);
+    cb->nb.tot = a.take<uint64_t>(2);
+  }
   if (nd.trans) {
     cb->tr_aB = a.take<double>(h->tx.cell_off[u1] - h->tx.cell_off[u0]);
     cb->tr_bE = a.take<double>(h->tx.cell_off[u1] - h->tx.cell_off[u0]);
@@ -3153,6 +3186,101 @@ extern "C" int scrf_align_batch(scrf_handle h, scrf_batch b, const uint32_t* pho
   return decode_result_fetch(h, b, "scrf_align_batch", call, seg_labels, max_labels, lab_off, cost);
 }
 
+// ---------------------------------------------------------------------------------------------
+// batched N-best decoding: scrf_viterbi_batch's chunk loop and score stage, a search that keeps a list per
+// state; the backtrace of a chunk runs before its scratch goes, into a result sized by what it found
+// ---------------------------------------------------------------------------------------------
+extern "C" int scrf_nbest_batch(scrf_handle h, scrf_batch b, uint32_t n_best, uint64_t* hyp_off, uint64_t* n_labels) {
+  if (!h || !b || !hyp_off) return SCRF_ERR_INVALID;
+  const char* fn = "scrf_nbest_batch";
+  h->nb.batch = nullptr;   // whatever happens, the previous result is gone
+  RCCHK(model_ok(h, fn, "N-best decoding"));
+  const ScrfLayout& l = h->lay;
+  if (l.D > 0x7fff) return fail(h, SCRF_ERR_INVALID, "%s: maximum duration %u does not fit the 15 duration bits of a back pointer (at most %u)", fn, l.D, 0x7fffu);
+  if (l.L > 0xffff) return fail(h, SCRF_ERR_INVALID, "%s: %u labels do not fit the 16 label bits of a back pointer (at most %u)", fn, l.L, 0xffffu);
+  if (n_best == 0 || n_best > 0xffff) return fail(h, SCRF_ERR_INVALID, "%s: n_best must be 1 .. 65535 (got %u)", fn, n_best);
+  if (nbest_smem_bytes(l, n_best) > 160 * 1024)
+    return fail(h, SCRF_ERR_INVALID, "%s: n_best %u with %u labels and maximum duration %u needs (%u + 2) x %u x %u x 4 + %zu = %zu bytes of LDS, "
+                "a workgroup has %d", fn, n_best, l.L, l.D, l.D, l.L, n_best, nbest_smem_bytes(l, n_best) - sizeof(float) * ((size_t)l.D + 2) * l.L * n_best,
+                nbest_smem_bytes(l, n_best), 160 * 1024);
+  HIPCHK(h, hipSetDevice(h->device));
+  const bool frame_model = h->cfg.model_type == SCRF_STDFRAME;
+  const uint32_t U = b->U;
+  RCCHK(reserve_drained(h, h->nb.hyp_off, (size_t)U + 1));
+  CallTimer call(h);
+  h->nb.n_calls++;
+  ScrfBatchView bv = b->view();
+  uint64_t n_lab = 0, n_hyp = 0;   // of the chunks done
+  int rc2 = SCRF_OK;
+  if (U == 0) HIPCHK(h, hipMemsetAsync(h->nb.hyp_off, 0, sizeof(uint64_t), h->stream));
+  RCCHK(decode_chunks(h, b, Need::nbest_of(n_best), [&](const ChunkBufs& cb, uint32_t u0, uint32_t u1, bool fast) {
+    if (rc2 != SCRF_OK) return;
+    const uint32_t nutt = u1 - u0;
+    h->nb.n_chunks++;
+    if (fast) h->nb.n_fast_chunks++;
+    KT_RUN("k_nbest", h->stream, launch_nbest(h->stream, l, bv, u0, nutt, fast ? nullptr : cb.S, fast ? cb.Wn : nullptr, cb.M, cb.m_per_frame,
+                                              frame_model, cb.nb));
+    KT_RUN("k_nbest_count", h->stream, launch_nbest_count(h->stream, l, bv, u0, nutt, frame_model, cb.nb));
+    KT_RUN("k_nbest_scan", h->stream, launch_nbest_scan(h->stream, cb.nb, u0, nutt, n_lab, n_hyp, h->nb.hyp_off));
+    uint64_t tot[2] = {0, 0};   // the chunk's labels and hypotheses must have room before they are written
+    hipError_t e = hipMemcpyAsync(tot, cb.nb.tot, sizeof(tot), hipMemcpyDeviceToHost, h->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
+    // what the chunks done wrote moves with a growing array
+    if (e == hipSuccess) e = h->nb.lab.reserve_keep(n_lab + tot[0], n_lab, h->stream);
+    if (e == hipSuccess) e = h->nb.cost.reserve_keep(n_hyp + tot[1], n_hyp, h->stream);
+    if (e == hipSuccess) e = h->nb.lab_off.reserve_keep(n_hyp + tot[1] + 1, u0 ? n_hyp + 1 : 0, h->stream);   // (the first chunk finds nothing to keep)
+    if (e != hipSuccess) { rc2 = fail(h, SCRF_ERR_HIP, "%s: %s", fn, hipGetErrorString(e)); return; }
+    KT_RUN("k_nbest_trace", h->stream, launch_nbest_trace(h->stream, l, bv, u0, nutt, frame_model, cb.nb, h->nb.lab.cap(),
+                                                          std::min(h->nb.cost.cap(), h->nb.lab_off.cap() - 1), h->nb.lab, h->nb.lab_off, h->nb.cost));
+    n_lab += tot[0];
+    n_hyp += tot[1];
+  }));
+  if (rc2 != SCRF_OK) return rc2;
+  HIPCHK(h, hipGetLastError());
+  h->nb.off.resize((size_t)U + 1);
+  HIPCHK(h, hipMemcpyAsync(h->nb.off.data(), h->nb.hyp_off, sizeof(uint64_t) * ((size_t)U + 1), hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  call.stop();
+  if (h->nb.off[U] != n_hyp) return fail(h, SCRF_ERR_INVALID, "%s: hypothesis count mismatch (internal)", fn);
+  memcpy(hyp_off, h->nb.off.data(), sizeof(uint64_t) * ((size_t)U + 1));
+  if (n_labels) *n_labels = n_lab;
+  h->nb.n_labels = n_lab;
+  h->nb.batch = b;
+  return SCRF_OK;
+}
+
+extern "C" int scrf_nbest_paths(scrf_handle h, scrf_batch b, uint32_t u0, uint32_t n, uint32_t* seg_labels, uint64_t max_labels,
+                                uint64_t* lab_off, float* cost) {
+  if (!h || !b) return SCRF_ERR_INVALID;
+  const char* fn = "scrf_nbest_paths";
+  if (h->nb.batch != b)
+    return fail(h, SCRF_ERR_INVALID, "%s: no valid result for this batch (call scrf_nbest_batch first; new weights, another N-best call or "
+                "destroying the batch drop it)", fn);
+  if ((uint64_t)u0 + n > b->U) return fail(h, SCRF_ERR_INVALID, "%s: utterances %u .. %llu of a batch of %u", fn, u0, (unsigned long long)u0 + n, b->U);
+  if (!lab_off) return SCRF_ERR_INVALID;
+  const uint64_t h0 = h->nb.off[u0], nh = h->nb.off[u0 + n] - h0;
+  if (nh == 0) { lab_off[0] = 0; return SCRF_OK; }
+  HIPCHK(h, hipSetDevice(h->device));
+  HIPCHK(h, hipMemcpyAsync(lab_off, h->nb.lab_off + h0, sizeof(uint64_t) * (nh + 1), hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  const uint64_t a0 = lab_off[0], na = lab_off[nh] - a0;
+  for (uint64_t i = 0; i <= nh; i++) lab_off[i] -= a0;
+  if (max_labels < na) return fail(h, SCRF_ERR_INVALID, "%s: room for %llu labels, %llu needed", fn, (unsigned long long)max_labels, (unsigned long long)na);
+  if (na && !seg_labels) return SCRF_ERR_INVALID;
+  if (na) HIPCHK(h, hipMemcpyAsync(seg_labels, h->nb.lab + a0, sizeof(uint32_t) * na, hipMemcpyDeviceToHost, h->stream));
+  if (cost && nh) HIPCHK(h, hipMemcpyAsync(cost, h->nb.cost + h0, sizeof(float) * nh, hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  return SCRF_OK;
+}
+
+extern "C" int scrf_nbest_stats(scrf_handle h, uint64_t* n_calls, uint64_t* n_chunks, uint64_t* n_fast_chunks) {
+  if (!h) return SCRF_ERR_INVALID;
+  if (n_calls) *n_calls = h->nb.n_calls;
+  if (n_chunks) *n_chunks = h->nb.n_chunks;
+  if (n_fast_chunks) *n_fast_chunks = h->nb.n_fast_chunks;
+  return SCRF_OK;
+}
+
 extern "C" int scrf_align_stats(scrf_handle h, uint64_t* n_calls, uint64_t* n_chunks, uint64_t* n_wave, uint64_t* n_group) {
   if (!h) return SCRF_ERR_INVALID;
   if (n_calls) *n_calls = h->tx.n_al_calls;
@@ -3551,6 +3679,7 @@ extern "C" int scrf_sgd_step(scrf_handle h, double lr_or_eta, int use_adagrad, d
   HIPCHK(h, hipMemsetAsync(h->d_sums, 0, sizeof(double) * 4, h->stream));
   h->m0_valid = false;
   h->lp.batch = nullptr;
+  h->nb.batch = nullptr;
   HIPCHK(h, hipGetLastError());
   return SCRF_OK;
 }

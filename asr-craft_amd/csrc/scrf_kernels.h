@@ -352,4 +352,33 @@ void launch_transcript_seg(hipStream_t st, const ScrfLayout& lay, ScrfBatchView 
                            const uint32_t* q_e, const uint32_t* q_lab, uint64_t q0, uint64_t nq, const double* S,
                            const double* smax, const ScrfTransArgs& ta, const double* log_num, double* out);
 
+
+// ---- N-best decoding (scrf_nbest.hip)
+struct ScrfNbestBufs {
+  uint32_t N;           // list length = the n_best of the call
+  uint32_t* bp_b;       // [frames of the chunk][L][N] boundary(t, l)[r] (frame model: state): predecessor label << 16 | its rank
+  uint32_t* bp_e;       // [frames of the chunk][L][N] end(t, l)[r]: duration << 16 | rank in boundary(t - d + 1, l)
+  float* fin_cost;      // [utterances of the chunk][N] ascending, +inf where the utterance has fewer paths
+  uint32_t* fin_ptr;    // [utterances of the chunk][N] last label << 16 | its rank in end(T-1, .)
+  uint32_t* cnt;        // [utterances of the chunk][N] segments of the hypothesis, 0: none
+  uint64_t* lab_pos;    // [utterances * N + 1] where each hypothesis's labels start in the result
+  uint64_t* hyp_pos;    // [utterances * N] index of each hypothesis in the result
+  uint64_t* tot;        // {labels, hypotheses} of the chunk
+};
+// head ranks of one wavefront's merge: one 16-bit entry per list, L (boundary, final) or D + 1 (end) of them
+__host__ __device__ inline uint32_t nbest_heads(uint32_t L, uint32_t D) { return ((L > D + 1 ? L : D + 1) + 1) & ~1u; }
+// dynamic LDS of a workgroup: end double-buffered and the boundary ring, (D + 2) L N floats, + the head ranks
+size_t nbest_smem_bytes(const ScrfLayout& lay, uint32_t n_best);
+// S (fp64 scores) or Wn (their float arc weights, segment model only): exactly one is given
+void launch_nbest(hipStream_t st, const ScrfLayout& lay, ScrfBatchView bv, uint32_t u0, uint32_t n_utts, const double* S, const float* Wn,
+                  const double* M, int m_per_frame, int frame_model, const ScrfNbestBufs& nb);
+void launch_nbest_count(hipStream_t st, const ScrfLayout& lay, ScrfBatchView bv, uint32_t u0, uint32_t n_utts, int frame_model,
+                        const ScrfNbestBufs& nb);
+// lab_base / hyp_base: labels and hypotheses of the chunks done; hyp_off [U + 1]: the batch's hypothesis offsets
+void launch_nbest_scan(hipStream_t st, const ScrfNbestBufs& nb, uint32_t u0, uint32_t n_utts, uint64_t lab_base, uint64_t hyp_base,
+                       uint64_t* hyp_off);
+// res_lab [lab_cap], res_off [hyp_cap + 1], res_cost [hyp_cap]: the result of the whole batch
+void launch_nbest_trace(hipStream_t st, const ScrfLayout& lay, ScrfBatchView bv, uint32_t u0, uint32_t n_utts, int frame_model,
+                        const ScrfNbestBufs& nb, uint64_t lab_cap, uint64_t hyp_cap, uint32_t* res_lab, uint64_t* res_off, float* res_cost);
+
 #endif  // SCRF_KERNELS_H_

@@ -53,6 +53,15 @@
 //   crf_conf_given=transcript|none (default none = the bytes of before): whether the last column of crf_output_conffile is
 //   the posterior of the aligned segment given the transcript, or the free one (which mostly measures whether free
 //   decoding agrees with the transcript).
+// A sixth one (N-best lists), in crf_decode_mode=decode on the best-paths-only branch:
+//   crf_nbest=N crf_output_nbestfile=PATH: beside the label file, the N least-cost paths of every utterance, computed on the
+//   device in batches of crf_bunch_size utterances, one line per hypothesis: `sent rank cost n lab_1 .. lab_n [logp]` (cost with
+//   9 significant digits; rank 0 is the label file's path).  crf_nbest_unique=path (default): labels as the label file
+//   prints them; crf_nbest_unique=phones: one line per distinct collapsed phone sequence (its cheapest path), the labels
+//   being that sequence.  crf_nbest_rescore=1 (needs crf_nbest_unique=phones) appends logp = log P(sequence | x) (17
+//   significant digits), the sum over every alignment of the sequence; it costs up to N transcript passes per batch.  The
+//   label file and crf_output_conffile keep their bytes.  Refused in align or posteriors mode, with crf_lat_outdir,
+//   crf_output_mlffile or crf_lat_beam, and the three other flags without crf_nbest.
 #include "cli_common.h"
 
 #include <math.h>
@@ -128,6 +137,22 @@ int main(int argc, char** argv) {
     std::cerr << "crf_output_conffile goes with the best paths of the label file only: not with crf_decode_mode=" << mode
               << ", crf_lat_outdir or crf_output_mlffile" << std::endl;
     return 1;
+  }
+  const bool want_nbest = a.has("crf_nbest");
+  for (const char* k : {"crf_output_nbestfile", "crf_nbest_unique", "crf_nbest_rescore"})
+    if (a.has(k) && !want_nbest) { std::cerr << k << " needs crf_nbest=N" << std::endl; return 1; }
+  const long n_best = a.num("crf_nbest", 0);
+  const std::string nbest_unique = a.str("crf_nbest_unique", "path");
+  const long nbest_rescore = a.num("crf_nbest_rescore", 0);
+  if (want_nbest) {
+    if (n_best < 1 || n_best > 65535) { std::cerr << "crf_nbest=" << a.str("crf_nbest") << ": the number of hypotheses must be 1 .. 65535" << std::endl; return 1; }
+    if (!a.has("crf_output_nbestfile")) { std::cerr << "crf_nbest needs crf_output_nbestfile=PATH" << std::endl; return 1; }
+    if (nbest_unique != "path" && nbest_unique != "phones") { std::cerr << "crf_nbest_unique=" << nbest_unique << " (path|phones)" << std::endl; return 1; }
+    if (nbest_rescore != 0 && nbest_rescore != 1) { std::cerr << "crf_nbest_rescore=" << nbest_rescore << " (0|1)" << std::endl; return 1; }
+    if (nbest_rescore && nbest_unique != "phones") { std::cerr << "crf_nbest_rescore=1 needs crf_nbest_unique=phones: it scores phone sequences" << std::endl; return 1; }
+    if (align_mode || post_mode) { std::cerr << "crf_nbest lists the best paths of crf_decode_mode=decode: not with crf_decode_mode=" << mode << std::endl; return 1; }
+    for (const char* k : {"crf_lat_outdir", "crf_output_mlffile", "crf_lat_beam"})
+      if (a.has(k)) { std::cerr << "crf_nbest goes with the best paths of the label file only: not with " << k << std::endl; return 1; }
   }
   if (align_mode && !a.has("hardtarget_file")) { std::cerr << "hardtarget_file required when crf_decode_mode=align" << std::endl; return -1; }
   std::vector<std::vector<uint32_t> > hard_labs;
@@ -455,12 +480,34 @@ int main(int argc, char** argv) {
   } else if (!a.has("crf_lat_outdir") && !want_mlf && !align_mode) {
     // best paths only: whole device batches of utterances (crf_bunch_size of them, default 256)
     const size_t bunch = (size_t)std::max(1L, a.num("crf_bunch_size", 256));
+    std::ofstream nbest;
+    if (want_nbest) {
+      nbest.open(a.str("crf_output_nbestfile").c_str());
+      if (!nbest.is_open()) { std::cerr << "ERROR: Failed opening file: " << a.str("crf_output_nbestfile") << std::endl; return -1; }
+    }
     bool at_end = strm.nextseg() == QN_SEGID_BAD;
     while (!at_end) {
       try {
         std::vector<std::vector<uint32_t> > labs;
         std::vector<float> costs;
-        if (want_conf) {
+        if (want_nbest) {
+          // hypothesis 0 is the best path, byte for byte: the label file (and the confidence file) from the same batch
+          std::vector<std::vector<CRF_NbestHyp> > hyps;
+          std::vector<std::vector<double> > sp;
+          crf_amd_nbest(&strm, &crf, bunch, (uint32_t)n_best, nbest_unique == "phones", nbest_rescore != 0, &hyps, &at_end, &labs, want_conf ? &sp : nullptr);
+          if (want_conf) write_conf(labs, sp);
+          for (size_t i = 0; i < hyps.size(); i++)
+            for (size_t r = 0; r < hyps[i].size(); r++) {
+              const CRF_NbestHyp& hy = hyps[i][r];
+              const std::vector<uint32_t>& v = nbest_unique == "phones" ? hy.phones : hy.labels;
+              nbest.precision(9);
+              nbest << u + i << " " << r << " " << hy.cost << " " << v.size();
+              for (uint32_t x : v) nbest << " " << x;
+              nbest.precision(17);
+              if (nbest_rescore) nbest << " " << hy.logp;
+              nbest << "\n";
+            }
+        } else if (want_conf) {
           // the same best paths (scrf_viterbi_batch on the same batch) with the posterior of each of their segments
           std::vector<std::vector<double> > sp;
           crf_amd_posteriors(&strm, &crf, bunch, nullptr, nullptr, nullptr, &labs, &costs, &sp, &at_end);

@@ -690,6 +690,29 @@ size_t crf_amd_transcript_scores(CRF_FeatureStream* ftr_strm, CRF_Model* crf, si
                                  std::vector<std::vector<double> >* seg_post_given,
                                  std::vector<std::vector<double> >* seg_post_free, bool* at_end);
 
+// N-best lists (scrf_nbest_batch) of the stream's CURRENT utterance and up to max_utts - 1 following ones in
+// one device batch, in the style of crf_amd_best_paths (the stream is advanced with nextseg(); *at_end is set when it ran
+// out).  hyps[u] = the utterance's hypotheses ascending by cost, at most n_best: labels as crf_amd_best_paths returns them
+// (hypothesis 0 is its path) and the float path cost.  With unique_phones every hypothesis is reduced to its collapsed phone
+// sequence (label % nActualLabs, equal neighbours merged) and only the first -- the cheapest -- of each distinct sequence is
+// kept, its sequence in `phones`.  With rescore (needs unique_phones) every kept hypothesis also gets logp = log P(phones | x)
+// = log_num - zx from scrf_transcript_batch(SCRF_ALIGN_RUNS) on the same batch; otherwise logp is NaN.  The transcript pass
+// scores one sequence per utterance, so rescoring costs as many passes over the batch as the longest kept list has entries:
+// up to n_best calls of the transcript pass.  A model the engine refuses throws the engine's message.
+struct CRF_NbestHyp {
+  std::vector<uint32_t> labels;   // l + nActualLabs * (d - 1) per segment (one label per frame for the frame model)
+  float cost = 0.0f;
+  std::vector<uint32_t> phones;   // unique_phones only
+  double logp = 0.0;              // rescore only
+};
+// best_labels / best_seg_post (each may be NULL): hypothesis 0 of every utterance before any reduction -- crf_amd_best_paths'
+// path -- and the posterior of each of its segments (scrf_posteriors_batch on the same batch, as crf_amd_posteriors gives it).
+size_t crf_amd_nbest(CRF_FeatureStream* ftr_strm, CRF_Model* crf, size_t max_utts, uint32_t n_best, bool unique_phones, bool rescore,
+                     std::vector<std::vector<CRF_NbestHyp> >* hyps, bool* at_end, std::vector<std::vector<uint32_t> >* best_labels = nullptr,
+                     std::vector<std::vector<double> >* best_seg_post = nullptr);
+// the collapsed phone sequence of a path: label % n_labs per segment, equal neighbours merged
+std::vector<uint32_t> crf_amd_collapsed_phones(const std::vector<uint32_t>& labels, uint32_t n_labs);
+
 // lattice builders: same call as the reference's templates; the arcs come from the engine in
 // AddArc order and are replayed into the caller's FST object
 class CRF_LatticeBuilder {

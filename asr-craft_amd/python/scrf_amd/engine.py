@@ -454,6 +454,28 @@ class Engine:
         self._chk(self.lib.scrf_align_stats(self.h, *[C.byref(x) for x in v]))
         return tuple(x.value for x in v)
 
+    def nbest_batch(self, batch, n):
+        """The n least-cost paths of every utterance (scrf_nbest_batch + scrf_nbest_paths), pairwise distinct and ascending by
+        cost.  Returns (RaggedLabels over all hypotheses of the batch back to back, hyp_off [U + 1] = the hypotheses before
+        each utterance, costs [hypotheses]): hypothesis i of utterance u is labs[hyp_off[u] + i], in viterbi_batch's label
+        format.  An utterance has min(n, its number of paths) hypotheses; hypothesis 0 is viterbi_batch's result."""
+        U = batch.n
+        hoff = np.empty(U + 1, dtype=np.uint64)
+        nl = C.c_uint64()
+        self._chk(self.lib.scrf_nbest_batch(self.h, batch.handle, C.c_uint32(int(n)), _p(hoff), C.byref(nl)))
+        H = int(hoff[U])
+        labs = np.empty(max(nl.value, 1), dtype=np.uint32); off = np.empty(H + 1, dtype=np.uint64)
+        cost = np.empty(H, dtype=np.float32)
+        self._chk(self.lib.scrf_nbest_paths(self.h, batch.handle, C.c_uint32(0), C.c_uint32(U), _p(labs), C.c_uint64(nl.value), _p(off),
+                                            _p(cost)))
+        return RaggedLabels(labs, off), hoff, cost
+
+    def nbest_stats(self):
+        """(scrf_nbest_batch calls, searches launched -- one per chunk --, those on the fast-decode path's float arc weights) since create"""
+        v = [C.c_uint64() for _ in range(3)]
+        self._chk(self.lib.scrf_nbest_stats(self.h, *[C.byref(x) for x in v]))
+        return tuple(x.value for x in v)
+
     @staticmethod
     def _ragged(x, U):
         """(flat uint32 values, uint64 offsets [U + 1]) of per-utterance sequences or of a RaggedLabels"""

@@ -429,6 +429,46 @@ int scrf_transcript_batch(scrf_handle h, scrf_batch b, const uint32_t* phones, c
  * above, computeAlignedAlphaBeta's, lost every path of a fitting transcript to underflow, or the free recursion gave up) */
 int scrf_transcript_stats(scrf_handle h, uint64_t* n_calls, uint64_t* n_chunks, uint64_t* n_redone);
 
+/* ---- N-best decoding ------------------------------------------------------------------------------ */
+/* replaces: ShortestPath(lat, n) over buildLattice's lattice, for every utterance of the batch.  The hypotheses are the
+ * complete paths of the lattice exactly as scrf_lattice_arcs(..., norm = 0, ...) defines it, with its float weights.  The
+ * cost of a path is the left-to-right float sum scrf_viterbi_batch forms: 0.0f + w_seg(start), then alternately
+ * + w_boundary and + w_seg, then + (-0.0f) and + 0.0f (frame model: state(0,c) = 0.0f + w, then + float(-(M+S)) per frame,
+ * final weight 0.0f).  The result for utterance u is the min(n_best, number of paths) paths of least cost, pairwise distinct
+ * and ascending by cost.  The recursion is scrf_viterbi_batch's with a list of up to n_best entries per state:
+ *   boundary(t,l)[0..N) <- the N least of { end(t-1,p)[r] + w_boundary(M_t,p,l) },  candidates ordered by (cost, p, r)
+ *   end(t,l)[0..N)      <- the N least of { 0.0f + w_seg(t,t+1,l) (t < lab_max_dur) ; boundary(t',l)[r] + w_seg(t,t-t'+1,l) },
+ *                          ordered by (cost, the start arc first, then t' ascending = d descending, r ascending)
+ *   final[0..N)         <- the N least of { (end(T-1,l)[r] + (-0.0f)) + 0.0f },  ordered by (cost, l ascending, r ascending)
+ * frame model: one merge per (t,c) over state(t-1,p)[r] + w_frame, ordered by (cost, p, r).  Float addition is monotone: the
+ * r-th least cost into a state plus w is the r-th least cost through that arc, and the union of the per-predecessor N-least
+ * lists contains the N least overall, so the multiset of the N least path costs is defined bit for bit whatever the
+ * evaluation order, and every cost returned is that path's own left-to-right sum.  Which path is returned on ties is fixed
+ * by the stable order above; with n_best = 1 it is scrf_viterbi_batch's strict-improvement rule.  Hypothesis 0 of every
+ * utterance is scrf_viterbi_batch's result, labels and cost byte for byte.  (OpenFST's ShortestPath(n) associates its float
+ * sums differently: parity with it is unpinned, as for the best path.)
+ * Labels are in scrf_viterbi_batch's format (l + num_labs * (d-1), one per frame for the frame model): any hypothesis can go
+ * into scrf_posteriors_batch or scrf_transcript_batch as a segment query.  The batch needs no labels.  A T = 0 utterance has
+ * 0 hypotheses; a path whose float cost is not finite is not a hypothesis.
+ * scrf_nbest_batch runs the search and keeps the result on the device: hyp_off[u] = hypotheses of the utterances before u,
+ * *n_labels = the labels of all of them.  scrf_nbest_paths fetches the hypotheses of utterances u0 .. u0+n-1 back to back,
+ * H = hyp_off[u0+n] - hyp_off[u0] of them: lab_off[i] .. lab_off[i+1] (lab_off [H+1], starting at 0) are hypothesis i's
+ * labels in seg_labels, cost[i] its cost.  The result belongs to the batch and the weights it was computed from:
+ * scrf_set_lambda, scrf_sgd_step, another scrf_nbest_batch or destroying the batch drop it.  scrf_nbest_paths without a valid
+ * result, with a bad range or with max_labels too small is SCRF_ERR_INVALID (the message names the count needed).
+ * Arc weights as in scrf_viterbi_batch (the fast-decode path where that call takes it, bit-identical); chunks under
+ * scratch_bytes, which the back pointers (8 * num_labs * n_best bytes per frame) are part of; the result lives outside it,
+ * sized by the labels found.  One workgroup per utterance, a wavefront per merge; (lab_max_dur + 2) * num_labs * n_best * 4
+ * bytes and a few KiB of head ranks must fit a workgroup's 160 KiB of LDS (SCRF_ERR_INVALID beyond, with the figure).  No
+ * atomics: two runs and any chunking give the same bytes.
+ * Models: as scrf_align_batch; SCRF_STDSEG, SCRF_STDSEG_NO_DUR, num_states > 1, lab_max_dur > 32767, num_labs > 65535 and
+ * n_best = 0 or > 65535 are refused (SCRF_ERR_INVALID), all before any launch. */
+int scrf_nbest_batch(scrf_handle h, scrf_batch b, uint32_t n_best, uint64_t* hyp_off /* [n_utts+1] */, uint64_t* n_labels /* total, or NULL */);
+int scrf_nbest_paths(scrf_handle h, scrf_batch b, uint32_t u0, uint32_t n, uint32_t* seg_labels, uint64_t max_labels,
+                     uint64_t* lab_off /* [hyps of u0..u0+n-1, +1] */, float* cost /* [hyps], or NULL */);
+/* since scrf_create: calls; searches launched (one per chunk); of these, on the fast-decode path's float arc weights */
+int scrf_nbest_stats(scrf_handle h, uint64_t* n_calls, uint64_t* n_chunks, uint64_t* n_fast_chunks);
+
 /* ---- minibatch reduce + optimizer ------------------------------------------------------------ */
 /* replaces the join/sum/average of CRF_Minibatch_GradAccumulator::accumulateGradient
  * (trainers/accumulators/CRF_Minibatch_GradAccumulator.cpp:277-312): all-reduce (sum) of the
