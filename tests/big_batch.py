@@ -258,6 +258,8 @@ def array_bytes(name):
             out[a] = nf * max(kw["P"] * kw["P"], kw["P"] * kw["K"]) * 8
         elif a == "cells":              # transcript scoring: aB and bE, each [sum T * K] fp64 over the chunk's transcripts
             out[a] = 8 * sum(n * T * K for T, K, n in zip(kw["Ts"], TRANSCRIPT_K[name], row["counts"]))
+        elif a == "bp":                 # N-best: bp_b and bp_e, each [nfr][L][N] 32-bit back pointers (chunk_layout, scrf_engine.cpp)
+            out[a] = nf * L * NBEST_N[name] * 4
         elif a == "arcs":               # kept arcs, 20 bytes each: per frame t and duration d <= min(D, t + 1): L start or L * L
             out[a] = 20 * sum(n * lattice_arcs(T, L, D) for T, n in zip(kw["Ts"], row["counts"]))
         else:
@@ -291,6 +293,8 @@ def need_bytes(name, prec=EXACT):
     if name == "latprune":
         per_fr += 20 * (D * L + L * L)
     cells = 2 * array_bytes(name)["cells"] if "cells" in row["arrays"] else 0
+    if "bp" in row["arrays"]:           # both back-pointer arrays next to the scores
+        cells += 2 * array_bytes(name)["bp"]
     return int(1.25 * (ns * per_seg + nf * per_fr + cells)) + (2 << 30)
 
 
@@ -316,7 +320,10 @@ CASES = {
     "latprune": _case_row(dict(L=48, D=25, in_w=5, Ts=BASE_TS, seed=2101), [130, 110, 20, 8], arrays=("arcs",)),
     # transcript scoring: the long-K shape of tests/test_gpu_transcript.py, 510 utterances
     "transcript": _case_row(dict(L=2, D=2, in_w=2, Ts=[1100, 1090], seed=2110), [270, 240], arrays=("cells",)),
+    # N-best decoding at N = 64: 1500 utterances, 371,840 frames
+    "nbest": _case_row(dict(L=48, D=2, in_w=2, Ts=BASE_TS, seed=2111), [730, 570, 150, 50], arrays=("bp",)),
 }
+NBEST_N = {"nbest": 64}                           # list length (scrf_nbest_batch)
 TRANSCRIPT_K = {"transcript": [1030, 1020]}       # phones per base utterance (SCRF_ALIGN_ONE: K <= T <= K * D)
 
 

@@ -9,6 +9,8 @@ per frame, final weight 0.0f).  Float addition is monotone, so the multiset of t
                      r; final: l, r).  Returns [(labels, cost)] ascending, min(N, number of paths) of them
   enumerate_all(w)   form 2: every (segmentation, labelling), each path summed left to right; [(labels, cost)] in enumeration order
   path_cost(w, labs) the left-to-right float32 sum of one path
+  merge_by_heads(c, N)   a merge of form 1 redone head by head, the way a wavefront of 64 lanes does it: which output steps had
+                         two equal least heads in lists j and j + 64 (nbest(w, N, on_merge=...) hands over the candidates)
 """
 import itertools
 
@@ -37,7 +39,35 @@ def _merge(flat, N):
     return np.take_along_axis(flat, order, 0), order
 
 
-def nbest(w, N):
+def merge_by_heads(cand, N, lanes=64):
+    """cand [n_lists, N, cols]: per column n_lists sorted candidate lists in the order of the tie rule, +inf padded.  The first N
+    outputs of their merge, one head at a time; of all equal least heads the list of least j gives its head.  Returns (values
+    [N, cols], list taken [N, cols], and per (step, column) whether two of the equal least finite heads lay in lists j and j'
+    with j = j' mod lanes, that is in one lane of the kernel's nb_merge, [N, cols] bool)"""
+    n_lists, n, cols = cand.shape
+    assert n == N
+    padded = np.concatenate([cand, np.full((n_lists, 1, cols), INF, F32)], axis=1)
+    head = np.zeros((n_lists, cols), dtype=np.int64)
+    col = np.arange(cols)
+    lane = np.arange(n_lists) % lanes
+    val = np.full((N, cols), INF, F32)
+    src = np.zeros((N, cols), dtype=np.int64)
+    same_lane = np.zeros((N, cols), dtype=bool)
+    for s in range(N):
+        h = np.take_along_axis(padded, head[:, None, :], 1)[:, 0, :]   # [n_lists, cols]
+        m = h.min(0)
+        tie = (h == m[None, :]) & (m < INF)[None, :]
+        for k in range(min(lanes, n_lists - lanes) if n_lists > lanes else 0):
+            same_lane[s] |= tie[lane == k].sum(0) >= 2
+        j = np.argmax(h == m[None, :], axis=0)                          # the first list of least head
+        val[s], src[s] = m, j
+        head[j, col] += (m < INF)
+    return val, src, same_lane
+
+
+def nbest(w, N, on_merge=None):
+    """on_merge(kind, t, cand [n_lists, N, cols], values [N, cols]): called with the candidates of every merge ("boundary", "end",
+    "final") and its result"""
     T, L, D = w.T, w.L, w.D
     if T == 0:
         return []
@@ -52,6 +82,8 @@ def nbest(w, N):
             wt = np.stack([arc(t, p, labs) for p in range(L)]).astype(F32)    # [p, l]
             cand = (end[t - 1][:, :, None] + wt[:, None, :]).astype(F32)     # [p, r, l]: rows in (p, r) order
             val, order = _merge(cand.reshape(L * N, L), N)
+            if on_merge:
+                on_merge("boundary", t, cand, val)
             (end if w.frame_model else bnd)[t] = val.T
             bp_b[t, :, :, 0], bp_b[t, :, :, 1] = (order // N).T, (order % N).T
         if w.frame_model:
@@ -68,11 +100,17 @@ def nbest(w, N):
             dur += [d] * N
             rank += list(range(N))
         val, order = _merge(np.concatenate(rows), N)
+        if on_merge:
+            start = np.full((1, N, L), INF, F32)
+            start[0, 0] = rows[0][0]
+            on_merge("end", t, np.concatenate([start] + [r[None] for r in rows[1:]]), val)
         order = np.minimum(order, len(dur) - 1)   # padding rows: +inf, never followed
         end[t] = val.T
         bp_e[t, :, :, 0], bp_e[t, :, :, 1] = np.asarray(dur)[order].T, np.asarray(rank)[order].T
     wf = F32(0.0) if w.frame_model else F32(-0.0)
     val, order = _merge((end[T - 1] + wf).astype(F32).reshape(L * N, 1), N)
+    if on_merge:
+        on_merge("final", T - 1, (end[T - 1] + wf).astype(F32)[:, :, None], val)
     out = []
     for i in range(N):
         c = val[i, 0]

@@ -111,6 +111,12 @@ def test_every_axis_a_case_crosses_what_it_is_there_for():
     assert [len(p) for p in bb.transcript_phones("transcript")] == bb.TRANSCRIPT_K["transcript"]
     assert bb.array_bytes("transcript")["cells"] == 8 * (270 * 1100 * 1030 + 240 * 1090 * 1020)
     assert bb.need_bytes("transcript") < 16 << 30
+    # N-best: nfr * 48 * 64 * 4 bytes per back-pointer array pass 2^32 once nfr > 349,526; the lists fit a workgroup's LDS
+    kw, N = bb.CASES["nbest"]["kw"], bb.NBEST_N["nbest"]
+    nf = bb.case_sizes("nbest")[1]
+    assert nf > bb.MARGIN * 349526 and bb.array_bytes("nbest")["bp"] == nf * 48 * 64 * 4
+    assert (kw["D"] + 2) * kw["L"] * N * 4 + 16 * 48 * 2 <= 160 * 1024
+    assert bb.need_bytes("nbest") >= 2 * bb.array_bytes("nbest")["bp"] and bb.need_bytes("nbest") < 32 << 30
 
 
 def test_axis_b_passes_the_utterance_caps():

@@ -1,7 +1,7 @@
 """-m gpu: batches of the size the engine is built for -- arrays past 2^32 bytes inside one chunk (axis A) and more utterances
 than the chunk caps (axis B) -- against the CPU oracle.  Every batch is a few base utterances repeated many times
 (tests/big_batch.py), so the expected gradient is sum_i counts[i] * g_i of the per-utterance oracle gradients and the
-expected numerator, Zx, best path, alignment, transcript score, posteriors and pruned arcs of every copy are those of its base utterance.
+expected numerator, Zx, best path, N best paths, alignment, transcript score, posteriors and pruned arcs of every copy are those of its base utterance.
 tests/test_big_batch.py (no GPU) asserts that each shape here crosses the byte size and the plan breakpoints it is there for.
 
 Bounds, all taken from the suite and none measured on the code under test: gradient relative to max |g| 1e-9 EXACT / FAST,
@@ -32,6 +32,7 @@ import align_ref as ar
 import big_batch as bb
 import family_shapes as fs
 import latprune_ref as lr
+import nbest_ref as nr
 import orc
 import post_ref
 import scrf_amd
@@ -62,6 +63,7 @@ class Ref:
         self.case = bb.make_case(row_or_kw)
         self.exp = bb.Expected(self.case)
         self._utts = self._post = self._lat = None
+        self._nbest = {}
 
     def utts(self):
         """per base utterance (arcs, n_states, final, best labels, best cost)"""
@@ -78,6 +80,12 @@ class Ref:
         if self._post is None:
             self._post = [post_ref.utterance(self.case, u) for u in range(len(self.case.Ts))]
         return self._post
+
+    def nbest(self, N):
+        """per base utterance ((labels, cost), ..) of the N-best reference"""
+        if N not in self._nbest:
+            self._nbest[N] = [[(tuple(p), c) for p, c in nr.nbest(ar.case_weights(self.case, u), N)] for u in range(len(self.case.Ts))]
+        return self._nbest[N]
 
     def pruned(self, beam):
         """per base utterance (kept arcs, fp64 cost of the best path) under the beam"""
@@ -233,6 +241,32 @@ def check_align(what, t, ref, eng, b, labs, chunks=1):
         u = int(t.first[i])
         want_l, want_c = ar.dp(ar.case_weights(ref.case, i), tr[u], scrf_amd.ALIGN_ONE)
         assert [int(x) for x in al[u]] == want_l and np.float32(cost[u]).tobytes() == np.float32(want_c).tobytes(), (what, i)
+
+
+def check_nbest(what, t, ref, eng, b, N, chunks=1):
+    """the N best paths of every copy: labels, label counts and costs equal to the first copy's bit for bit, the first copy's
+    equal to tests/nbest_ref.py on the base utterance"""
+    s0 = eng.nbest_stats()
+    labs, hoff, cost = eng.nbest_batch(b, N)
+    s1 = eng.nbest_stats()
+    n, k = s1[1] - s0[1], len(t.counts)
+    hoff = np.asarray(hoff).astype(np.int64)
+    loff = np.asarray(labs.off).astype(np.int64)
+    same_l, _ = bb.blocks_vs_first(labs.flat, loff[hoff], t.base, k)
+    same_n, _ = bb.blocks_vs_first(np.diff(loff), hoff, t.base, k)
+    same_c, _ = bb.blocks_vs_first(cost, hoff, t.base, k)
+    print("%s nbest_batch N = %d: %d chunk(s) (%d on fast-decode weights), %d hypotheses, %d labels; copies vs first copy: labels %s, lengths %s, costs %s"
+          % (what, N, n, s1[2] - s0[2], int(hoff[-1]), int(loff[hoff[-1]]), same_l, same_n, same_c))
+    assert s1[0] == s0[0] + 1 and n == chunks, (what, s0, s1)
+    assert same_l and same_n and same_c, what
+    for i, want in enumerate(ref.nbest(N)):
+        u = int(t.first[i])
+        h0, h1 = int(hoff[u]), int(hoff[u + 1])
+        assert h1 - h0 == len(want), (what, i, h1 - h0, len(want))
+        for r, (wl, wc) in enumerate(want):
+            assert np.float32(cost[h0 + r]).tobytes() == np.float32(wc).tobytes(), (what, i, r, cost[h0 + r], wc)
+            assert tuple(int(x) for x in labs[h0 + r]) == wl, (what, i, r)
+    return n, s1[2] - s0[2]
 
 
 def check_transcript(what, t, ref, eng, b, transcripts, prec, chunks=1):
@@ -417,6 +451,21 @@ def test_transcript_cells_past_4_gib(refs):
         b.close(); eng.close()
 
 
+def test_nbest_back_pointers_past_4_gib(refs, monkeypatch):
+    """L = 48, D = 2, N = 64, 1500 utterances, 371,840 frames: bp_b and bp_e, [nfr][48][64] 32-bit words each, are 4.57e9 bytes
+    (1.06 x 2^32) apiece in one chunk; the back pointers of the last utterances sit past 2^32 bytes from the chunk's first."""
+    monkeypatch.setenv("SCRF_FAST_DECODE", "0")
+    ref, t = tiled_of(refs, "nbest")
+    N = bb.NBEST_N["nbest"]
+    print("nbest: bp_b = bp_e = %d bytes (%.3f x 2^32)" % (bb.array_bytes("nbest")["bp"], bb.array_bytes("nbest")["bp"] / bb.TWO32))
+    require_memory("nbest", bb.need_bytes("nbest"))
+    eng = t.engine(EXACT, ONE_CHUNK); b = t.batch(eng, with_labels=False)
+    try:
+        check_nbest("nbest", t, ref, eng, b, N, chunks=1)
+    finally:
+        b.close(); eng.close()
+
+
 # ---- axis B: more utterances than the chunk caps ----------------------------------------------------------------------
 def many_of(refs, name):
     ref = refs("many_" + name)
@@ -440,6 +489,7 @@ def test_70000_utterances_decode_outputs(name, refs, monkeypatch):
         try:
             what = "70000 %s (SCRF_FAST_DECODE=%s)" % (name, fast_decode)
             labs, _ = check_viterbi(what, t, ref, eng, b, chunks=2)
+            check_nbest(what, t, ref, eng, b, 3, chunks=2)     # 65,535 * 3 scan entries in the larger chunk
             if fast_decode == "1":
                 continue
             check_align(what, t, ref, eng, b, labs, chunks=2)
