@@ -1037,6 +1037,14 @@ struct LzWin {
     for (int j = MO; j >= 1; j--) v[j] = v[j - 1];
     v[0] = 0.0;
   }
+  // retire() in two halves for a walk past frame DMAX (t >= MO holds): the caller stores done() to frame t - MO with
+  // the frame's other stores, then slides
+  __device__ __forceinline__ double done() const { return v[MO]; }
+  __device__ __forceinline__ void slide() {
+#pragma unroll
+    for (int j = MO; j >= 1; j--) v[j] = v[j - 1];
+    v[0] = 0.0;
+  }
   // after the last frame T-1 (already slid): v[j] holds frame T - j, j = 1 .. MO
   __device__ __forceinline__ void flush(double* Zk, int T, size_t zstride) {
 #pragma unroll
@@ -1542,6 +1550,51 @@ void launch_ztf(hipStream_t st, const double* Zm, uint32_t n_out, const float* F
 // utterances is a handful of wavefronts whose frame step is bare load latency (BASELINE config 3, 256 utterances: one
 // wavefront per CU, 4 us per frame).  A segment warms its ring of alpha-plus-trans vectors from the stored ones; the
 // per-frame sums of frames near a segment boundary get windows from both sides and are ADDED into the zeroed Z (LzWin).
+// PZ_STEADY: 1 = the frames past D - 1 of a one-piece walk with D == DMAX <= 25 take the branch-free step with its small
+// inputs requested ahead of the rows (same results, bit for bit); 0 = the general loop serves every frame (the A/B
+// build, like FW_SCAN)
+#ifndef PZ_STEADY
+#define PZ_STEADY 1
+#endif
+#ifndef PZ_G
+#define PZ_G 5   // rows per address group of the steady-state step
+#endif
+#ifndef PZ_B
+#define PZ_B 5   // ring reads per batch
+#endif
+// exp(x) by the device library's own steps (ocml's double-precision exp: argument reduction by ln 2 in two parts, the
+// degree-11 polynomial, ldexp, the two range checks; the same operations on the same constants, so the same bits), written
+// out so that the polynomial's constants are scalar operands.  Inside exp() they are vector-register constants, which the
+// compiler hoists out of the frame loop and, the loop's register file being full, reloads from scratch in every frame.
+__device__ __forceinline__ double pz_sconst(double k) {
+  asm volatile("" : "+s"(k));
+  return k;
+}
+__device__ __forceinline__ double pz_exp(double x) {
+  const double dn = __builtin_rint(x * 0x1.71547652b82fep+0);
+  double t = __builtin_fma(-dn, 0x1.62e42fefa39efp-1, x);
+  t = __builtin_fma(-dn, 0x1.abc9e3b39803fp-56, t);
+  double p = __builtin_fma(t, 0x1.ade156a5dcb37p-26, pz_sconst(0x1.28af3fca7ab0cp-22));
+  p = __builtin_fma(t, p, pz_sconst(0x1.71dee623fde64p-19));
+  p = __builtin_fma(t, p, pz_sconst(0x1.a01997c89e6b0p-16));
+  p = __builtin_fma(t, p, pz_sconst(0x1.a01a014761f6ep-13));
+  p = __builtin_fma(t, p, pz_sconst(0x1.6c16c1852b7b0p-10));
+  p = __builtin_fma(t, p, pz_sconst(0x1.1111111122322p-7));
+  p = __builtin_fma(t, p, pz_sconst(0x1.55555555502a1p-5));
+  p = __builtin_fma(t, p, pz_sconst(0x1.5555555555511p-3));
+  p = __builtin_fma(t, p, pz_sconst(0x1.000000000000bp-1));
+  p = __builtin_fma(t, p, 1.0);
+  p = __builtin_fma(t, p, 1.0);
+  double z = ldexp(p, (int)dn);
+  z = x > 1024.0 ? INFINITY : z;
+  z = x < -1075.0 ? 0.0 : z;
+  return z;
+}
+// wave-uniform base plus a 32-bit byte offset per lane: the form a global access takes with its base in SGPRs
+template <class P>
+__device__ __forceinline__ P* pz_at(P* base, uint32_t byte_off) {
+  return (P*)((const char*)base + byte_off);
+}
 template <int DMAX, int LA, int RW, int SPLIT>
 __global__ __launch_bounds__(64, 2) void k_post_z(ScrfLayout lay, ScrfBatchView bv, uint32_t u0,
                                                   const uint32_t* __restrict__ next_lab,
@@ -1588,8 +1641,12 @@ __global__ __launch_bounds__(64, 2) void k_post_z(ScrfLayout lay, ScrfBatchView 
     for (int j = 1; j <= (int)D && j <= fa; j++)
       if (rw_ok) pring[((fa - j) % (int)D) * RW + lane] = o_.p[(f_base + fa - j) * L + oc];
   }
+  // frames past D - 1 of a one-piece walk with D == DMAX take the steady-state step below (DMAX <= 25: the D = 32 and
+  // D = 40 forms spill hundreds of registers either way and were not measured with it; they keep the one loop)
+  const bool steady = PZ_STEADY && !SPLIT && DMAX <= 25 && D == (uint32_t)DMAX && T > DMAX;
+  const int fe = steady ? DMAX : fb;
 #pragma unroll 1
-  for (int t = fa; t < fb; t++) {
+  for (int t = fa; t < fe; t++) {
     const uint32_t nd = scrf_node_max_dur((uint32_t)t, D), np = scrf_num_prev((uint32_t)t, D);
     const uint64_t row0 = scrf_seg_base((uint32_t)t, D);
     double r[DMAX];
@@ -1693,6 +1750,184 @@ __global__ __launch_bounds__(64, 2) void k_post_z(ScrfLayout lay, ScrfBatchView 
       numer_f[f_base + t] = nodeLi;
     }
   }
+#if PZ_STEADY
+  if (!SPLIT && steady) {
+    // Steady state, frames D .. T - 1: every duration exists and has a predecessor (nd = np = D = DMAX), so the step has
+    // no per-duration branch or select, ring slots are wave-uniform scalars, rows and sums go through wave-uniform
+    // pointers that advance by a frame, the scale factors stay in a register (lane d0 holds duration d0's) and reach the
+    // multiply as scalar operands, and the stores of a frame sit in one region of the exec mask each.  The frame's small
+    // inputs (the log-scales, the labels, the true score, b) are requested AHEAD of the rows: loads return in the order
+    // they were issued, so the scale factors' exp and the label arithmetic run while the rows are in flight, and the rows
+    // are the one memory round trip a frame waits for.  (Requesting them a frame ahead was built first: it keeps a dozen
+    // registers live across the whole step, which this loop does not have -- profiles/EXPERIMENTS.md.)
+    // The arithmetic is the loop's above, operation for operation.
+    const bool has_lab = bv.labels != nullptr;
+    const uint32_t LD = L * DMAX;
+    const uint64_t row_d = scrf_seg_base(DMAX, DMAX);
+    double* Rt = ES + (s_base + row_d) * L;                 // rows of frame t
+    const double* smt = smu + row_d;
+    double* Zb = Z + f_base * (uint64_t)zs;
+    double* zq0 = Zb + (size_t)(DMAX - w0.MO) * zs;         // where each window's finished frame goes
+    double* zq1 = Zb + (size_t)(DMAX - w1.MO) * zs + L;
+    double* zq2 = Zb + (size_t)(DMAX - w2.MO) * zs + 2 * (size_t)L;
+    double* zq3 = Zb + (size_t)(DMAX - w3.MO) * zs + 3 * (size_t)L;
+    double* zq4 = Zb + (size_t)(DMAX - w4.MO) * zs + 4 * (size_t)L;
+    double* zq5 = Zb + zs + 5 * (size_t)L;                  // Z_avg of frame t + 1 - D
+    struct In { double gp, sm, gb, st; uint32_t lab, nl; };
+    auto request = [&](int tt, const double* sm_tt, uint32_t ln) {
+      In q;
+      const uint32_t dl = ln < (uint32_t)DMAX ? ln : 0;   // the duration whose scale factor this lane forms
+      // wave-uniform bases, per-lane byte offsets; the zero offset makes the uniform loads vector loads (a scalar one is
+      // waited for where it is issued)
+      uint32_t z0 = 0, d8 = dl * 8;
+      asm volatile("" : "+v"(z0));
+      asm volatile("" : "+v"(d8));
+      const uint64_t f = f_base + tt;
+      q.gp = *pz_at(o_.gp + f - DMAX, (uint32_t)(DMAX - 1) * 8 - d8);   // gp[f - 1 - dl]
+      q.sm = *pz_at(sm_tt, d8);
+      q.gb = *pz_at(o_.gb + f, z0);
+      q.lab = q.nl = SCRF_LAB_BAD;
+      q.st = 0.0;
+      if (has_lab) {
+        q.lab = *pz_at(bv.labels + gf0 + tt, z0);
+        q.nl = *pz_at(next_lab + gf0 + tt, z0);
+        q.st = *pz_at(s_true + f, z0);
+      }
+      return q;
+    };
+    // fs: lane d0 holds the scale factor of duration d0; the rest is wave-uniform and kept in scalars
+    struct Cur { double fs, st; uint32_t lab, nl, al, ld; };
+    auto settle = [&](const In& q, bool& xbad, uint32_t ln) {
+      Cur c;
+      const double x = (ln < (uint32_t)DMAX) ? q.gp + q.sm + q.gb - Zx : -INFINITY;
+      xbad = ln < (uint32_t)DMAX && x >= LN_MAX;
+      c.fs = pz_exp(x);
+      c.st = __hiloint2double(__builtin_amdgcn_readfirstlane(__double2hiint(q.st)), __builtin_amdgcn_readfirstlane(__double2loint(q.st)));
+      c.lab = __builtin_amdgcn_readfirstlane(q.lab);
+      c.nl = __builtin_amdgcn_readfirstlane(q.nl);
+      c.al = c.ld = SCRF_LAB_BAD;
+      if (c.lab != SCRF_LAB_BAD) {
+        c.al = c.lab % L;
+        c.ld = c.lab / L + 1;
+      }
+      return c;
+    };
+#pragma unroll 1
+    for (int t = DMAX; t < T; t++) {
+      const bool more = t + 1 < T;
+      double r[DMAX];
+      // What depends on the lane alone is formed again in every frame from the lane index: held across the loop these
+      // values are the first the register allocator sends to scratch, and a reload waits for the frame's stores.  The
+      // offsets' zero extension then also stands in the block of the access, which selects base-in-SGPRs addressing.
+      uint32_t ln = lane;
+      asm volatile("" : "+v"(ln));
+      const uint32_t ol = blockIdx.y * 64 + ln;                  // o
+      const uint32_t o8 = (ol < L ? ol : L - 1) * 8;             // oc * 8
+      // a frame's rows: row groups with wave-uniform bases, the rows of a group at per-lane offsets
+      uint32_t vo[PZ_G];
+#pragma unroll
+      for (int j = 0; j < PZ_G; j++) vo[j] = o8 + (uint32_t)j * L * 8;
+      const In q = request(t, smt, ln);
+      const double b = *pz_at(o_.b + (f_base + t) * L, o8);
+#pragma unroll
+      for (int d0 = 0; d0 < DMAX; d0++) r[d0] = __builtin_nontemporal_load(pz_at(Rt + (size_t)(d0 / PZ_G * PZ_G) * L, vo[d0 % PZ_G]));
+      bool xbad;
+      const Cur c = settle(q, xbad, ln);   // under the rows' flight
+      if (xbad) err = SCRF_ERR_NUMERIC;
+      if (c.lab != SCRF_LAB_BAD && c.lab >= LD) err = SCRF_ERR_BAD_LABEL;
+      const bool hit = ol == c.al;
+      double gs = 0.0;
+#pragma unroll
+      for (int g0 = 0; g0 < DMAX; g0 += PZ_B) {   // the ring reads of a batch go out together
+        double pv[PZ_B];
+#pragma unroll
+        for (int j = 0; j < PZ_B && g0 + j < DMAX; j++) {
+          int ps = slot - 1 - (g0 + j);            // ring slot of p[t-1-d0]
+          ps += (ps < 0) ? DMAX : 0;
+          pv[j] = pring[ps * RW + rl];
+        }
+#pragma unroll
+        for (int j = 0; j < PZ_B && g0 + j < DMAX; j++) {
+          const int d0 = g0 + j;
+          const double g = (pv[j] * r[d0]) * (b * rdlane(c.fs, d0));
+          const double y = (hit && (uint32_t)d0 + 1 == c.ld) ? 1.0 : 0.0;
+          r[d0] = y - g;
+          gs += g;
+        }
+      }
+      if (act) {
+        uint32_t so[PZ_G];   // the offsets again: the zero extension has to stand in the block of the access
+#pragma unroll
+        for (int j = 0; j < PZ_G; j++) { so[j] = vo[j]; asm volatile("" : "+v"(so[j])); }
+#pragma unroll
+        for (int d0 = 0; d0 < DMAX; d0++) __builtin_nontemporal_store(r[d0], pz_at(Rt + (size_t)(d0 / PZ_G * PZ_G) * L, so[d0 % PZ_G]));
+      }
+      // Requested here, with the ring values' registers free again, what the end of the step needs: the vector for the
+      // ring (p has T - 1 rows: the last frame, which hands none on, reads one row back and drops it) and the numerator's
+      // transition term from the label pair (M's first element where there is none).  They arrive under the sums below.
+      uint32_t po = o8;
+      asm volatile("" : "+v"(po));
+      const double pl = *pz_at(o_.p + (f_base + t - (more ? 0 : 1)) * L, po);
+      double mv = 0.0;
+      if (has_lab) {
+        const bool ok = more && c.lab < LD && c.nl < LD;   // SCRF_LAB_BAD is above every L * D
+        const size_t mi = (m_per_frame ? (f_base + t + 1) * (size_t)L * L : 0) + (size_t)c.al * L + c.nl % L;
+        uint32_t z0 = 0;
+        asm volatile("" : "+v"(z0));
+        mv = *pz_at(M + (ok ? mi : 0), z0);
+      }
+      {
+        const double m = wave_sum_f64_dpp(act ? gs : 0.0);
+        if (lane == 0) {
+          if (gridDim.y == 1) mass_s[f_base + t] = m;
+          else atomicAdd(&mass_s[f_base + t], m);
+        }
+      }
+      double zv = 0.0;
+      if (LA && rw_ok) {
+        double usum = 0.0;
+#pragma unroll
+        for (int d0 = DMAX - 1; d0 >= 0; d0--) {
+          usum = fma(r[d0], 1.0 / (double)(d0 + 1), usum);
+          int zsl = slot - d0;
+          zsl += (zsl < 0) ? DMAX : 0;
+          __hip_atomic_fetch_add(&zring[zsl * RW + lane], usum, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
+        }
+        const int zf = slot + 1 == DMAX ? 0 : slot + 1;
+        zv = zring[zf * RW + lane];
+        zring[zf * RW + lane] = 0.0;
+      }
+      w0.add(r); w1.add(r); w2.add(r); w3.add(r); w4.add(r);
+      if (act) {
+        uint32_t so = o8;
+        asm volatile("" : "+v"(so));
+        __builtin_nontemporal_store(w0.done(), pz_at(zq0, so));
+        __builtin_nontemporal_store(w1.done(), pz_at(zq1, so));
+        __builtin_nontemporal_store(w2.done(), pz_at(zq2, so));
+        __builtin_nontemporal_store(w3.done(), pz_at(zq3, so));
+        __builtin_nontemporal_store(w4.done(), pz_at(zq4, so));
+        if (LA) __builtin_nontemporal_store(zv, pz_at(zq5, so));
+      }
+      w0.slide(); w1.slide(); w2.slide(); w3.slide(); w4.slide();
+      if (rw_ok) pring[slot * RW + lane] = more ? pl : 0.0;
+      slot = (slot + 1 == DMAX) ? 0 : slot + 1;
+      if (lane == 0 && blockIdx.y == 0) {
+        double nodeLi = 0.0;
+        if (c.lab != SCRF_LAB_BAD && err == 0) {
+          nodeLi += c.st;   // ld <= D: every duration exists
+          if (more && c.nl != SCRF_LAB_BAD) {
+            if (c.nl >= LD) err = SCRF_ERR_BAD_LABEL;
+            else nodeLi += mv;
+          }
+        }
+        numer_f[f_base + t] = nodeLi;
+      }
+      Rt += (size_t)DMAX * L;
+      smt += DMAX;
+      zq0 += zs; zq1 += zs; zq2 += zs; zq3 += zs; zq4 += zs; zq5 += zs;
+    }
+  }
+#endif
   if (act && SPLIT) {
     w0.flush_seg(Zu, fb, zs, own_lo, own_hi);
     w1.flush_seg(Zu + L, fb, zs, own_lo, own_hi);
