@@ -49,7 +49,9 @@ __device__ inline uint32_t align_backtrace(const uint16_t* __restrict__ bp, cons
 // k_align_wave: lane = transcript position.  q_k, q_{k-1} and (single M) the lane's two transition weights stay in
 // registers; end(t-1, .) and the D-deep ring of boundary values sit in LDS, the ring private to the lane's column -- the one
 // cross-lane read is end(t-1, k-1).  No workgroup barrier.  The frame's D segment weights (column q_k of D consecutive rows)
-// are requested a frame ahead, as k_viterbi_fast does.
+// are requested a frame ahead, as k_viterbi_fast does.  It reads the weights through the scrf_w_* functions directly, not
+// through ScrfArcView as k_align_group does: with the view its D <= 40 variant measured 0.8 % slower at 4096 utterances x 300
+// frames (profiles/EXPERIMENTS.md), so its body stays as it was.
 // ------------------------------------------------------------------------------------------
 #define AL_WAVES 4
 template <int DMAX>
@@ -184,15 +186,14 @@ __global__ __launch_bounds__(64 * AL_WAVES) void k_align_wave(ScrfLayout lay, Sc
 
 int align_wave_supported(const ScrfLayout& lay) { return lay.D <= 40; }
 
-void launch_align_wave(hipStream_t st, const ScrfLayout& lay, ScrfBatchView bv, uint32_t u0, uint32_t n_utts, const double* S,
-                       const float* Wn, const double* M, int m_per_frame, int frame_model, const ScrfAlignArgs& aa,
-                       uint32_t* out_labels, uint32_t* out_n, float* out_cost) {
+void launch_align_wave(hipStream_t st, const ScrfLayout& lay, ScrfBatchView bv, uint32_t u0, uint32_t n_utts, const ScrfArcSrc& src,
+                       const ScrfAlignArgs& aa, uint32_t* out_labels, uint32_t* out_n, float* out_cost) {
   if (n_utts == 0) return;
   const size_t sm = sizeof(float) * AL_WAVES * (64 + (size_t)lay.D * 64);   // D <= 40: at most 41 KiB
   const dim3 grid((n_utts + AL_WAVES - 1) / AL_WAVES), block(64 * AL_WAVES);
 #define AL_GO(N)                                                                                                               \
-  hipLaunchKernelGGL((k_align_wave<N>), grid, block, sm, st, lay, bv, u0, n_utts, S, Wn, M, m_per_frame, frame_model, aa, \
-                     out_labels, out_n, out_cost)
+  hipLaunchKernelGGL((k_align_wave<N>), grid, block, sm, st, lay, bv, u0, n_utts, src.S, src.Wn, src.M, src.m_per_frame,       \
+                     src.frame_model, aa, out_labels, out_n, out_cost)
   if (lay.D <= 4) AL_GO(4);
   else if (lay.D <= 12) AL_GO(12);
   else AL_GO(40);
@@ -211,18 +212,14 @@ __global__ void k_align_group(ScrfLayout lay, ScrfBatchView bv, uint32_t u0, con
   const int L = lay.L, D = lay.D;
   const int tid = threadIdx.x, NT = blockDim.x;
   const uint32_t u = u0 + blockIdx.x;
-  const int T = (int)bv.T[u];
+  const ScrfArcView v(ScrfArcSrc{S, Wn, M, m_per_frame, frame_model}, lay, bv, u0, u);
+  const int T = (int)v.T;
   const uint64_t K64 = aa.phone_off[u + 1] - aa.phone_off[u];
   if (!scrf_align_feasible((uint32_t)T, K64, (uint32_t)D, aa.mode)) {   // uniform over the workgroup
     if (tid == 0) { out_n[u] = 0; out_cost[u] = INFINITY; }
     return;
   }
   const int K = (int)K64, mode = aa.mode;   // K <= T
-  const uint64_t f_base = bv.frame_off[u] - bv.frame_off[u0];
-  const uint64_t s_base = bv.seg_off[u] - bv.seg_off[u0];
-  const double* Su = S ? S + s_base * L : nullptr;
-  const float* Wu = Wn ? Wn + s_base * L : nullptr;
-  const size_t LL = (size_t)L * L;
   const uint32_t* ph = aa.phones + aa.phone_off[u];
   uint16_t* bp = aa.bp + (aa.bp_off[u] - aa.bp_off[u0]);
   float* ring = agsm + 2 * (size_t)K;   // [D][K]
@@ -230,7 +227,7 @@ __global__ void k_align_group(ScrfLayout lay, ScrfBatchView bv, uint32_t u0, con
   for (int t = 0; t < T; t++) {
     const float* e_prev = agsm + (size_t)((t + 1) & 1) * K;
     float* e_cur = agsm + (size_t)(t & 1) * K;
-    const double* Mt = M + (m_per_frame ? (f_base + t) * LL : 0);
+    const double* Mt = v.Mt(t);
     const uint64_t base = scrf_seg_base(t, D);
     for (int k = tid; k < K; k += NT) {
       const bool live = align_live(t, k, T, K, D, mode);
@@ -240,14 +237,14 @@ __global__ void k_align_group(ScrfLayout lay, ScrfBatchView bv, uint32_t u0, con
         if (live) {
           const uint32_t q = ph[k];
           if (t == 0) {
-            best = 0.0f + scrf_w_segment(Su, 0, 1, L, q);
+            best = 0.0f + v.start(q);
           } else {
             if (k >= 1) {
-              const float c = e_prev[k - 1] + scrf_w_frame(Mt, Su, t, L, ph[k - 1], q);
+              const float c = e_prev[k - 1] + v.frame(Mt, t, ph[k - 1], q);
               if (c < best) best = c;
             }
             if (mode == SCRF_ALIGN_RUNS) {
-              const float c = e_prev[k] + scrf_w_frame(Mt, Su, t, L, q, q);
+              const float c = e_prev[k] + v.frame(Mt, t, q, q);
               if (c < best) { best = c; flag = AL_STAY; }
             }
           }
@@ -259,11 +256,11 @@ __global__ void k_align_group(ScrfLayout lay, ScrfBatchView bv, uint32_t u0, con
           float b = INFINITY;
           if (align_live_b(t, k, T, K, D, mode)) {
             if (k >= 1) {
-              const float c = e_prev[k - 1] + scrf_w_boundary(Mt, L, ph[k - 1], q);
+              const float c = e_prev[k - 1] + v.boundary(Mt, ph[k - 1], q);
               if (c < b) b = c;
             }
             if (mode == SCRF_ALIGN_RUNS) {
-              const float c = e_prev[k] + scrf_w_boundary(Mt, L, q, q);
+              const float c = e_prev[k] + v.boundary(Mt, q, q);
               if (c < b) { b = c; flag = AL_STAY; }
             }
           }
@@ -271,7 +268,7 @@ __global__ void k_align_group(ScrfLayout lay, ScrfBatchView bv, uint32_t u0, con
         }
         if (live) {
           if (k == 0 && t < D) {   // from the start state: duration t+1
-            const float c = 0.0f + (Wu ? Wu[(base + t) * L + q] : scrf_w_segment(Su, base, t + 1, L, q));
+            const float c = 0.0f + v.segment(base, t + 1, q);
             if (c < best) { best = c; arg = t + 1; }
           }
           // tp ascending = d descending from min(t, D), eight weights requested at a time so that their loads overlap
@@ -280,7 +277,7 @@ __global__ void k_align_group(ScrfLayout lay, ScrfBatchView bv, uint32_t u0, con
 #pragma unroll
             for (int j = 0; j < 8; j++) {
               const int d = d0 - j > 1 ? d0 - j : 1;
-              w[j] = Wu ? Wu[(base + d - 1) * L + q] : scrf_w_segment(Su, base, d, L, q);
+              w[j] = v.segment(base, d, q);
             }
 #pragma unroll
             for (int j = 0; j < 8; j++) {
@@ -317,13 +314,12 @@ __global__ void k_align_group(ScrfLayout lay, ScrfBatchView bv, uint32_t u0, con
 size_t align_group_smem_bytes(const ScrfLayout& lay, uint64_t K) { return sizeof(float) * ((size_t)lay.D + 2) * K; }
 
 void launch_align_group(hipStream_t st, const ScrfLayout& lay, ScrfBatchView bv, uint32_t u0, uint32_t n_utts, uint32_t k_max,
-                        const double* S, const float* Wn, const double* M, int m_per_frame, int frame_model,
-                        const ScrfAlignArgs& aa, uint32_t* out_labels, uint32_t* out_n, float* out_cost) {
+                        const ScrfArcSrc& src, const ScrfAlignArgs& aa, uint32_t* out_labels, uint32_t* out_n, float* out_cost) {
   if (n_utts == 0) return;
   int NT = ((int)(k_max ? k_max : 1) + 63) / 64 * 64;
   if (NT > 1024) NT = 1024;
   const size_t sm = align_group_smem_bytes(lay, k_max ? k_max : 1);   // the chunk's longest transcript
   hipFuncSetAttribute((const void*)k_align_group, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sm);
-  hipLaunchKernelGGL(k_align_group, dim3(n_utts), dim3(NT), sm, st, lay, bv, u0, S, Wn, M, m_per_frame, frame_model, aa,
-                     out_labels, out_n, out_cost);
+  hipLaunchKernelGGL(k_align_group, dim3(n_utts), dim3(NT), sm, st, lay, bv, u0, src.S, src.Wn, src.M, src.m_per_frame, src.frame_model,
+                     aa, out_labels, out_n, out_cost);
 }

@@ -9,6 +9,7 @@
 #include "scrf_abi.h"
 
 #define SCRF_WAVE 64
+#define SCRF_LDS_BYTES (160 * 1024)   // LDS of a workgroup
 
 // Lambda layout and feature ranges, closed form of CRF_StdFeatureMap::recalc /
 // computeStateFeatureIdx / computeTransFeatureIdx for numStates == 1

@@ -1119,6 +1119,14 @@ struct ChunkBufs {
   bool lamT_ready = false;   // sparse maps: h->d_lamT already re-laid for this call (scrf_fb_batch: once, before the lanes fork)
 };
 
+// The arcs of a scored chunk for the lattice searches (scrf_arcw.h).  The one place that knows which weights a search reads:
+// a fast-decode chunk carries the formed float weights cb.Wn and no scores; the frame model never has Wn.
+static ScrfArcSrc arc_src(scrf_handle h, const ChunkBufs& cb, bool fast = false) {
+  const int frame_model = h->cfg.model_type == SCRF_STDFRAME;
+  const bool formed = fast && !frame_model;
+  return ScrfArcSrc{formed ? nullptr : cb.S, formed ? cb.Wn : nullptr, cb.M, cb.m_per_frame, frame_model};
+}
+
 // ponly (scrf_posteriors_batch): the recursion of the training path without anything that needs labels or feeds the
 // gradient -- the linear-domain vectors (or alpha_dur / beta) and the per-frame state mass, no count buffers
 struct Need {
@@ -1653,7 +1661,7 @@ static int queue_status(scrf_handle h, scrf_batch b, hipStream_t st);
 // STDSEG_NO_DUR: one transition matrix per window, its own workgroup recursion
 static int dp_segtrans(scrf_handle h, scrf_batch b, uint32_t u0, uint32_t u1, ChunkBufs& cb, bool post, uint32_t* nl) {
   const ScrfLayout& l = h->lay;
-  if (fb_segtrans_smem_bytes(l, fb_block_threads(l)) > 160 * 1024)
+  if (fb_segtrans_smem_bytes(l, fb_block_threads(l)) > SCRF_LDS_BYTES)
     return fail(h, SCRF_ERR_INVALID, "labels x maximum duration = %u x %u is too large for the stdseg_no_dur recursion "
                 "(its three [D][L] rings must fit 160 KB of LDS)", l.L, l.D);
   KT_RUN("k_fb_segtrans", cb.st, launch_fb_segtrans(cb.st, h->kn, l, b->view(), u0, u1 - u0, b->d_prev_lab, cb.S, cb.M, cb.AD, cb.alpha, cb.beta,
@@ -1666,7 +1674,7 @@ static int dp_segtrans(scrf_handle h, scrf_batch b, uint32_t u0, uint32_t u1, Ch
 static int dp_group(scrf_handle h, scrf_batch b, uint32_t u0, uint32_t u1, ChunkBufs& cb, bool post, uint32_t* nl) {
   const ScrfLayout& l = h->lay;
   const uint32_t nutt = u1 - u0;
-  if (fb_smem_bytes(l, fb_block_threads(l)) > 160 * 1024)
+  if (fb_smem_bytes(l, fb_block_threads(l)) > SCRF_LDS_BYTES)
     return fail(h, SCRF_ERR_INVALID, "labels x maximum duration = %u x %u is too large for the workgroup-per-utterance recursion "
                 "(its two [D][L] rings must fit 160 KB of LDS; the wavefront kernels cover L <= 256 with D <= 40)", l.L, l.D);
   if (post && cb.xi_acc) HIPCHK(h, hipMemsetAsync(cb.xi_acc, 0, sizeof(double) * nutt * l.L * l.L, cb.st));
@@ -2876,7 +2884,7 @@ extern "C" int scrf_lattice_arcs(scrf_handle h, scrf_batch b, uint32_t u, int no
   DevArray<scrf_arc> d_arcs;
   HIPCHK(h, d_arcs.reserve(na));
   if (segtrans(h)) launch_arcs_segtrans(h->stream, l, T, cb.S, cb.M, final_w, d_arcs);
-  else launch_arcs(h->stream, l, T, frame_model, cb.S, cb.M, cb.m_per_frame, final_w, d_arcs);
+  else launch_arcs(h->stream, l, T, arc_src(h, cb), final_w, d_arcs);
   std::vector<scrf_arc> dense;
   if (h->shadow) dense.resize(na);
   hipError_t e = hipMemcpyAsync(h->shadow ? dense.data() : arcs, d_arcs, sizeof(scrf_arc) * na, hipMemcpyDeviceToHost, h->stream);
@@ -2919,10 +2927,9 @@ extern "C" int scrf_lattice_prune_batch(scrf_handle h, scrf_batch b, double beam
   if (!(beam > 0.0) || !std::isfinite(beam))
     return fail(h, SCRF_ERR_INVALID, "scrf_lattice_prune_batch: the beam must be finite and > 0 (got %g)", beam);
   const ScrfLayout& l = h->lay;
-  if (lat_sweep_smem_bytes(l) > 160 * 1024)
+  if (lat_sweep_smem_bytes(l) > SCRF_LDS_BYTES)
     return fail(h, SCRF_ERR_INVALID, "scrf_lattice_prune_batch: %u labels x maximum duration %u do not fit the sweep kernel's LDS window", l.L, l.D);
   HIPCHK(h, hipSetDevice(h->device));
-  const bool frame_model = h->cfg.model_type == SCRF_STDFRAME;
   const uint32_t U = b->U;
   const size_t by_best = pad256(sizeof(double) * U), need_meta = by_best + pad256(sizeof(uint64_t) * (U + 1));
   RCCHK(reserve_drained(h, h->lp.meta, need_meta));
@@ -2942,15 +2949,16 @@ extern "C" int scrf_lattice_prune_batch(scrf_handle h, scrf_batch b, double beam
     const uint64_t nfr = b->frame_off[u1] - b->frame_off[u0], n_nodes = nfr + nutt;
     const uint32_t t_max = longest_utt(b, u0, u1);
     cb.lat.best = d_best;
-    KT_RUN("k_lat_sweep", cb.st, launch_lat_sweep(cb.st, l, bv, u0, nutt, cb.S, cb.M, cb.m_per_frame, frame_model, cb.lat));
-    KT_RUN("k_lat_count", cb.st, launch_lat_count(cb.st, l, bv, u0, nutt, t_max, cb.S, cb.M, cb.m_per_frame, frame_model, cb.lat, beam, cb.lat_counts));
+    const ScrfArcSrc src = arc_src(h, cb);
+    KT_RUN("k_lat_sweep", cb.st, launch_lat_sweep(cb.st, l, bv, u0, nutt, src, cb.lat));
+    KT_RUN("k_lat_count", cb.st, launch_lat_count(cb.st, l, bv, u0, nutt, t_max, src, cb.lat, beam, cb.lat_counts));
     KT_RUN("k_lat_scan", cb.st, launch_lat_scan(cb.st, bv, u0, nutt, cb.lat_counts, n_nodes, cb.lat_node_off, total, d_uoff));
     uint64_t kept = 0;   // the chunk's arcs must have room before they are written
     HIPCHK(h, hipMemcpyAsync(&kept, cb.lat_node_off + n_nodes, sizeof(uint64_t), hipMemcpyDeviceToHost, cb.st));
     HIPCHK(h, hipStreamSynchronize(cb.st));
     HIPCHK(h, h->lp.arcs.reserve_keep(total + kept, total, cb.st));   // the arcs of the chunks done move with it
-    KT_RUN("k_lat_emit", cb.st, launch_lat_emit(cb.st, l, bv, u0, nutt, t_max, cb.S, cb.M, cb.m_per_frame, frame_model, cb.lat, beam, cb.lat_node_off,
-                                                total, h->lp.arcs.cap(), h->lp.arcs));
+    KT_RUN("k_lat_emit", cb.st, launch_lat_emit(cb.st, l, bv, u0, nutt, t_max, src, cb.lat, beam, cb.lat_node_off, total, h->lp.arcs.cap(),
+                                                h->lp.arcs));
     HIPCHK(h, hipGetLastError());
     total += kept;
     u0 = u1;
@@ -3069,7 +3077,6 @@ extern "C" int scrf_viterbi_batch(scrf_handle h, scrf_batch b, uint32_t* seg_lab
   if (!h || !b || !seg_labels || !lab_off) return SCRF_ERR_INVALID;
   HIPCHK(h, hipSetDevice(h->device));
   const ScrfLayout& l = h->lay;
-  const bool frame_model = h->cfg.model_type == SCRF_STDFRAME;
   CallTimer call(h);
   HIPCHK(h, h->dec.reserve(b->frame_off[b->U], b->U));
   int rc = SCRF_OK;
@@ -3102,13 +3109,9 @@ extern "C" int scrf_viterbi_batch(scrf_handle h, scrf_batch b, uint32_t* seg_lab
   else
     rc = decode_chunks(h, b, Need::viterbi(), [&](const ChunkBufs& cb, uint32_t u0, uint32_t u1, bool fast) {
       if (fast && viterbi_fast_supported(l))
-        launch_viterbi_fast(h->stream, h->kn, l, b->view(), u0, u1 - u0, cb.Wn, cb.M, cb.bp_b, cb.bp_e, d_lab, d_n, d_cost);
-      else if (fast)
-        launch_viterbi(h->stream, l, b->view(), u0, u1 - u0, nullptr, cb.M, cb.m_per_frame, 0, cb.bp_b, cb.bp_e, d_lab, d_n,
-                       d_cost, cb.Wn);
+        launch_viterbi_fast(h->stream, h->kn, l, b->view(), u0, u1 - u0, arc_src(h, cb, fast), cb.bp_b, cb.bp_e, d_lab, d_n, d_cost);
       else if (segtrans(h)) launch_viterbi_segtrans(h->stream, l, b->view(), u0, u1 - u0, cb.S, cb.M, cb.bp_b, cb.bp_e, d_lab, d_n, d_cost);
-      else launch_viterbi(h->stream, l, b->view(), u0, u1 - u0, cb.S, cb.M, cb.m_per_frame, frame_model, cb.bp_b, cb.bp_e,
-                          d_lab, d_n, d_cost);
+      else launch_viterbi(h->stream, l, b->view(), u0, u1 - u0, arc_src(h, cb, fast), cb.bp_b, cb.bp_e, d_lab, d_n, d_cost);
     });
   if (rc != SCRF_OK) return rc;
   return decode_result_fetch(h, b, "scrf_viterbi_batch", call, seg_labels, max_labels, lab_off, best_cost);
@@ -3127,6 +3130,43 @@ static int upload_transcripts(scrf_handle h, uint32_t U, const uint32_t* phones,
   return SCRF_OK;
 }
 
+// The checks of a call's transcripts, one pass in a fixed order (scrf_align_batch, scrf_transcript_batch), and cell_off [U + 1]:
+// the T x K cells before each utterance, none for a transcript that no path realises (the chunk planner sizes a chunk with
+// them).  no_repeats: with SCRF_ALIGN_RUNS equal neighbours are refused.  lds(K): the bytes of LDS the caller's workgroup
+// kernel needs for a transcript of K phones, `cell_bytes` a cell, or 0 where another kernel serves it; a workgroup has
+// SCRF_LDS_BYTES less `lds_less`.  An offset past phone_off[U] counts as a decrease: no phone is read outside the array.
+template <class Lds>
+static int check_transcripts(scrf_handle h, scrf_batch b, const char* fn, const uint32_t* phones, const uint64_t* phone_off, int mode,
+                             bool no_repeats, int cell_bytes, int lds_less, Lds&& lds, std::vector<uint64_t>* cell_off) {
+  const ScrfLayout& l = h->lay;
+  const uint32_t U = b->U;
+  const uint64_t NP = phone_off[U];
+  if (phone_off[0] != 0 || (NP && !phones)) return fail(h, SCRF_ERR_INVALID, "%s: phone_off must start at 0 and phones must be given", fn);
+  char less[24] = "";
+  if (lds_less) snprintf(less, sizeof(less), " less %d", lds_less);
+  cell_off->assign(U + 1, 0);
+  for (uint32_t u = 0; u < U; u++) {
+    if (phone_off[u + 1] < phone_off[u] || phone_off[u + 1] > NP) return fail(h, SCRF_ERR_INVALID, "%s: phone_off decreases at utterance %u", fn, u);
+    const uint64_t K = phone_off[u + 1] - phone_off[u];
+    const uint32_t* ph = phones + phone_off[u];
+    for (uint64_t k = 0; k < K; k++) {
+      if (ph[k] >= l.L)
+        return fail(h, SCRF_ERR_INVALID, "%s: phone %u at position %llu of utterance %u's transcript (the model has %u)", fn, ph[k],
+                    (unsigned long long)k, u, l.L);
+      if (no_repeats && mode == SCRF_ALIGN_RUNS && k >= 1 && ph[k] == ph[k - 1])
+        return fail(h, SCRF_ERR_INVALID, "%s: utterance %u's transcript repeats phone %u at position %llu; with SCRF_ALIGN_RUNS equal "
+                    "neighbours make the sum count a path more than once: collapse them first", fn, u, ph[k], (unsigned long long)k);
+    }
+    const bool fits = scrf_align_feasible(b->T[u], K, l.D, mode);
+    const size_t need = fits ? lds(K) : 0;
+    if (need > (size_t)(SCRF_LDS_BYTES - lds_less))
+      return fail(h, SCRF_ERR_INVALID, "%s: utterance %u's transcript of %llu phones needs (%u + 2) x %llu x %d = %zu bytes of LDS, "
+                  "a workgroup has %d%s", fn, u, (unsigned long long)K, l.D, (unsigned long long)K, cell_bytes, need, SCRF_LDS_BYTES, less);
+    (*cell_off)[u + 1] = (*cell_off)[u] + (fits ? (uint64_t)b->T[u] * K : 0);
+  }
+  return SCRF_OK;
+}
+
 // ---------------------------------------------------------------------------------------------
 // batched forced alignment: scrf_viterbi_batch's chunk loop and score stage, a constrained search
 // ---------------------------------------------------------------------------------------------
@@ -3140,27 +3180,11 @@ extern "C" int scrf_align_batch(scrf_handle h, scrf_batch b, const uint32_t* pho
   if (l.D > 0x7fff)
     return fail(h, SCRF_ERR_INVALID, "scrf_align_batch: maximum duration %u does not fit the 15 duration bits of a back pointer (at most %u)", l.D, 0x7fffu);
   const uint32_t U = b->U;
-  const uint64_t NP = phone_off[U];
-  if (phone_off[0] != 0 || (NP && !phones)) return fail(h, SCRF_ERR_INVALID, "scrf_align_batch: phone_off must start at 0 and phones must be given");
-  // back-pointer cells before each utterance (the chunk planner sizes a chunk with them), the longest transcript the
-  // workgroup kernel may meet
+  // back-pointer cells before each utterance; the workgroup kernel takes the transcripts the wavefront kernel does not
   const bool wave_on = h->kn.align_wave && align_wave_supported(l);
-  h->tx.bp_off.assign(U + 1, 0);
-  for (uint32_t u = 0; u < U; u++) {
-    if (phone_off[u + 1] < phone_off[u]) return fail(h, SCRF_ERR_INVALID, "scrf_align_batch: phone_off decreases at utterance %u", u);
-    const uint64_t K = phone_off[u + 1] - phone_off[u];
-    for (uint64_t k = phone_off[u]; k < phone_off[u + 1]; k++)
-      if (phones[k] >= l.L)
-        return fail(h, SCRF_ERR_INVALID, "scrf_align_batch: phone %u at position %llu of utterance %u's transcript (the model has %u)",
-                    phones[k], (unsigned long long)(k - phone_off[u]), u, l.L);
-    const bool fits = scrf_align_feasible(b->T[u], K, l.D, mode);
-    if (fits && (K > 64 || !wave_on) && align_group_smem_bytes(l, K) > 160 * 1024)
-      return fail(h, SCRF_ERR_INVALID, "scrf_align_batch: utterance %u's transcript of %llu phones needs (%u + 2) x %llu x 4 = %zu bytes of LDS, "
-                  "a workgroup has %d", u, (unsigned long long)K, l.D, (unsigned long long)K, align_group_smem_bytes(l, K), 160 * 1024);
-    h->tx.bp_off[u + 1] = h->tx.bp_off[u] + (fits ? (uint64_t)b->T[u] * K : 0);
-  }
+  RCCHK(check_transcripts(h, b, "scrf_align_batch", phones, phone_off, mode, false, 4, 0,
+                          [&](uint64_t K) { return (K > 64 || !wave_on) ? align_group_smem_bytes(l, K) : 0; }, &h->tx.bp_off));
   HIPCHK(h, hipSetDevice(h->device));
-  const bool frame_model = h->cfg.model_type == SCRF_STDFRAME;
   CallTimer call(h);
   HIPCHK(h, h->dec.reserve(b->frame_off[b->U], b->U));
   RCCHK(upload_transcripts(h, U, phones, phone_off, h->tx.bp_off.data()));
@@ -3170,17 +3194,15 @@ extern "C" int scrf_align_batch(scrf_handle h, scrf_batch b, const uint32_t* pho
     uint64_t k_max = 0;   // over the transcripts that fit
     for (uint32_t u = u0; u < u1; u++)
       if (h->tx.bp_off[u + 1] > h->tx.bp_off[u]) k_max = std::max(k_max, phone_off[u + 1] - phone_off[u]);
-    const double* S = fast ? nullptr : cb.S;
-    const float* Wn = fast ? cb.Wn : nullptr;
+    const ScrfArcSrc src = arc_src(h, cb, fast);
     h->tx.n_al_chunks++;
     if (wave_on && k_max <= 64) {
       h->tx.n_al_wave++;
-      KT_RUN("k_align_wave", h->stream, launch_align_wave(h->stream, l, b->view(), u0, u1 - u0, S, Wn, cb.M, cb.m_per_frame, frame_model, aa,
-                                                          h->dec.lab, h->dec.n, h->dec.cost));
+      KT_RUN("k_align_wave", h->stream, launch_align_wave(h->stream, l, b->view(), u0, u1 - u0, src, aa, h->dec.lab, h->dec.n, h->dec.cost));
     } else {
       h->tx.n_al_group++;
-      KT_RUN("k_align_group", h->stream, launch_align_group(h->stream, l, b->view(), u0, u1 - u0, (uint32_t)k_max, S, Wn, cb.M, cb.m_per_frame,
-                                                            frame_model, aa, h->dec.lab, h->dec.n, h->dec.cost));
+      KT_RUN("k_align_group", h->stream, launch_align_group(h->stream, l, b->view(), u0, u1 - u0, (uint32_t)k_max, src, aa, h->dec.lab, h->dec.n,
+                                                            h->dec.cost));
     }
   }));
   return decode_result_fetch(h, b, "scrf_align_batch", call, seg_labels, max_labels, lab_off, cost);
@@ -3199,10 +3221,10 @@ extern "C" int scrf_nbest_batch(scrf_handle h, scrf_batch b, uint32_t n_best, ui
   if (l.D > 0x7fff) return fail(h, SCRF_ERR_INVALID, "%s: maximum duration %u does not fit the 15 duration bits of a back pointer (at most %u)", fn, l.D, 0x7fffu);
   if (l.L > 0xffff) return fail(h, SCRF_ERR_INVALID, "%s: %u labels do not fit the 16 label bits of a back pointer (at most %u)", fn, l.L, 0xffffu);
   if (n_best == 0 || n_best > 0xffff) return fail(h, SCRF_ERR_INVALID, "%s: n_best must be 1 .. 65535 (got %u)", fn, n_best);
-  if (nbest_smem_bytes(l, n_best) > 160 * 1024)
+  if (nbest_smem_bytes(l, n_best) > SCRF_LDS_BYTES)
     return fail(h, SCRF_ERR_INVALID, "%s: n_best %u with %u labels and maximum duration %u needs (%u + 2) x %u x %u x 4 + %zu = %zu bytes of LDS, "
                 "a workgroup has %d", fn, n_best, l.L, l.D, l.D, l.L, n_best, nbest_smem_bytes(l, n_best) - sizeof(float) * ((size_t)l.D + 2) * l.L * n_best,
-                nbest_smem_bytes(l, n_best), 160 * 1024);
+                nbest_smem_bytes(l, n_best), SCRF_LDS_BYTES);
   HIPCHK(h, hipSetDevice(h->device));
   const bool frame_model = h->cfg.model_type == SCRF_STDFRAME;
   const uint32_t U = b->U;
@@ -3218,8 +3240,7 @@ extern "C" int scrf_nbest_batch(scrf_handle h, scrf_batch b, uint32_t n_best, ui
     const uint32_t nutt = u1 - u0;
     h->nb.n_chunks++;
     if (fast) h->nb.n_fast_chunks++;
-    KT_RUN("k_nbest", h->stream, launch_nbest(h->stream, l, bv, u0, nutt, fast ? nullptr : cb.S, fast ? cb.Wn : nullptr, cb.M, cb.m_per_frame,
-                                              frame_model, cb.nb));
+    KT_RUN("k_nbest", h->stream, launch_nbest(h->stream, l, bv, u0, nutt, arc_src(h, cb, fast), cb.nb));
     KT_RUN("k_nbest_count", h->stream, launch_nbest_count(h->stream, l, bv, u0, nutt, frame_model, cb.nb));
     KT_RUN("k_nbest_scan", h->stream, launch_nbest_scan(h->stream, cb.nb, u0, nutt, n_lab, n_hyp, h->nb.hyp_off));
     uint64_t tot[2] = {0, 0};   // the chunk's labels and hypotheses must have room before they are written
@@ -3336,28 +3357,10 @@ extern "C" int scrf_transcript_batch(scrf_handle h, scrf_batch b, const uint32_t
     return fail(h, SCRF_ERR_INVALID, "%s: unknown mode %d (SCRF_ALIGN_ONE = 0, SCRF_ALIGN_RUNS = 1)", fn, mode);
   const uint32_t U = b->U;
   const uint64_t NP = phone_off[U], nF = b->frame_off[U];
-  if (phone_off[0] != 0 || (NP && !phones)) return fail(h, SCRF_ERR_INVALID, "%s: phone_off must start at 0 and phones must be given", fn);
-  // the checks of every transcript, the cells before each utterance (the chunk planner sizes a chunk with them) and the
-  // inverted lists: per utterance its positions sorted by label (a counting sort: ascending inside a label)
-  h->tx.cell_off.assign(U + 1, 0);
-  for (uint32_t u = 0; u < U; u++) {
-    if (phone_off[u + 1] < phone_off[u] || phone_off[u + 1] > NP) return fail(h, SCRF_ERR_INVALID, "%s: phone_off decreases at utterance %u", fn, u);
-    const uint64_t K = phone_off[u + 1] - phone_off[u];
-    const uint32_t* ph = phones + phone_off[u];
-    for (uint64_t k = 0; k < K; k++) {
-      if (ph[k] >= l.L)
-        return fail(h, SCRF_ERR_INVALID, "%s: phone %u at position %llu of utterance %u's transcript (the model has %u)", fn, ph[k],
-                    (unsigned long long)k, u, l.L);
-      if (mode == SCRF_ALIGN_RUNS && k >= 1 && ph[k] == ph[k - 1])
-        return fail(h, SCRF_ERR_INVALID, "%s: utterance %u's transcript repeats phone %u at position %llu; with SCRF_ALIGN_RUNS equal "
-                    "neighbours make the sum count a path more than once: collapse them first", fn, u, ph[k], (unsigned long long)k);
-    }
-    const bool fits = scrf_align_feasible(b->T[u], K, l.D, mode);
-    if (fits && transcript_smem_bytes(l, K) + 128 > 160 * 1024)   // + the 16 per-wavefront parts of end[t]
-      return fail(h, SCRF_ERR_INVALID, "%s: utterance %u's transcript of %llu phones needs (%u + 2) x %llu x 8 = %zu bytes of LDS, "
-                  "a workgroup has %d less 128", fn, u, (unsigned long long)K, l.D, (unsigned long long)K, transcript_smem_bytes(l, K), 160 * 1024);
-    h->tx.cell_off[u + 1] = h->tx.cell_off[u] + (fits ? (uint64_t)b->T[u] * K : 0);
-  }
+  // the checks of every transcript and the cells before each utterance; 128 bytes of LDS go to the 16 per-wavefront parts of
+  // end[t].  Then the inverted lists: per utterance its positions sorted by label (a counting sort: ascending inside a label)
+  RCCHK(check_transcripts(h, b, fn, phones, phone_off, mode, true, 8, 128, [&](uint64_t K) { return transcript_smem_bytes(l, K); },
+                          &h->tx.cell_off));
   std::vector<uint32_t> q;   // [3][nq]: utterance, end frame, label value
   uint64_t nq = 0;
   RCCHK(seg_queries(h, b, fn, seg_labels, lab_off, seg_post != nullptr, &q, &nq));

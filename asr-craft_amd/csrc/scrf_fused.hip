@@ -2656,7 +2656,7 @@ static size_t fused_expf_ws_smem_rows(uint32_t W, int g0, int zb, uint32_t rows)
 static bool fused_expf_ws_fits(uint32_t W, int g0, int zb) {
   uint32_t n_ct;
   fused_expf_ws_xs(W, g0, zb, &n_ct);
-  return n_ct <= 13 && fused_expf_ws_smem_rows(W, g0, zb, FE_ROWS) <= 160 * 1024;
+  return n_ct <= 13 && fused_expf_ws_smem_rows(W, g0, zb, FE_ROWS) <= SCRF_LDS_BYTES;
 }
 static int fused_expf_ws_zb(uint32_t W, int g0) { return !fused_expf_ws_fits(W, g0, 0) && fused_expf_ws_fits(W, g0, 1) ? 1 : 0; }
 // The R tiles go to LDS by DMA (16-byte pieces) when every output pair of R is 16-byte aligned: an even row length
@@ -2672,7 +2672,7 @@ static uint32_t fused_expf_ws_rows(const ScrfKnobs& kn, uint32_t W, int g0) {
   // on the weights after five steps): the default keeps the order the 76-row list gives.
   uint32_t n_ct;
   fused_expf_ws_xs(W, g0, 0, &n_ct);
-  return (kn.expf_big && g0 == 1 && n_ct <= 5 && !fused_expf_ws_zb(W, g0) && fused_expf_ws_smem_rows(W, g0, 0, FW_ROWS_BIG) <= 160 * 1024) ? FW_ROWS_BIG : FE_ROWS;
+  return (kn.expf_big && g0 == 1 && n_ct <= 5 && !fused_expf_ws_zb(W, g0) && fused_expf_ws_smem_rows(W, g0, 0, FW_ROWS_BIG) <= SCRF_LDS_BYTES) ? FW_ROWS_BIG : FE_ROWS;
 }
 static bool fused_expf_ws(const ScrfKnobs& kn, const ScrfLayout& lay, uint32_t W, int f32, int g0) {
   return kn.expf_ws && !f32 && (fused_expf_ws_fits(W, g0, 0) || fused_expf_ws_fits(W, g0, 1));

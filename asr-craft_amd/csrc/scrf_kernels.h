@@ -2,6 +2,7 @@
 #ifndef SCRF_KERNELS_H_
 #define SCRF_KERNELS_H_
 
+#include "scrf_arcw.h"
 #include "scrf_common.h"
 #include "scrf_knobs.h"
 
@@ -27,12 +28,10 @@ void launch_reduce_slabs(hipStream_t st, const double* slab, uint32_t n_chunks, 
 void launch_reduce_xiacc(hipStream_t st, const double* xi_acc, uint32_t n_utts, const ScrfLayout& lay,
                          double* grad);
 void launch_batch_sums(hipStream_t st, const double* numer, const double* zx, uint32_t n, double* sums3);
-void launch_viterbi(hipStream_t st, const ScrfLayout& lay, ScrfBatchView bv, uint32_t u0, uint32_t n_utts,
-                    const double* S, const double* M, int m_per_frame, int frame_model, uint16_t* bp_b,
-                    uint16_t* bp_e, uint32_t* out_labels, uint32_t* out_n, float* out_cost,
-                    const float* Wn = nullptr);   // Wn: float(-1 * score) per (segment, label), replaces S
-void launch_arcs(hipStream_t st, const ScrfLayout& lay, uint32_t T, int frame_model, const double* S,
-                 const double* M, int m_per_frame, float final_w, scrf_arc* arcs);
+// src (here and below): the chunk's arcs, ScrfArcSrc of scrf_arcw.h
+void launch_viterbi(hipStream_t st, const ScrfLayout& lay, ScrfBatchView bv, uint32_t u0, uint32_t n_utts, const ScrfArcSrc& src,
+                    uint16_t* bp_b, uint16_t* bp_e, uint32_t* out_labels, uint32_t* out_n, float* out_cost);
+void launch_arcs(hipStream_t st, const ScrfLayout& lay, uint32_t T, const ScrfArcSrc& src, float final_w, scrf_arc* arcs);
 void launch_sgd_step(hipStream_t st, double* lambda, double* lambda_acc, double* gsa, double* grad, uint32_t n,
                      double lr, int adagrad, double eps);
 void launch_scale(hipStream_t st, double* v, uint32_t n, double s, int divide);
@@ -160,8 +159,8 @@ void launch_dur_table(hipStream_t st, const ScrfLayout& lay, uint32_t W, const d
 void launch_avg_prefix(hipStream_t st, ScrfBatchView bv, uint32_t u0, uint32_t n_utts, uint32_t L, double* P);
 // k_viterbi on float arc weights with one wavefront per utterance (fast decode; L <= 64, constant M)
 int viterbi_fast_supported(const ScrfLayout& lay);
-void launch_viterbi_fast(hipStream_t st, const ScrfKnobs& kn, const ScrfLayout& lay, ScrfBatchView bv, uint32_t u0, uint32_t n_utts, const float* Wn,
-                         const double* M, uint16_t* bp_b, uint16_t* bp_e, uint32_t* out_labels, uint32_t* out_n, float* out_cost);
+void launch_viterbi_fast(hipStream_t st, const ScrfKnobs& kn, const ScrfLayout& lay, ScrfBatchView bv, uint32_t u0, uint32_t n_utts,
+                         const ScrfArcSrc& src, uint16_t* bp_b, uint16_t* bp_e, uint32_t* out_labels, uint32_t* out_n, float* out_cost);
 // decode mode: float arc weights + the list of entries to recompute (ScrfDecodeOut)
 void launch_scores_fused_decode(hipStream_t st, const ScrfFusedArgs& fa, const ScrfLayout& lay, const double* lambda,
                                 const double* P, uint64_t n_tiles, const ScrfDecodeOut& dz);
@@ -280,16 +279,15 @@ struct ScrfLatBufs {
   double* best;   // [U], batch-absolute
 };
 size_t lat_sweep_smem_bytes(const ScrfLayout& lay);
-void launch_lat_sweep(hipStream_t st, const ScrfLayout& lay, ScrfBatchView bv, uint32_t u0, uint32_t n_utts, const double* S,
-                      const double* M, int m_per_frame, int frame_model, const ScrfLatBufs& lb);
+void launch_lat_sweep(hipStream_t st, const ScrfLayout& lay, ScrfBatchView bv, uint32_t u0, uint32_t n_utts, const ScrfArcSrc& src,
+                      const ScrfLatBufs& lb);
 void launch_lat_count(hipStream_t st, const ScrfLayout& lay, ScrfBatchView bv, uint32_t u0, uint32_t n_utts, uint32_t t_max,
-                      const double* S, const double* M, int m_per_frame, int frame_model, const ScrfLatBufs& lb, double beam,
-                      uint32_t* counts);
+                      const ScrfArcSrc& src, const ScrfLatBufs& lb, double beam, uint32_t* counts);
 void launch_lat_scan(hipStream_t st, ScrfBatchView bv, uint32_t u0, uint32_t n_utts, const uint32_t* counts, uint64_t n_nodes,
                      uint64_t* node_off, uint64_t base, uint64_t* utt_off);
 void launch_lat_emit(hipStream_t st, const ScrfLayout& lay, ScrfBatchView bv, uint32_t u0, uint32_t n_utts, uint32_t t_max,
-                     const double* S, const double* M, int m_per_frame, int frame_model, const ScrfLatBufs& lb, double beam,
-                     const uint64_t* node_off, uint64_t base, uint64_t cap, scrf_arc* out);
+                     const ScrfArcSrc& src, const ScrfLatBufs& lb, double beam, const uint64_t* node_off, uint64_t base, uint64_t cap,
+                     scrf_arc* out);
 
 // ---- forced alignment (scrf_align.hip)
 struct ScrfAlignArgs {
@@ -319,14 +317,11 @@ __device__ inline bool align_live_b(int t, int k, int T, int K, int D, int mode)
 }
 
 int align_wave_supported(const ScrfLayout& lay);
-// S (fp64 scores) or Wn (their float arc weights, segment model only): exactly one is given
-void launch_align_wave(hipStream_t st, const ScrfLayout& lay, ScrfBatchView bv, uint32_t u0, uint32_t n_utts, const double* S,
-                       const float* Wn, const double* M, int m_per_frame, int frame_model, const ScrfAlignArgs& aa,
-                       uint32_t* out_labels, uint32_t* out_n, float* out_cost);
+void launch_align_wave(hipStream_t st, const ScrfLayout& lay, ScrfBatchView bv, uint32_t u0, uint32_t n_utts, const ScrfArcSrc& src,
+                       const ScrfAlignArgs& aa, uint32_t* out_labels, uint32_t* out_n, float* out_cost);
 size_t align_group_smem_bytes(const ScrfLayout& lay, uint64_t K);
 void launch_align_group(hipStream_t st, const ScrfLayout& lay, ScrfBatchView bv, uint32_t u0, uint32_t n_utts, uint32_t k_max,
-                        const double* S, const float* Wn, const double* M, int m_per_frame, int frame_model,
-                        const ScrfAlignArgs& aa, uint32_t* out_labels, uint32_t* out_n, float* out_cost);
+                        const ScrfArcSrc& src, const ScrfAlignArgs& aa, uint32_t* out_labels, uint32_t* out_n, float* out_cost);
 
 // ---- transcript scoring (scrf_transcript.hip)
 struct ScrfTransArgs {
@@ -369,9 +364,8 @@ struct ScrfNbestBufs {
 __host__ __device__ inline uint32_t nbest_heads(uint32_t L, uint32_t D) { return ((L > D + 1 ? L : D + 1) + 1) & ~1u; }
 // dynamic LDS of a workgroup: end double-buffered and the boundary ring, (D + 2) L N floats, + the head ranks
 size_t nbest_smem_bytes(const ScrfLayout& lay, uint32_t n_best);
-// S (fp64 scores) or Wn (their float arc weights, segment model only): exactly one is given
-void launch_nbest(hipStream_t st, const ScrfLayout& lay, ScrfBatchView bv, uint32_t u0, uint32_t n_utts, const double* S, const float* Wn,
-                  const double* M, int m_per_frame, int frame_model, const ScrfNbestBufs& nb);
+void launch_nbest(hipStream_t st, const ScrfLayout& lay, ScrfBatchView bv, uint32_t u0, uint32_t n_utts, const ScrfArcSrc& src,
+                  const ScrfNbestBufs& nb);
 void launch_nbest_count(hipStream_t st, const ScrfLayout& lay, ScrfBatchView bv, uint32_t u0, uint32_t n_utts, int frame_model,
                         const ScrfNbestBufs& nb);
 // lab_base / hyp_base: labels and hypotheses of the chunks done; hyp_off [U + 1]: the batch's hypothesis offsets

@@ -570,6 +570,8 @@ void launch_batch_sums(hipStream_t st, const double* numer, const double* zx, ui
 //   boundary(t,l) <- end(t-1,p), p ascending ; end(t,l) <- start (d=t+1) then boundary(t',l),
 //   t' ascending (d descending) ; final <- end(T-1,l), l ascending, weight -0.0f.
 // Frame model (CRF_LatticeBuilder.h:97-204): state(t,c) <- state(t-1,p), w = float(-(M+S)).
+// The weights are written out here as scrf_arcw.h's scrf_w_* form them: through the view (ScrfArcView) the kernel measured
+// 0.5 % slower at 256 utterances x 304 frames with a matrix per frame (profiles/EXPERIMENTS.md), so its body stays as it was.
 // ------------------------------------------------------------------------------------------
 __global__ void k_viterbi(ScrfLayout lay, ScrfBatchView bv, uint32_t u0, const double* __restrict__ S,
                           const double* __restrict__ M, int m_per_frame, int frame_model,
@@ -691,16 +693,15 @@ __global__ void k_viterbi(ScrfLayout lay, ScrfBatchView bv, uint32_t u0, const d
   }
 }
 
-void launch_viterbi(hipStream_t st, const ScrfLayout& lay, ScrfBatchView bv, uint32_t u0, uint32_t n_utts,
-                    const double* S, const double* M, int m_per_frame, int frame_model, uint16_t* bp_b,
-                    uint16_t* bp_e, uint32_t* out_labels, uint32_t* out_n, float* out_cost, const float* Wn) {
+void launch_viterbi(hipStream_t st, const ScrfLayout& lay, ScrfBatchView bv, uint32_t u0, uint32_t n_utts, const ScrfArcSrc& src,
+                    uint16_t* bp_b, uint16_t* bp_e, uint32_t* out_labels, uint32_t* out_n, float* out_cost) {
   if (n_utts == 0) return;
   int NT = ((int)lay.L + 63) / 64 * 64;
   if (NT > 1024) NT = 1024;
   size_t sm = sizeof(float) * ((size_t)2 * lay.L + (size_t)lay.D * lay.L);
   hipFuncSetAttribute((const void*)k_viterbi, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sm);
-  hipLaunchKernelGGL(k_viterbi, dim3(n_utts), dim3(NT), sm, st, lay, bv, u0, S, M, m_per_frame, frame_model,
-                     frame_model ? nullptr : Wn, bp_b, bp_e, out_labels, out_n, out_cost);
+  hipLaunchKernelGGL(k_viterbi, dim3(n_utts), dim3(NT), sm, st, lay, bv, u0, src.S, src.M, src.m_per_frame, src.frame_model,
+                     src.Wn, bp_b, bp_e, out_labels, out_n, out_cost);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -848,16 +849,16 @@ int viterbi_fast_supported(const ScrfLayout& lay) {
   return lay.L <= 64 && lay.D >= 2 && lay.D <= 40 && !lay.use_tf &&
          sizeof(float) * ((size_t)lay.L * lay.L + VF_WAVES * ((size_t)lay.L + (size_t)lay.D * lay.L)) <= 64 * 1024;
 }
-void launch_viterbi_fast(hipStream_t st, const ScrfKnobs& kn, const ScrfLayout& lay, ScrfBatchView bv, uint32_t u0, uint32_t n_utts, const float* Wn,
-                         const double* M, uint16_t* bp_b, uint16_t* bp_e, uint32_t* out_labels, uint32_t* out_n, float* out_cost) {
+void launch_viterbi_fast(hipStream_t st, const ScrfKnobs& kn, const ScrfLayout& lay, ScrfBatchView bv, uint32_t u0, uint32_t n_utts,
+                         const ScrfArcSrc& src, uint16_t* bp_b, uint16_t* bp_e, uint32_t* out_labels, uint32_t* out_n, float* out_cost) {
   if (n_utts == 0) return;
   const size_t sm = sizeof(float) * ((size_t)lay.L * lay.L + VF_WAVES * ((size_t)lay.L + (size_t)lay.D * lay.L));
   const dim3 grid((n_utts + VF_WAVES - 1) / VF_WAVES), block(64 * VF_WAVES);
 #define VF_GO2(N, LV)                                                                                                          \
   do {                                                                                                                         \
     hipFuncSetAttribute((const void*)k_viterbi_fast<N, LV>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sm);              \
-    hipLaunchKernelGGL((k_viterbi_fast<N, LV>), grid, block, sm, st, lay, bv, u0, n_utts, Wn, M, bp_b, bp_e, out_labels, out_n, \
-                       out_cost);                                                                                              \
+    hipLaunchKernelGGL((k_viterbi_fast<N, LV>), grid, block, sm, st, lay, bv, u0, n_utts, src.Wn, src.M, bp_b, bp_e, out_labels, \
+                       out_n, out_cost);                                                                                       \
   } while (0)
   // register column + 16-byte reads of the previous node's costs: L a multiple of 4 (the LDS vectors stay 16-byte aligned)
   const bool vec_ok = kn.viterbi_vec;
@@ -998,89 +999,37 @@ void launch_decode_fixup(hipStream_t st, const float* frames, uint32_t W, ScrfBa
 
 // ------------------------------------------------------------------------------------------
 // k_arcs_seg / k_arcs_frame: one block per node (+1 for the final arcs), arcs written at the
-// index the reference's AddArc call order gives them.
+// index the reference's AddArc call order gives them: the node's first arc, then scrf_node_arc's
+// order inside the node (scrf_arcw.h).
 // ------------------------------------------------------------------------------------------
+template <int FRAME>
+__device__ inline void arcs_node(const ScrfLayout& lay, uint32_t T, const ScrfArcSrc& src, float final_w, scrf_arc* __restrict__ arcs) {
+  const uint32_t L = lay.L, t = blockIdx.x;
+  const ScrfArcNode n = scrf_arc_node(ScrfArcView(src, lay, T), lay.D, t, FRAME, final_w);
+  const uint64_t ab = !FRAME ? scrf_arc_base(t, L, lay.D) : t == 0 ? 0 : (uint64_t)L + (uint64_t)(t - 1) * L * L;
+  ScrfArcEnd from, to;
+  // the n.nb arcs ahead and the arcs behind them in loops of their own: inside each, which of the two idx is needs no test
+  for (uint32_t idx = threadIdx.x; idx < n.nb; idx += blockDim.x) arcs[ab + idx] = scrf_node_arc(n, idx, &from, &to);
+  for (uint32_t idx = n.nb + threadIdx.x; idx < n.n_arcs; idx += blockDim.x) {
+    __builtin_assume(idx >= n.nb);
+    arcs[ab + idx] = scrf_node_arc(n, idx, &from, &to);
+  }
+}
 __global__ void k_arcs_seg(ScrfLayout lay, uint32_t T, const double* __restrict__ S,
                            const double* __restrict__ M, int m_per_frame, float final_w,
                            scrf_arc* __restrict__ arcs) {
-  const uint32_t L = lay.L, D = lay.D;
-  const uint32_t t = blockIdx.x;
-  const size_t LL = (size_t)L * L;
-  if (t == T) {  // final arcs (:366-399)
-    const uint64_t ab = scrf_arc_base(T, L, D);
-    const int32_t fin = scrf_node_start_state(T, L);
-    for (uint32_t p = threadIdx.x; p < L; p += blockDim.x) {
-      int32_t src = (T == 1) ? scrf_node_start_state(0, L) + (int32_t)p
-                             : scrf_node_start_state(T - 1, L) + (int32_t)L + (int32_t)p;
-      scrf_arc a = {src, 0, 0, final_w, fin};
-      arcs[ab + p] = a;
-    }
-    return;
-  }
-  const uint64_t ab = scrf_arc_base(t, L, D);
-  const uint32_t np = scrf_num_prev(t, D), nd = scrf_node_max_dur(t, D);
-  const uint64_t base = scrf_seg_base(t, D);
-  const int32_t nss = scrf_node_start_state(t, L);
-  uint64_t eb = ab;
-  if (np > 0) {  // boundary arcs (:260-296): for lab, for prev_lab
-    const double* Mt = M + (m_per_frame ? (size_t)t * LL : 0);
-    const int32_t pbase = (t == 1) ? scrf_node_start_state(0, L) : scrf_node_start_state(t - 1, L) + (int32_t)L;
-    for (uint32_t idx = threadIdx.x; idx < L * L; idx += blockDim.x) {
-      uint32_t lab = idx / L, pl = idx % L;
-      scrf_arc a = {pbase + (int32_t)pl, 0, 0, scrf_w_boundary(Mt, L, pl, lab), nss + (int32_t)lab};
-      arcs[ab + idx] = a;
-    }
-    eb += LL;
-  }
-  const int32_t ebase = (t == 0) ? nss : nss + (int32_t)L;  // end states of node t
-  for (uint32_t idx = threadIdx.x; idx < L * nd; idx += blockDim.x) {  // (:300-325): for lab, for dur
-    uint32_t lab = idx / nd, d = idx % nd + 1;
-    int32_t src = (d <= np) ? scrf_node_start_state(t - d + 1, L) + (int32_t)lab : 0;
-    int32_t lb = (int32_t)(lab + L * (d - 1) + 1);
-    scrf_arc a = {src, lb, lb, scrf_w_segment(S, base, d, L, lab), ebase + (int32_t)lab};
-    arcs[eb + idx] = a;
-  }
+  arcs_node<0>(lay, T, ScrfArcSrc{S, nullptr, M, m_per_frame, 0}, final_w, arcs);
 }
-
 __global__ void k_arcs_frame(ScrfLayout lay, uint32_t T, const double* __restrict__ S,
                              const double* __restrict__ M, int m_per_frame, float final_w,
                              scrf_arc* __restrict__ arcs) {
-  const uint32_t L = lay.L;
-  const uint32_t t = blockIdx.x;
-  const size_t LL = (size_t)L * L;
-  if (t == T) {
-    const uint64_t ab = (uint64_t)L + (uint64_t)(T - 1) * LL;
-    const int32_t fin = (int32_t)(L * T + 1);
-    for (uint32_t p = threadIdx.x; p < L; p += blockDim.x) {
-      scrf_arc a = {(int32_t)(L * (T - 1) + p + 1), 0, 0, final_w, fin};
-      arcs[ab + p] = a;
-    }
-    return;
-  }
-  if (t == 0) {
-    for (uint32_t c = threadIdx.x; c < L; c += blockDim.x) {
-      scrf_arc a = {0, (int32_t)c + 1, (int32_t)c + 1, scrf_w_segment(S, 0, 1, L, c), (int32_t)c + 1};
-      arcs[c] = a;
-    }
-    return;
-  }
-  const uint64_t ab = (uint64_t)L + (uint64_t)(t - 1) * LL;
-  const double* Mt = M + (m_per_frame ? (size_t)t * LL : 0);
-  for (uint32_t idx = threadIdx.x; idx < L * L; idx += blockDim.x) {
-    uint32_t c = idx / L, p = idx % L;
-    float w = scrf_w_frame(Mt, S, t, L, p, c);
-    scrf_arc a = {(int32_t)(L * (t - 1) + p + 1), (int32_t)c + 1, (int32_t)c + 1, w, (int32_t)(L * t + c + 1)};
-    arcs[ab + idx] = a;
-  }
+  arcs_node<1>(lay, T, ScrfArcSrc{S, nullptr, M, m_per_frame, 1}, final_w, arcs);
 }
 
-void launch_arcs(hipStream_t st, const ScrfLayout& lay, uint32_t T, int frame_model, const double* S,
-                 const double* M, int m_per_frame, float final_w, scrf_arc* arcs) {
+void launch_arcs(hipStream_t st, const ScrfLayout& lay, uint32_t T, const ScrfArcSrc& src, float final_w, scrf_arc* arcs) {
   if (T == 0) return;
-  if (frame_model)
-    hipLaunchKernelGGL(k_arcs_frame, dim3(T + 1), dim3(256), 0, st, lay, T, S, M, m_per_frame, final_w, arcs);
-  else
-    hipLaunchKernelGGL(k_arcs_seg, dim3(T + 1), dim3(256), 0, st, lay, T, S, M, m_per_frame, final_w, arcs);
+  hipLaunchKernelGGL(src.frame_model ? k_arcs_frame : k_arcs_seg, dim3(T + 1), dim3(256), 0, st, lay, T, src.S, src.M, src.m_per_frame,
+                     final_w, arcs);
 }
 
 // ------------------------------------------------------------------------------------------

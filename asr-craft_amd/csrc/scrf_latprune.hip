@@ -1,7 +1,7 @@
 // scrf_latprune.hip -- beam-pruned lattices, batched.
 //
-// The lattice is the one k_arcs_seg / k_arcs_frame emit (same states, same arc order, the same float weights through
-// scrf_arcw.h); it is never materialised here.  With wd = (double)w:
+// The lattice is the one k_arcs_seg / k_arcs_frame emit: both take a node's arcs -- states, order and float weights -- from
+// scrf_node_arc (scrf_arcw.h); it is never materialised here.  With wd = (double)w:
 //   fwd[0] = 0,      fwd[s] = min over arcs into s  of fwd[src] + wd
 //   bwd[final] = 0,  bwd[s] = min over arcs out of s of wd + bwd[dst]
 //   an arc is kept iff (fwd[src] + wd) + bwd[dst] <= fwd[final] + beam          (fp64, that association)
@@ -31,10 +31,9 @@ __global__ void k_lat_sweep(ScrfLayout lay, ScrfBatchView bv, uint32_t u0, const
   const int L = lay.L, D = lay.D;
   const int tid = threadIdx.x, NT = blockDim.x;
   const uint32_t u = u0 + blockIdx.x;
-  const int T = (int)bv.T[u];
-  const uint64_t f_base = bv.frame_off[u] - bv.frame_off[u0];
-  const double* Su = S + (bv.seg_off[u] - bv.seg_off[u0]) * L;
-  const size_t LL = (size_t)L * L;
+  const ScrfArcView v(ScrfArcSrc{S, nullptr, M, m_per_frame, frame_model}, lay, bv, u0, u);
+  const int T = (int)v.T;
+  const uint64_t f_base = v.f_base;
   const double wfin = (double)(frame_model ? 0.0f : -0.0f);
   double* sh = lsm;            // [2][L]: the vector every label reads (end states forward, boundary states backward)
   double* ring = lsm + 2 * L;  // [D][L]: the vector a label reads only its own column of
@@ -45,25 +44,25 @@ __global__ void k_lat_sweep(ScrfLayout lay, ScrfBatchView bv, uint32_t u0, const
     for (int t = 0; t < T; t++) {
       double* cur = sh + (t & 1) * L;
       const double* prev = sh + ((t + 1) & 1) * L;
-      const double* Mt = M + (m_per_frame ? (f_base + t) * LL : 0);
+      const double* Mt = v.Mt(t);
       const uint64_t base = scrf_seg_base(t, D);
       const int np = (int)scrf_num_prev(t, D), nd = (int)scrf_node_max_dur(t, D);
       for (int l = tid; l < L; l += NT) {
         double e = INFINITY;
         if (frame_model) {
-          if (t == 0) e = 0.0 + (double)scrf_w_segment(Su, 0, 1, L, l);
+          if (t == 0) e = 0.0 + (double)v.start(l);
           else
-            for (int p = 0; p < L; p++) e = lat_min(e, prev[p] + (double)scrf_w_frame(Mt, Su, t, L, p, l));
+            for (int p = 0; p < L; p++) e = lat_min(e, prev[p] + (double)v.frame(Mt, t, p, l));
         } else {
           if (t >= 1) {
             double b = INFINITY;
-            for (int p = 0; p < L; p++) b = lat_min(b, prev[p] + (double)scrf_w_boundary(Mt, L, p, l));
+            for (int p = 0; p < L; p++) b = lat_min(b, prev[p] + (double)v.boundary(Mt, p, l));
             ring[(t % D) * L + l] = b;
             fB[(size_t)t * L + l] = b;
           }
           for (int d = 1; d <= nd; d++) {
             const double src = d <= np ? ring[((t - d + 1) % D) * L + l] : 0.0;
-            e = lat_min(e, src + (double)scrf_w_segment(Su, base, d, L, l));
+            e = lat_min(e, src + (double)v.segment(base, d, l));
           }
         }
         cur[l] = e;
@@ -83,14 +82,14 @@ __global__ void k_lat_sweep(ScrfLayout lay, ScrfBatchView bv, uint32_t u0, const
     for (int t = T - 1; t >= 0; t--) {
       double* cur = sh + (t & 1) * L;
       const double* nxt = sh + ((t + 1) & 1) * L;
-      const double* Mn = M + (m_per_frame ? (f_base + t + 1) * LL : 0);   // read only when t + 1 < T
+      const double* Mn = v.Mt(t + 1);   // read only when t + 1 < T
       for (int l = tid; l < L; l += NT) {
         double e = INFINITY;
         if (t == T - 1) e = wfin + 0.0;
         else if (frame_model)
-          for (int c = 0; c < L; c++) e = lat_min(e, (double)scrf_w_frame(Mn, Su, t + 1, L, l, c) + nxt[c]);
+          for (int c = 0; c < L; c++) e = lat_min(e, (double)v.frame(Mn, t + 1, l, c) + nxt[c]);
         else
-          for (int c = 0; c < L; c++) e = lat_min(e, (double)scrf_w_boundary(Mn, L, l, c) + nxt[c]);
+          for (int c = 0; c < L; c++) e = lat_min(e, (double)v.boundary(Mn, l, c) + nxt[c]);
         bE[(size_t)t * L + l] = e;
         if (frame_model) {
           cur[l] = e;
@@ -101,7 +100,7 @@ __global__ void k_lat_sweep(ScrfLayout lay, ScrfBatchView bv, uint32_t u0, const
             const int dmax = T - t < D ? T - t : D;
             for (int d = 1; d <= dmax; d++) {
               const int te = t + d - 1;
-              b = lat_min(b, (double)scrf_w_segment(Su, scrf_seg_base(te, D), d, L, l) + ring[(te % D) * L + l]);
+              b = lat_min(b, (double)v.segment(scrf_seg_base(te, D), d, l) + ring[(te % D) * L + l]);
             }
             cur[l] = b;
             bB[(size_t)t * L + l] = b;
@@ -113,75 +112,28 @@ __global__ void k_lat_sweep(ScrfLayout lay, ScrfBatchView bv, uint32_t u0, const
   }
 }
 
-// everything a (utterance, node) workgroup needs to walk its arcs
+// everything a (utterance, node) workgroup needs to walk its arcs: the node (scrf_arcw.h) and the utterance's sweeps
 struct LatNode {
-  uint32_t L, D, T, t, n_arcs, nb, np, nd;
-  int frame_model;
-  const double *Su, *Mt, *fB, *fE, *bB, *bE;
-  uint64_t base;
+  ScrfArcNode a;
+  const double *fB, *fE, *bB, *bE;
   double limit;
-  float final_w;
 };
 
 static __device__ inline LatNode lat_node(const ScrfLayout& lay, const ScrfBatchView& bv, uint32_t u0, uint32_t u, uint32_t t,
-                                          const double* S, const double* M, int m_per_frame, int frame_model,
-                                          const ScrfLatBufs& lb, double beam) {
-  LatNode n;
-  n.L = lay.L; n.D = lay.D; n.T = bv.T[u]; n.t = t; n.frame_model = frame_model;
-  const uint64_t f_base = bv.frame_off[u] - bv.frame_off[u0];
-  n.Su = S + (bv.seg_off[u] - bv.seg_off[u0]) * n.L;
-  n.Mt = M + ((m_per_frame && t < n.T) ? (f_base + t) * (size_t)n.L * n.L : 0);
-  n.fB = lb.fB + f_base * n.L; n.fE = lb.fE + f_base * n.L;
-  n.bB = lb.bB + f_base * n.L; n.bE = lb.bE + f_base * n.L;
-  n.limit = lb.best[u] + beam;
-  n.final_w = frame_model ? 0.0f : -0.0f;
-  n.base = t < n.T ? scrf_seg_base(t, n.D) : 0;
-  n.np = t < n.T ? scrf_num_prev(t, n.D) : 0;
-  n.nd = t < n.T ? scrf_node_max_dur(t, n.D) : 0;
-  if (t == n.T) { n.nb = 0; n.n_arcs = n.L; }
-  else if (frame_model) { n.nb = t > 0 ? n.L * n.L : 0; n.n_arcs = t > 0 ? n.nb : n.L; }
-  else { n.nb = n.np > 0 ? n.L * n.L : 0; n.n_arcs = n.nb + n.L * n.nd; }
-  return n;
+                                          const ScrfArcSrc& src, const ScrfLatBufs& lb, double beam) {
+  const ScrfArcView v(src, lay, bv, u0, u);
+  const size_t fl = v.f_base * v.L;
+  return LatNode{scrf_arc_node(v, lay.D, t, src.frame_model, src.frame_model ? 0.0f : -0.0f),
+                 lb.fB + fl, lb.fE + fl, lb.bB + fl, lb.bE + fl, lb.best[u] + beam};
 }
 
-// arc `idx` of the node, as k_arcs_seg / k_arcs_frame write it, and whether the beam keeps it
+// arc `idx` of the node and whether the beam keeps it: fwd of its source state, bwd of its destination
 static __device__ inline bool lat_arc(const LatNode& n, uint32_t idx, scrf_arc* a) {
-  const uint32_t L = n.L, t = n.t, T = n.T;
-  double fs, bd;
-  if (n.frame_model) {
-    if (t == T) {
-      *a = scrf_arc{(int32_t)(L * (T - 1) + idx + 1), 0, 0, n.final_w, (int32_t)(L * T + 1)};
-      fs = n.fE[(size_t)(T - 1) * L + idx]; bd = 0.0;
-    } else if (t == 0) {
-      *a = scrf_arc{0, (int32_t)idx + 1, (int32_t)idx + 1, scrf_w_segment(n.Su, 0, 1, L, idx), (int32_t)idx + 1};
-      fs = 0.0; bd = n.bE[idx];
-    } else {
-      const uint32_t c = idx / L, p = idx % L;
-      *a = scrf_arc{(int32_t)(L * (t - 1) + p + 1), (int32_t)c + 1, (int32_t)c + 1, scrf_w_frame(n.Mt, n.Su, t, L, p, c),
-                    (int32_t)(L * t + c + 1)};
-      fs = n.fE[(size_t)(t - 1) * L + p]; bd = n.bE[(size_t)t * L + c];
-    }
-  } else if (t == T) {
-    const int32_t src = (T == 1) ? scrf_node_start_state(0, L) + (int32_t)idx
-                                 : scrf_node_start_state(T - 1, L) + (int32_t)L + (int32_t)idx;
-    *a = scrf_arc{src, 0, 0, n.final_w, scrf_node_start_state(T, L)};
-    fs = n.fE[(size_t)(T - 1) * L + idx]; bd = 0.0;
-  } else {
-    const int32_t nss = scrf_node_start_state(t, L);
-    if (idx < n.nb) {
-      const uint32_t lab = idx / L, pl = idx % L;
-      const int32_t pbase = (t == 1) ? scrf_node_start_state(0, L) : scrf_node_start_state(t - 1, L) + (int32_t)L;
-      *a = scrf_arc{pbase + (int32_t)pl, 0, 0, scrf_w_boundary(n.Mt, L, pl, lab), nss + (int32_t)lab};
-      fs = n.fE[(size_t)(t - 1) * L + pl]; bd = n.bB[(size_t)t * L + lab];
-    } else {
-      const uint32_t j = idx - n.nb, lab = j / n.nd, d = j % n.nd + 1;
-      const int32_t src = (d <= n.np) ? scrf_node_start_state(t - d + 1, L) + (int32_t)lab : 0;
-      const int32_t lbl = (int32_t)(lab + L * (d - 1) + 1);
-      const int32_t ebase = (t == 0) ? nss : nss + (int32_t)L;
-      *a = scrf_arc{src, lbl, lbl, scrf_w_segment(n.Su, n.base, d, L, lab), ebase + (int32_t)lab};
-      fs = (d <= n.np) ? n.fB[(size_t)(t - d + 1) * L + lab] : 0.0; bd = n.bE[(size_t)t * L + lab];
-    }
-  }
+  ScrfArcEnd s, d;
+  *a = scrf_node_arc(n.a, idx, &s, &d);
+  const size_t L = n.a.v.L;
+  const double fs = s.kind == SCRF_ARC_TERM ? 0.0 : (s.kind == SCRF_ARC_BOUNDARY ? n.fB : n.fE)[s.t * L + s.l];
+  const double bd = d.kind == SCRF_ARC_TERM ? 0.0 : (d.kind == SCRF_ARC_BOUNDARY ? n.bB : n.bE)[d.t * L + d.l];
   return (fs + (double)a->w) + bd <= n.limit;
 }
 
@@ -196,10 +148,10 @@ __global__ __launch_bounds__(LAT_NT) void k_lat_count(ScrfLayout lay, ScrfBatchV
   __shared__ uint32_t red[LAT_NT];
   const uint32_t u = u0 + blockIdx.y, t = blockIdx.x;
   if (t > bv.T[u]) return;
-  const LatNode n = lat_node(lay, bv, u0, u, t, S, M, m_per_frame, frame_model, lb, beam);
+  const LatNode n = lat_node(lay, bv, u0, u, t, ScrfArcSrc{S, nullptr, M, m_per_frame, frame_model}, lb, beam);
   uint32_t c = 0;
   scrf_arc a;
-  for (uint32_t idx = threadIdx.x; idx < n.n_arcs; idx += LAT_NT) c += lat_arc(n, idx, &a) ? 1u : 0u;
+  for (uint32_t idx = threadIdx.x; idx < n.a.n_arcs; idx += LAT_NT) c += lat_arc(n, idx, &a) ? 1u : 0u;
   red[threadIdx.x] = c;
   __syncthreads();
   for (uint32_t s = LAT_NT / 2; s > 0; s >>= 1) {
@@ -248,15 +200,15 @@ __global__ __launch_bounds__(LAT_NT) void k_lat_emit(ScrfLayout lay, ScrfBatchVi
   const uint64_t ni = lat_node_index(bv, u0, u, t);
   const uint64_t o0 = node_off[ni], o1 = node_off[ni + 1];
   if (o0 == o1) return;   // nothing of this node survives
-  const LatNode n = lat_node(lay, bv, u0, u, t, S, M, m_per_frame, frame_model, lb, beam);
+  const LatNode n = lat_node(lay, bv, u0, u, t, ScrfArcSrc{S, nullptr, M, m_per_frame, frame_model}, lb, beam);
   const uint32_t lane = threadIdx.x % SCRF_WAVE, wv = threadIdx.x / SCRF_WAVE;
   uint64_t run = base + o0;
   // the node's arcs in index order, a workgroup's width at a time: rank inside the wavefront from the ballot, the
   // wavefronts' bases through LDS
-  for (uint32_t r0 = 0; r0 < n.n_arcs; r0 += LAT_NT) {
+  for (uint32_t r0 = 0; r0 < n.a.n_arcs; r0 += LAT_NT) {
     const uint32_t idx = r0 + threadIdx.x;
     scrf_arc a;
-    const bool keep = idx < n.n_arcs && lat_arc(n, idx, &a);
+    const bool keep = idx < n.a.n_arcs && lat_arc(n, idx, &a);
     const unsigned long long bal = __ballot(keep);
     if (lane == 0) wcnt[wv] = (uint32_t)__popcll(bal);
     __syncthreads();
@@ -277,22 +229,21 @@ __global__ __launch_bounds__(LAT_NT) void k_lat_emit(ScrfLayout lay, ScrfBatchVi
 
 size_t lat_sweep_smem_bytes(const ScrfLayout& lay) { return sizeof(double) * ((size_t)lay.D + 2) * lay.L; }
 
-void launch_lat_sweep(hipStream_t st, const ScrfLayout& lay, ScrfBatchView bv, uint32_t u0, uint32_t n_utts, const double* S,
-                      const double* M, int m_per_frame, int frame_model, const ScrfLatBufs& lb) {
+void launch_lat_sweep(hipStream_t st, const ScrfLayout& lay, ScrfBatchView bv, uint32_t u0, uint32_t n_utts, const ScrfArcSrc& src,
+                      const ScrfLatBufs& lb) {
   if (n_utts == 0) return;
   int NT = ((int)lay.L + 63) / 64 * 64;
   if (NT > 256) NT = 256;
   const size_t sm = lat_sweep_smem_bytes(lay);
   hipFuncSetAttribute((const void*)k_lat_sweep, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sm);
-  hipLaunchKernelGGL(k_lat_sweep, dim3(n_utts, 2), dim3(NT), sm, st, lay, bv, u0, S, M, m_per_frame, frame_model, lb);
+  hipLaunchKernelGGL(k_lat_sweep, dim3(n_utts, 2), dim3(NT), sm, st, lay, bv, u0, src.S, src.M, src.m_per_frame, src.frame_model, lb);
 }
 
 void launch_lat_count(hipStream_t st, const ScrfLayout& lay, ScrfBatchView bv, uint32_t u0, uint32_t n_utts, uint32_t t_max,
-                      const double* S, const double* M, int m_per_frame, int frame_model, const ScrfLatBufs& lb, double beam,
-                      uint32_t* counts) {
+                      const ScrfArcSrc& src, const ScrfLatBufs& lb, double beam, uint32_t* counts) {
   if (n_utts == 0) return;
-  hipLaunchKernelGGL(k_lat_count, dim3(t_max + 1, n_utts), dim3(LAT_NT), 0, st, lay, bv, u0, S, M, m_per_frame, frame_model, lb,
-                     beam, counts);
+  hipLaunchKernelGGL(k_lat_count, dim3(t_max + 1, n_utts), dim3(LAT_NT), 0, st, lay, bv, u0, src.S, src.M, src.m_per_frame, src.frame_model,
+                     lb, beam, counts);
 }
 
 void launch_lat_scan(hipStream_t st, ScrfBatchView bv, uint32_t u0, uint32_t n_utts, const uint32_t* counts, uint64_t n_nodes,
@@ -302,9 +253,9 @@ void launch_lat_scan(hipStream_t st, ScrfBatchView bv, uint32_t u0, uint32_t n_u
 }
 
 void launch_lat_emit(hipStream_t st, const ScrfLayout& lay, ScrfBatchView bv, uint32_t u0, uint32_t n_utts, uint32_t t_max,
-                     const double* S, const double* M, int m_per_frame, int frame_model, const ScrfLatBufs& lb, double beam,
-                     const uint64_t* node_off, uint64_t base, uint64_t cap, scrf_arc* out) {
+                     const ScrfArcSrc& src, const ScrfLatBufs& lb, double beam, const uint64_t* node_off, uint64_t base, uint64_t cap,
+                     scrf_arc* out) {
   if (n_utts == 0) return;
-  hipLaunchKernelGGL(k_lat_emit, dim3(t_max + 1, n_utts), dim3(LAT_NT), 0, st, lay, bv, u0, S, M, m_per_frame, frame_model, lb,
-                     beam, node_off, base, cap, out);
+  hipLaunchKernelGGL(k_lat_emit, dim3(t_max + 1, n_utts), dim3(LAT_NT), 0, st, lay, bv, u0, src.S, src.M, src.m_per_frame, src.frame_model,
+                     lb, beam, node_off, base, cap, out);
 }

@@ -27,19 +27,18 @@
 // the lists a merge draws from, in the order of the tie rule: list(j) = the N sorted costs of predecessor j (nullptr: the
 // single entry 0.0f), w(j) = the arc's weight, tag(j) = the high half of the back pointer
 struct NbBoundary {   // end(t-1, p) -> boundary(t, l) ; frame model: state(t-1, p) -> state(t, l)
-  const float* prev; const double* Mt; const double* Su; int L, N, l, t, frame_model;
+  const float* prev; const ScrfArcView& v; const double* Mt; int N, l, t, frame_model;
   __device__ const float* list(int p) const { return prev + (size_t)p * N; }
-  __device__ float w(int p) const { return frame_model ? scrf_w_frame(Mt, Su, t, L, p, l) : scrf_w_boundary(Mt, L, p, l); }
+  __device__ float w(int p) const { return frame_model ? v.frame(Mt, t, p, l) : v.boundary(Mt, p, l); }
   __device__ uint32_t tag(int p) const { return (uint32_t)p << 16; }
 };
 struct NbEnd {   // j = 0: the start arc (t < D) ; j >= 1: boundary(t - d + 1, l) with d = dmax - j + 1, d descending
-  const float* ring; const double* Su; const float* Wu; uint64_t base; int L, D, N, l, t, dmax;
+  const float* ring; const ScrfArcView& v; uint64_t base; int L, D, N, l, t, dmax;
   __device__ int dur(int j) const { return j == 0 ? t + 1 : dmax - j + 1; }
   __device__ const float* list(int j) const { return j == 0 ? nullptr : ring + ((size_t)((t - dur(j) + 1) % D) * L + l) * N; }
   __device__ float w(int j) const {
     if (j == 0 && t >= D) return INFINITY;   // no start arc of this length
-    const int d = dur(j);
-    return Wu ? Wu[(base + d - 1) * L + l] : scrf_w_segment(Su, base, d, L, l);
+    return v.segment(base, dur(j), l);
   }
   __device__ uint32_t tag(int j) const { return (uint32_t)dur(j) << 16; }
 };
@@ -106,12 +105,10 @@ __global__ __launch_bounds__(64 * NB_WAVES) void k_nbest(ScrfLayout lay, ScrfBat
   const int L = lay.L, D = lay.D, N = (int)nb.N;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, n_waves = blockDim.x >> 6;
   const uint32_t ui = blockIdx.x, u = u0 + ui;
-  const int T = (int)bv.T[u];
-  const uint64_t f_base = bv.frame_off[u] - bv.frame_off[u0];
-  const uint64_t s_base = bv.seg_off[u] - bv.seg_off[u0];
-  const double* Su = S ? S + s_base * L : nullptr;
-  const float* Wu = Wn ? Wn + s_base * L : nullptr;   // float(-1 * score) already formed (segment model)
-  const size_t LL = (size_t)L * L, LN = (size_t)L * N;
+  const ScrfArcView v(ScrfArcSrc{S, Wn, M, m_per_frame, frame_model}, lay, bv, u0, u);
+  const int T = (int)v.T;
+  const uint64_t f_base = v.f_base;
+  const size_t LN = (size_t)L * N;
   float* ring = nbsm + 2 * LN;                                        // [D][L][N] boundary(t', .), slot t' % D
   uint16_t* hd = (uint16_t*)(ring + (size_t)D * LN) + (size_t)wave * nbest_heads(L, D);
   uint32_t* bpb = nb.bp_b + f_base * LN;
@@ -125,14 +122,14 @@ __global__ __launch_bounds__(64 * NB_WAVES) void k_nbest(ScrfLayout lay, ScrfBat
   for (int t = 0; t < T; t++) {
     const float* e_prev = nbsm + (size_t)((t + 1) & 1) * LN;
     float* e_cur = nbsm + (size_t)(t & 1) * LN;
-    const double* Mt = M + (m_per_frame ? (f_base + t) * LL : 0);
+    const double* Mt = v.Mt(t);
     if (frame_model) {
       for (int l = wave; l < L; l += n_waves) {
         float* out = e_cur + (size_t)l * N;
         if (t == 0) {
-          for (int i = lane; i < N; i += 64) out[i] = i == 0 ? 0.0f + scrf_w_segment(Su, 0, 1, L, l) : INFINITY;
+          for (int i = lane; i < N; i += 64) out[i] = i == 0 ? 0.0f + v.start(l) : INFINITY;
         } else {
-          const NbBoundary src{e_prev, Mt, Su, L, N, l, t, 1};
+          const NbBoundary src{e_prev, v, Mt, N, l, t, 1};
           nb_merge(src, L, N, lane, hd, out, bpb + ((size_t)t * L + l) * N);
         }
       }
@@ -141,14 +138,14 @@ __global__ __launch_bounds__(64 * NB_WAVES) void k_nbest(ScrfLayout lay, ScrfBat
     }
     if (t >= 1) {
       for (int l = wave; l < L; l += n_waves) {
-        const NbBoundary src{e_prev, Mt, Su, L, N, l, t, 0};
+        const NbBoundary src{e_prev, v, Mt, N, l, t, 0};
         nb_merge(src, L, N, lane, hd, ring + ((size_t)(t % D) * L + l) * N, bpb + ((size_t)t * L + l) * N);
       }
     }
     __syncthreads();
     const int dmax = t < D ? t : D;
     for (int l = wave; l < L; l += n_waves) {
-      const NbEnd src{ring, Su, Wu, scrf_seg_base(t, D), L, D, N, l, t, dmax};
+      const NbEnd src{ring, v, scrf_seg_base(t, D), L, D, N, l, t, dmax};
       nb_merge(src, 1 + dmax, N, lane, hd, e_cur + (size_t)l * N, bpe + ((size_t)t * L + l) * N);
     }
     __syncthreads();
@@ -269,13 +266,14 @@ size_t nbest_smem_bytes(const ScrfLayout& lay, uint32_t n_best) {
   return sizeof(float) * ((size_t)lay.D + 2) * lay.L * n_best + sizeof(uint16_t) * NB_WAVES * (size_t)nbest_heads(lay.L, lay.D);
 }
 
-void launch_nbest(hipStream_t st, const ScrfLayout& lay, ScrfBatchView bv, uint32_t u0, uint32_t n_utts, const double* S, const float* Wn,
-                  const double* M, int m_per_frame, int frame_model, const ScrfNbestBufs& nb) {
+void launch_nbest(hipStream_t st, const ScrfLayout& lay, ScrfBatchView bv, uint32_t u0, uint32_t n_utts, const ScrfArcSrc& src,
+                  const ScrfNbestBufs& nb) {
   if (n_utts == 0) return;
   const int n_waves = lay.L < NB_WAVES ? (int)lay.L : NB_WAVES;
   const size_t sm = nbest_smem_bytes(lay, nb.N);
   hipFuncSetAttribute((const void*)k_nbest, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sm);
-  hipLaunchKernelGGL(k_nbest, dim3(n_utts), dim3(64 * n_waves), sm, st, lay, bv, u0, S, Wn, M, m_per_frame, frame_model, nb);
+  hipLaunchKernelGGL(k_nbest, dim3(n_utts), dim3(64 * n_waves), sm, st, lay, bv, u0, src.S, src.Wn, src.M, src.m_per_frame,
+                     src.frame_model, nb);
 }
 
 void launch_nbest_count(hipStream_t st, const ScrfLayout& lay, ScrfBatchView bv, uint32_t u0, uint32_t n_utts, int frame_model,

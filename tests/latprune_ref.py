@@ -17,6 +17,7 @@ GPU_SHAPES = [
     dict(L=7, D=10, in_w=5, Ts=[9, 10, 11, 30]),
     dict(L=70, D=2, in_w=3, Ts=[5, 2], lam_scale=0.1),
     dict(L=66, D=4, in_w=69, Ts=[9, 14, 3, 1, 11, 8], lam_scale=0.05),
+    dict(L=4, D=1, in_w=3, Ts=[1, 2, 6], frame_model=True),   # bias-only transitions: the frame model with a single M
 ]
 
 

@@ -70,6 +70,19 @@ def test_pruned_arcs_equal_the_reference_byte_for_byte(si):
     b.close(); eng.close()
 
 
+@pytest.mark.parametrize("si", range(len(SHAPES)))
+def test_the_full_lattice_equals_the_reference_byte_for_byte(si):
+    """scrf_lattice_arcs at every shape of the beam's table: the lattice the beam prunes, from the same enumeration of a
+    node's arcs (the frame model with one transition matrix has no other byte-exact lattice test)"""
+    c = case(si)
+    eng = c.engine(); b = c.batch(eng, with_labels=False)
+    for u, (full, ns, fin, _, _) in enumerate(reference(si)):
+        arcs, gns, gfin = eng.lattice_arcs(b, u)
+        assert (gns, gfin) == (ns, fin), u
+        assert arcs.tobytes() == full.tobytes(), u
+    b.close(); eng.close()
+
+
 def test_chunked_runs_equal_the_one_chunk_run_and_repeat_bit_for_bit():
     si = CHUNKED
     c1 = case(si); cn = case(si, scratch_bytes=1 << 18)

@@ -27,6 +27,7 @@ CASES = [
     (dict(L=70, D=4, in_w=3, Ts=[12], lam_scale=0.1), (8,)),                                     # more lists than lanes
     (dict(L=2, D=66, in_w=2, Ts=[70]), (5,)),                                                    # more durations than lanes
     (dict(L=48, D=25, in_w=39, Ts=[300, 57], lam_scale=0.3), (16,)),                             # U = 2, the config-2 shape
+    (dict(L=4, D=1, in_w=3, Ts=[1, 2, 6], frame_model=True), (1, 8)),                            # frame model, a single M
 ]
 BIG = 6
 CHUNKED = dict(L=66, D=4, in_w=69, Ts=[9, 14, 3, 1, 11, 8], lam_scale=0.05)
