@@ -12,12 +12,14 @@
 
 #include <algorithm>
 #include <cmath>
+#include <functional>
 #include <string>
 #include <unordered_map>
 #include <vector>
 
 #include "scrf_kernels.h"
 #include "scrf_own.h"
+#include "scrf_softnum.h"
 
 // ---------------------------------------------------------------------------------------------
 // RCCL, bound lazily (so that loading the library never drags a second RCCL into a process
@@ -161,6 +163,17 @@ struct Transcripts {
   uint64_t n_tr_calls = 0, n_tr_chunks = 0, n_tr_redone = 0;   // calls; chunks swept (both passes of a redone call); calls redone
 };
 
+// scrf_fb_transcript_batch: the transcripts go into tx as scrf_transcript_batch's do.  bad: label arrays that
+// are all SCRF_LAB_BAD, sized to the largest batch seen -- the training kernels read them where a labelled batch has its
+// labels, and so form the free expectation alone.  log_num [U]: A of every utterance.  ph_off: the host image of phone_off
+// chunk_layout sizes a chunk's per-position sums with.
+struct SoftGrad {
+  DevArray<uint32_t> bad;
+  DevArray<double> log_num;
+  std::vector<uint64_t> ph_off;
+  uint64_t n_calls = 0, n_chunks = 0, n_redone = 0;   // calls; chunks run (both passes of a redone call); calls redone
+};
+
 // HIP-event times of the last timed call: per phase (scrf_last_timing) and per kernel (scrf_kernel_timing)
 struct KTime { std::string name; double ms; uint32_t n; };
 struct Timing {
@@ -248,6 +261,7 @@ struct __attribute__((visibility("hidden"))) scrf_engine_s {   // (hidden: its c
   PrunedLattice lp;
   NBestResult nb;
   Transcripts tx;
+  SoftGrad soft;
   std::string err;
   Timing tm;
   scrf_nccl_comm comm = nullptr;
@@ -1115,6 +1129,9 @@ struct ChunkBufs {
   uint64_t* lat_node_off = nullptr; // [nodes + 1]
   uint16_t* al_bp = nullptr;        // forced alignment: sum of T * K back pointers over the chunk's transcripts that fit
   double *tr_aB = nullptr, *tr_bE = nullptr;   // transcript scoring: the same cells, forward (segment start) and backward (segment end) sums
+  // soft-alignment gradient: the state numerators [nseg][L], the cells' forward sums at a segment's end / backward sums at
+  // its start, and (bias-only transitions) the per-position sums of the transition numerators
+  double *sn_G = nullptr, *sn_aE = nullptr, *sn_bB = nullptr, *sn_adv = nullptr, *sn_stay = nullptr, *sn_tab = nullptr;
   ScrfNbestBufs nb = {0, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};   // N-best: back pointers, final lists, offsets
   bool lamT_ready = false;   // sparse maps: h->d_lamT already re-laid for this call (scrf_fb_batch: once, before the lanes fork)
 };
@@ -1132,7 +1149,7 @@ static ScrfArcSrc arc_src(scrf_handle h, const ChunkBufs& cb, bool fast = false)
 struct Need {
   bool fb = false, post = false, beta = false, vit = false;
   bool fused = false, vitfast = false, la = false, hybrid = false;   // the batch's form (set_batch_form, decode_chunks)
-  bool ponly = false, plog = false, lat = false, align = false, trans = false;
+  bool ponly = false, plog = false, lat = false, align = false, trans = false, soft = false;
   uint32_t nbest = 0;   // scrf_nbest_batch: the list length
   // one constructor per kind of pass, so that no call site depends on the order of the fields
   static Need scores() { return Need(); }                                              // windows and scores only
@@ -1141,12 +1158,15 @@ struct Need {
   static Need training() { Need n; n.fb = n.post = true; return n; }
   static Need posterior(bool fast) { Need n = recursion(); n.ponly = true; n.plog = !fast; return n; }
   static Need transcript(bool fast) { Need n = posterior(fast); n.trans = true; return n; }
+  static Need soft_training() { Need n = training(); n.trans = n.soft = true; return n; }   // scrf_fb_transcript_batch
   static Need viterbi() { Need n; n.vit = true; return n; }
   static Need lattice() { Need n; n.lat = true; return n; }
   static Need alignment() { Need n; n.align = true; return n; }
   static Need nbest_of(uint32_t n_best) { Need n; n.nbest = n_best; return n; }
 };
 // trans (scrf_transcript_batch): two doubles per (frame, transcript position) cell of the chunk
+// soft (scrf_fb_transcript_batch): two more per cell, a double per (window row, label), and with bias-only transitions two
+// per transcript position and an [L][L] table per utterance
 // nbest (scrf_nbest_batch): two 32-bit back pointers per (frame, label, rank), and per (utterance, rank) the final list and
 // the offsets of the backtrace
 // align (scrf_align_batch): the back pointers of the chunk's (frame, transcript position) cells
@@ -1352,6 +1372,16 @@ static void chunk_layout(scrf_handle h, scrf_batch b, uint32_t u0, uint32_t u1, 
   if (nd.trans) {
     cb->tr_aB = a.take<double>(h->tx.cell_off[u1] - h->tx.cell_off[u0]);
     cb->tr_bE = a.take<double>(h->tx.cell_off[u1] - h->tx.cell_off[u0]);
+  }
+  if (nd.soft) {
+    cb->sn_G = a.take<double>(nseg * l.L);
+    cb->sn_aE = a.take<double>(h->tx.cell_off[u1] - h->tx.cell_off[u0]);
+    cb->sn_bB = a.take<double>(h->tx.cell_off[u1] - h->tx.cell_off[u0]);
+    if (!l.use_tf) {
+      cb->sn_adv = a.take<double>(h->soft.ph_off[u1] - h->soft.ph_off[u0]);
+      cb->sn_stay = a.take<double>(h->soft.ph_off[u1] - h->soft.ph_off[u0]);
+      cb->sn_tab = a.take<double>(nutt * LL);
+    }
   }
 }
 
@@ -1649,6 +1679,10 @@ struct DpOpts {
   bool post = false;    // + posteriors, numerators and xi: leaves R = Y - gamma in cb.R
   bool ponly = false;   // the recursion alone: the caller's posterior-output kernels take it from there
   FbRoute route;        // training pass: side sends the linear-domain path's check kernels to the second stream
+  // Launches that read the chunk's scores beside the pass (scrf_fb_transcript_batch's numerators).  run_dp queues them at the
+  // last point at which the scores exist: on the linear-domain path between the recursion and the posterior walk, which
+  // overwrites them with R (dp_wave_lin); on every other path, where S stays beside R = AD, behind the recursion's launches.
+  std::function<int()> reads_scores;
   static DpOpts training(const FbRoute& rt) { DpOpts o; o.post = true; o.route = rt; return o; }
   static DpOpts recursion_only() { DpOpts o; o.ponly = true; return o; }
 };
@@ -1719,6 +1753,7 @@ static int dp_wave_lin(scrf_handle h, scrf_batch b, uint32_t u0, uint32_t u1, Ch
   }
   *nl += 1;
   if (o.ponly) return SCRF_OK;
+  if (o.reads_scores) RCCHK(o.reads_scores());   // the walk below overwrites the scores
   if (cb.fused) {
     // posterior pass and the per-frame sums of R in one walk (R is not read back for Z)
     if (l.L > 64) HIPCHK(h, hipMemsetAsync(cb.mass_s, 0, sizeof(double) * nfr, cb.st));   // summed over the 64-output groups
@@ -1791,6 +1826,7 @@ static int run_dp(scrf_handle h, scrf_batch b, uint32_t u0, uint32_t u1, ChunkBu
     }
     RCCHK(cb.lin ? dp_wave_lin(h, b, u0, u1, cb, o, &nl) : dp_wave_log(h, b, u0, u1, cb, o.post, &nl));
   }
+  if (o.reads_scores && !cb.lin) RCCHK(o.reads_scores());   // cb.lin: dp_wave_lin has queued them before its posterior walk
   if (nl_out) *nl_out = nl;
   HIPCHK(h, hipGetLastError());
   return SCRF_OK;
@@ -3345,26 +3381,11 @@ static int transcript_chunk(scrf_handle h, scrf_batch b, const uint64_t* phone_o
   return SCRF_OK;
 }
 
-extern "C" int scrf_transcript_batch(scrf_handle h, scrf_batch b, const uint32_t* phones, const uint64_t* phone_off, int mode,
-                                     double* log_num, double* zx, double* frame_post, double* end_post,
-                                     const uint32_t* seg_labels, const uint64_t* lab_off, double* seg_post) {
-  if (!h || !b || !phone_off) return SCRF_ERR_INVALID;
-  const char* fn = "scrf_transcript_batch";
-  RCCHK(model_ok(h, fn, "posterior output"));
+// The inverted lists of a call's (checked) transcripts into h->tx.inv_h, [inv_pos (sum K) | inv_off (U x (L + 1))]: per
+// utterance its positions sorted by label (a counting sort: ascending inside a label).  Returns the number of entries.
+static uint64_t inverted_lists(scrf_handle h, uint32_t U, const uint32_t* phones, const uint64_t* phone_off) {
   const ScrfLayout& l = h->lay;
-  if (l.D > 0x7fff) return fail(h, SCRF_ERR_INVALID, "%s: maximum duration %u is not served (at most %u, as scrf_align_batch)", fn, l.D, 0x7fffu);
-  if (mode != SCRF_ALIGN_ONE && mode != SCRF_ALIGN_RUNS)
-    return fail(h, SCRF_ERR_INVALID, "%s: unknown mode %d (SCRF_ALIGN_ONE = 0, SCRF_ALIGN_RUNS = 1)", fn, mode);
-  const uint32_t U = b->U;
-  const uint64_t NP = phone_off[U], nF = b->frame_off[U];
-  // the checks of every transcript and the cells before each utterance; 128 bytes of LDS go to the 16 per-wavefront parts of
-  // end[t].  Then the inverted lists: per utterance its positions sorted by label (a counting sort: ascending inside a label)
-  RCCHK(check_transcripts(h, b, fn, phones, phone_off, mode, true, 8, 128, [&](uint64_t K) { return transcript_smem_bytes(l, K); },
-                          &h->tx.cell_off));
-  std::vector<uint32_t> q;   // [3][nq]: utterance, end frame, label value
-  uint64_t nq = 0;
-  RCCHK(seg_queries(h, b, fn, seg_labels, lab_off, seg_post != nullptr, &q, &nq));
-  const uint64_t n_inv = NP + (uint64_t)U * (l.L + 1);
+  const uint64_t NP = phone_off[U], n_inv = NP + (uint64_t)U * (l.L + 1);
   h->tx.inv_h.assign(n_inv, 0);
   for (uint32_t u = 0; u < U; u++) {
     const uint64_t K = phone_off[u + 1] - phone_off[u];
@@ -3377,6 +3398,29 @@ extern "C" int scrf_transcript_batch(scrf_handle h, scrf_batch b, const uint32_t
     for (uint32_t c = l.L; c >= 1; c--) ioff[c] = ioff[c - 1];
     ioff[0] = 0;
   }
+  return n_inv;
+}
+
+extern "C" int scrf_transcript_batch(scrf_handle h, scrf_batch b, const uint32_t* phones, const uint64_t* phone_off, int mode,
+                                     double* log_num, double* zx, double* frame_post, double* end_post,
+                                     const uint32_t* seg_labels, const uint64_t* lab_off, double* seg_post) {
+  if (!h || !b || !phone_off) return SCRF_ERR_INVALID;
+  const char* fn = "scrf_transcript_batch";
+  RCCHK(model_ok(h, fn, "posterior output"));
+  const ScrfLayout& l = h->lay;
+  if (l.D > 0x7fff) return fail(h, SCRF_ERR_INVALID, "%s: maximum duration %u is not served (at most %u, as scrf_align_batch)", fn, l.D, 0x7fffu);
+  if (mode != SCRF_ALIGN_ONE && mode != SCRF_ALIGN_RUNS)
+    return fail(h, SCRF_ERR_INVALID, "%s: unknown mode %d (SCRF_ALIGN_ONE = 0, SCRF_ALIGN_RUNS = 1)", fn, mode);
+  const uint32_t U = b->U;
+  const uint64_t nF = b->frame_off[U];
+  // the checks of every transcript and the cells before each utterance; 128 bytes of LDS go to the 16 per-wavefront parts of
+  // end[t].  Then the inverted lists (inverted_lists)
+  RCCHK(check_transcripts(h, b, fn, phones, phone_off, mode, true, 8, 128, [&](uint64_t K) { return transcript_smem_bytes(l, K); },
+                          &h->tx.cell_off));
+  std::vector<uint32_t> q;   // [3][nq]: utterance, end frame, label value
+  uint64_t nq = 0;
+  RCCHK(seg_queries(h, b, fn, seg_labels, lab_off, seg_post != nullptr, &q, &nq));
+  const uint64_t n_inv = inverted_lists(h, U, phones, phone_off);
   HIPCHK(h, hipSetDevice(h->device));
   TransOut to;
   RCCHK(reserve_drained(h, h->tx.inv, n_inv));
@@ -3410,6 +3454,154 @@ extern "C" int scrf_transcript_stats(scrf_handle h, uint64_t* n_calls, uint64_t*
   if (n_calls) *n_calls = h->tx.n_tr_calls;
   if (n_chunks) *n_chunks = h->tx.n_tr_chunks;
   if (n_redone) *n_redone = h->tx.n_tr_redone;
+  return SCRF_OK;
+}
+
+// ---------------------------------------------------------------------------------------------
+// training from transcripts: the training pass over label arrays that are all SCRF_LAB_BAD, which leaves
+// R = -gamma and XI = -xi (or the A^T B factors); the transcript sweep and the numerator kernels between the recursion and
+// the posterior walk; R += G and the transition numerators behind it; then the count and reduce phases as they are.  One
+// lane, no side route, no all-reduce overlap.
+// ---------------------------------------------------------------------------------------------
+// The batch reads as one whose every label is SCRF_LAB_BAD for the lifetime of this guard.  (k_xi_full and the posterior
+// walks read next_lab where a label is present or not, so a null pointer will not do.)  The label pointers of the caller's
+// batch are swapped and put back, because run_dp and the kernels' launchers take them from the batch (b->view(),
+// b->d_next_lab) at a dozen places: like every call on a handle, the call is not to run beside another call on the same
+// handle or batch (scrf_abi.h says so for this entry point).
+struct AllBadLabels {
+  scrf_batch b;
+  uint32_t *lab, *next;
+  AllBadLabels(scrf_batch b_, uint32_t* bad) : b(b_), lab(b_->d_labels), next(b_->d_next_lab) { b->d_labels = b->d_next_lab = bad; }
+  ~AllBadLabels() { b->d_labels = lab; b->d_next_lab = next; }
+  AllBadLabels(const AllBadLabels&) = delete;
+  AllBadLabels& operator=(const AllBadLabels&) = delete;
+};
+
+static int soft_chunk(scrf_handle h, scrf_batch b, const uint64_t* phone_off, int mode, uint32_t u0, uint32_t u1, bool last, const Need& nd) {
+  const ScrfLayout& l = h->lay;
+  const uint32_t U = b->U, nutt = u1 - u0;
+  const uint64_t nseg = b->seg_off[u1] - b->seg_off[u0];
+  ChunkBufs cb;
+  RCCHK(score_chunk(h, b, u0, u1, nd, &cb, SCORE_PASS));
+  cb.grad = h->d_stage;
+  cb.sums = h->d_sums_stage;
+  FbRoute rt;
+  rt.last = last;
+  ScrfBatchView bv = b->view();
+  uint64_t k_max = 0, cells_max = 0;
+  for (uint32_t u = u0; u < u1; u++) {
+    k_max = std::max(k_max, phone_off[u + 1] - phone_off[u]);
+    cells_max = std::max(cells_max, h->tx.cell_off[u + 1] - h->tx.cell_off[u]);
+  }
+  const uint32_t t_max = longest_utt(b, u0, u1);
+  const ScrfTransArgs ta{h->tx.ph, h->tx.off, h->tx.off + (U + 1), h->tx.inv, h->tx.inv + phone_off[U], cb.tr_aB, cb.tr_bE,
+                         mode, cb.lin ? 1 : 0, 1};
+  const ScrfSoftArgs sa{h->soft.log_num, b->d_status, cb.sn_aE, cb.sn_bB, cb.sn_G, cb.sn_adv, cb.sn_stay, cb.sn_tab};
+  h->soft.n_chunks++;
+  uint32_t nl = 0;
+  // everything that reads the scores: the sweep (A, aB, bE), then G and the aE / bB cells
+  auto numerators = [&]() -> int {
+    KT_RUN("k_transcript", cb.st, launch_transcript(cb.st, l, bv, u0, nutt, k_max, cb.S, cb.smax, cb.M, cb.m_per_frame, ta, b->d_status,
+                                                    h->soft.log_num, nullptr, nullptr));
+    KT_RUN("k_soft_state", cb.st, launch_soft_state(cb.st, l, bv, u0, nutt, t_max, cb.S, cb.smax, ta, sa));
+    KT_RUN("k_soft_trans", cb.st, launch_soft_trans(cb.st, l, bv, u0, nutt, cells_max, cb.S, cb.smax, ta, sa));
+    nl += 3;
+    HIPCHK(h, hipGetLastError());
+    return SCRF_OK;
+  };
+  {
+    PhaseTimer tm(h, PH_FB, cb.st);
+    DpOpts o = DpOpts::training(rt);
+    o.reads_scores = numerators;   // run_dp queues them while the scores exist (DpOpts)
+    uint32_t nl_dp = 0;
+    RCCHK(run_dp(h, b, u0, u1, cb, o, &nl_dp));
+    KT_RUN("k_soft_add_r", cb.st, launch_soft_add_r(cb.st, cb.R, cb.sn_G, nseg * l.L));
+    if (l.use_tf) KT_RUN("k_soft_add_xi", cb.st, launch_soft_add_xi(cb.st, l, bv, u0, nutt, t_max, cb.M, ta, sa, cb.XI));
+    else KT_RUN("k_soft_trans_table", cb.st, launch_soft_trans_table(cb.st, l, bv, u0, nutt, k_max, cb.M, ta, sa, cb.grad));
+    cb.z_ready = false;   // the fused form's Z was summed from R before the numerators went in: k_lin_z forms it again
+    // the numerator of the batch sums (k_numer_reduce / k_fb left 0: no label was observed)
+    HIPCHK(h, hipMemcpyAsync(b->d_numer + u0, h->soft.log_num.get() + u0, sizeof(double) * nutt, hipMemcpyDeviceToDevice, cb.st));
+    tm.stop(nl + nl_dp + 2);
+  }
+  if (last) RCCHK(queue_status(h, b));
+  ChunkCounts cc;
+  RCCHK(fb_count(h, b, u0, u1, cb, rt, &cc));
+  RCCHK(fb_reduce(h, b, u0, u1, cb, rt, cc));
+  HIPCHK(h, hipGetLastError());
+  return SCRF_OK;
+}
+
+static int soft_run(scrf_handle h, scrf_batch b, const uint64_t* phone_off, int mode, int latch[2]) {
+  const ScrfLayout& l = h->lay;
+  RCCHK(fb_begin(h, b));
+  Need nd = Need::soft_training();
+  set_batch_form(h, b, &nd);
+  nd.la = false;   // the six-block Z of the linear-average form exists only inside k_post_z: SCRF_PREC_FASTLIN runs as FAST
+  if (!l.use_tf) ensure_m0(h, h->stream);
+  if (sparse(h)) relay_sparse_lambda(h, h->stream);
+  for (uint32_t u0 = 0; u0 < b->U;) {
+    const uint32_t u1 = plan_chunk(h, b, u0, nd);
+    RCCHK(soft_chunk(h, b, phone_off, mode, u0, u1, u1 == b->U, nd));
+    u0 = u1;
+  }
+  return fb_commit(h, latch);   // no observed transition counts to add (launch_add_trans_counts): there are no labels
+}
+
+extern "C" int scrf_fb_transcript_batch(scrf_handle h, scrf_batch b, const uint32_t* phones, const uint64_t* phone_off, int mode,
+                                        double* log_num, double* zx) {
+  if (!h || !b || !phone_off) return SCRF_ERR_INVALID;
+  const char* fn = "scrf_fb_transcript_batch";
+  RCCHK(model_ok(h, fn, "training from transcripts"));
+  const ScrfLayout& l = h->lay;
+  if (l.D > 0x7fff) return fail(h, SCRF_ERR_INVALID, "%s: maximum duration %u is not served (at most %u, as scrf_align_batch)", fn, l.D, 0x7fffu);
+  if (mode != SCRF_ALIGN_ONE && mode != SCRF_ALIGN_RUNS)
+    return fail(h, SCRF_ERR_INVALID, "%s: unknown mode %d (SCRF_ALIGN_ONE = 0, SCRF_ALIGN_RUNS = 1)", fn, mode);
+  const uint32_t U = b->U;
+  const uint64_t nF = b->frame_off[U];
+  RCCHK(check_transcripts(h, b, fn, phones, phone_off, mode, true, 8, 128, [&](uint64_t K) { return transcript_smem_bytes(l, K); },
+                          &h->tx.cell_off));
+  // a transcript no path realises has no numerator: in training that is an error, not an empty sum
+  for (uint32_t u = 0; u < U; u++)
+    if (!scrf_align_feasible(b->T[u], phone_off[u + 1] - phone_off[u], l.D, mode))
+      return fail(h, SCRF_ERR_INVALID, "%s: utterance %u's transcript of %llu phones does not fit its %u frames (%s, maximum duration %u)", fn, u,
+                  (unsigned long long)(phone_off[u + 1] - phone_off[u]), b->T[u], mode == SCRF_ALIGN_ONE ? "SCRF_ALIGN_ONE" : "SCRF_ALIGN_RUNS", l.D);
+  h->soft.ph_off.assign(phone_off, phone_off + U + 1);
+  const uint64_t n_inv = inverted_lists(h, U, phones, phone_off);
+  HIPCHK(h, hipSetDevice(h->device));
+  RCCHK(reserve_drained(h, h->tx.inv, n_inv));
+  RCCHK(reserve_drained(h, h->soft.log_num, U));
+  if (nF > h->soft.bad.cap()) {
+    RCCHK(reserve_drained(h, h->soft.bad, nF));
+    HIPCHK(h, hipMemsetAsync(h->soft.bad, 0xff, sizeof(uint32_t) * h->soft.bad.cap(), h->stream));
+  }
+  if (n_inv) HIPCHK(h, hipMemcpyAsync(h->tx.inv, h->tx.inv_h.data(), sizeof(uint32_t) * n_inv, hipMemcpyHostToDevice, h->stream));
+  RCCHK(upload_transcripts(h, U, phones, phone_off, h->tx.cell_off.data()));
+  CallTimer call(h);
+  h->soft.n_calls++;
+  const uint64_t fb0 = h->n_lin_fallback;
+  int latch[2] = {0, 0};
+  int rc;
+  {
+    AllBadLabels unlabelled(b, h->soft.bad);
+    rc = run_with_redo(h, latch, [&] { return soft_run(h, b, phone_off, mode, latch); });
+  }
+  if (h->n_lin_fallback != fb0) h->soft.n_redone++;
+  if (rc != SCRF_OK) return rc;
+  call.stop();
+  if (latch[0] != 0) return fail(h, latch[0], "%s: utterance %d: %s", fn, latch[1], status_text(latch[0]));
+  if (log_num || zx) {
+    if (log_num) HIPCHK(h, hipMemcpyAsync(log_num, h->soft.log_num, sizeof(double) * U, hipMemcpyDeviceToHost, h->stream));
+    if (zx) HIPCHK(h, hipMemcpyAsync(zx, b->d_zx, sizeof(double) * U, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+  }
+  return SCRF_OK;
+}
+
+extern "C" int scrf_soft_stats(scrf_handle h, uint64_t* n_calls, uint64_t* n_chunks, uint64_t* n_redone) {
+  if (!h) return SCRF_ERR_INVALID;
+  if (n_calls) *n_calls = h->soft.n_calls;
+  if (n_chunks) *n_chunks = h->soft.n_chunks;
+  if (n_redone) *n_redone = h->soft.n_redone;
   return SCRF_OK;
 }
 

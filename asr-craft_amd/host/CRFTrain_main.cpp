@@ -12,6 +12,10 @@
 //     hands the RCCL unique id to the others through <out_weight_file>.rccl_id and is the only writer of
 //     weight files, markers and progress lines.  crf_force_comm=1 initialises the communicator for one rank.
 // crf_precision=exact|fast|fastlin|fast32 selects the arithmetic of the training contractions (default fast).
+// crf_objective_function=softexpf [crf_align_repeat=1|0] trains on each utterance's phone TRANSCRIPT (read from its labels,
+// durations dropped) instead of its segmentation, with crf_train_method=sg in one process.  crf_align_repeat
+// means what it means in CRFFstDecode: 1 (default) equal neighbours collapse and every phone takes one or more segments, 0
+// one segment per phone.
 #include "cli_common.h"
 
 int main(int argc, char** argv) {
@@ -25,6 +29,16 @@ int main(int argc, char** argv) {
     if (!a.has("out_weight_file")) { std::cerr << "out_weight_file is required" << std::endl; return 1; }
     const std::string method = a.str("crf_train_method", "sg");
     if (method != "sg" && method != "lbfgs") { std::cerr << "crf_train_method=" << method << " is not built (sg|lbfgs)" << std::endl; return 1; }
+    const std::string ofn = a.str("crf_objective_function", "expf");
+    const bool soft = ofn == "softexpf";
+    if (soft) {   // refused before anything is read or written
+      if (!crf_amd_soft_objective_linked()) { std::cerr << CRF_AMD_SOFT_NOT_LINKED << std::endl; return 1; }
+      if (world > 1) { std::cerr << "crf_objective_function=softexpf is built for one process (WORLD_SIZE=" << world << "): the distributed accumulator runs the expf pass only" << std::endl; return 1; }
+      if (method == "lbfgs") { std::cerr << "crf_objective_function=softexpf is built for crf_train_method=sg (the full-batch accumulator of lbfgs runs the expf pass only)" << std::endl; return 1; }
+    }
+    if (a.has("crf_align_repeat") && !soft) { std::cerr << "crf_align_repeat needs crf_objective_function=softexpf" << std::endl; return 1; }
+    const long align_repeat = a.num("crf_align_repeat", 1);
+    if (align_repeat != 0 && align_repeat != 1) { std::cerr << "crf_align_repeat=" << align_repeat << " (1|0)" << std::endl; return 1; }
     CliModel m;
     m.D = (uint32_t)a.num("label_maximum_duration", 1);
     m.L = (uint32_t)a.num("crf_label_size", 0);
@@ -77,6 +91,7 @@ int main(int argc, char** argv) {
     if (rank == 0) std::cout << "FEATURES: " << my_crf.getLambdaLen() << std::endl;
     my_crf.setDevice((int)a.num("crf_device", world > 1 ? local_rank : 0));
     my_crf.setTrainPrecision(parse_precision(a));
+    my_crf.setSoftAlignMode(align_repeat ? SCRF_ALIGN_RUNS : SCRF_ALIGN_ONE);
     my_crf.setTrainingOnly(true);   // this process never builds lattices: the n-state frame model may take the dense kernels
     if (rank == 0 && m.mtype == STDFRAME && m.fmap.numStates > 1 && parse_precision(a) != SCRF_PREC_EXACT)
       std::cout << "NOTE: crf_states=" << m.fmap.numStates << " on the frame model trains through the dense kernels (as the n-state segmental model with maximum duration 1: the same function and weight layout); crf_precision=exact keeps the reference-order n-state kernels" << std::endl;
@@ -103,7 +118,7 @@ int main(int argc, char** argv) {
       ((CRF_LBFGSTrainer*)my_trainer)->setObjectiveFunction(EXPF);
     } else {
       my_trainer = new CRF_SGTrainer(&my_crf, &str1, &wf[0]);
-      ((CRF_SGTrainer*)my_trainer)->setObjectiveFunction(EXPF);
+      ((CRF_SGTrainer*)my_trainer)->setObjectiveFunction(soft ? EXPFSOFT : EXPF);
       ((CRF_SGTrainer*)my_trainer)->setUseAdagrad((double)a.num("crf_use_adagrad", 0));
       ((CRF_SGTrainer*)my_trainer)->setEta(a.real("crf_adagrad_eta", 1.0));
       ((CRF_SGTrainer*)my_trainer)->setNThreads((int)threads);

@@ -70,7 +70,8 @@ inline void refuse_unbuilt_flags(const Args& a, uint32_t D) {
   if (we != 1 && we != (long)D) die("window_extent must be 1 or label_maximum_duration");
   if (a.num("hardtarget_window_offset", 0) != 0) die("hardtarget_window_offset must be 0");
   if (a.num("use_broken_class_label", 0) != 0) die("use_broken_class_label: broken-class labels are not built");
-  if (a.has("crf_objective_function") && a.str("crf_objective_function") != "expf") die("crf_objective_function=" + a.str("crf_objective_function") + " is not built (expf only)");
+  if (a.has("crf_objective_function") && a.str("crf_objective_function") != "expf" && a.str("crf_objective_function") != "softexpf")
+    die("crf_objective_function=" + a.str("crf_objective_function") + " is not built (expf only; CRFTrain also takes softexpf)");
   if (a.has("crf_featuremap_file")) die("crf_featuremap_file: file-defined feature maps are not built");
 }
 

@@ -739,9 +739,29 @@ const uint32_t* crf_amd::StreamBatch::labels(size_t u) const { return held->utts
 // ------------------------------------------------------------------------------------------
 // CRF_GradBuilder
 // ------------------------------------------------------------------------------------------
+crf_amd_soft_fb_fn crf_amd_soft_fb = nullptr;   // filled by crf_softgrad.cpp where that unit is linked
+
+// EXPF, or EXPFSOFT where its unit is linked; `who` names the refusing class
+static void check_objective(objfunctype ofunc, const char* who) {
+  if (ofunc == EXPFSOFT && !crf_amd_soft_objective_linked()) throw runtime_error(CRF_AMD_SOFT_NOT_LINKED);
+  if (ofunc != EXPF && ofunc != EXPFSOFT)
+    throw runtime_error(string(who) + ": only the EXPF and EXPFSOFT objectives are built (the reference disables the others, CRF_GradBuilder.cpp:130-135)");
+}
+
+// the soft objective's device pass on a batch made of `utts`, where the EXPF classes call scrf_fb_batch
+static void soft_fb_batch(crf_amd::Engine* e, CRF_Model* crf, scrf_batch b, const std::vector<HeldUtt>& utts, double* log_num, double* zx,
+                          const char* what) {
+  if (!crf_amd_soft_objective_linked()) throw runtime_error(CRF_AMD_SOFT_NOT_LINKED);
+  std::vector<const uint32_t*> labs(utts.size());
+  std::vector<uint32_t> T(utts.size());
+  for (size_t i = 0; i < utts.size(); i++) { labs[i] = utts[i].u.labels; T[i] = utts[i].u.T; }
+  const uint32_t L = crf->getNActualLabs() ? crf->getNActualLabs() : crf->getNLabs();
+  e->check(crf_amd_soft_fb(e->h, b, labs.data(), T.data(), (uint32_t)utts.size(), L, crf->softAlignMode(), log_num, zx), what);
+}
+
 CRF_GradBuilder* CRF_GradBuilder::create(CRF_Model* crf, objfunctype ofunc) {
-  if (ofunc != EXPF) throw runtime_error("CRF_GradBuilder::create: only the EXPF objective is built (the reference disables the others)");
-  return new CRF_GradBuilder(crf);
+  check_objective(ofunc, "CRF_GradBuilder::create");
+  return new CRF_GradBuilder(crf, ofunc);
 }
 
 double CRF_GradBuilder::buildGradient(CRF_FeatureStream* ftr_strm, double* grad, double* Zx_out) {
@@ -753,7 +773,8 @@ double CRF_GradBuilder::buildGradient(CRF_FeatureStream* ftr_strm, double* grad,
   make_batch(e, ftr_strm, utts, &g);
   e->check(scrf_zero_grad(e->h), "buildGradient");
   double numer = 0, zx = 0;
-  e->check(scrf_fb_batch(e->h, g.b, &numer, &zx), "CRF_NewGradBuilder_StdSeg_NoDur_NoTrans::buildGradient()");
+  if (objective == EXPFSOFT) soft_fb_batch(e, crf, g.b, utts, &numer, &zx, "CRF_NewGradBuilderSoft::buildGradient()");
+  else e->check(scrf_fb_batch(e->h, g.b, &numer, &zx), "CRF_NewGradBuilder_StdSeg_NoDur_NoTrans::buildGradient()");
   std::vector<double> gd(e->lambda_len);
   e->check(scrf_get_grad(e->h, gd.data(), e->lambda_len), "buildGradient");
   for (uint32_t i = 0; i < e->lambda_len; i++) grad[i] += gd[i];
@@ -787,7 +808,8 @@ CRF_Minibatch_GradAccumulator::CRF_Minibatch_GradAccumulator(CRF_Model* myCrf, C
 }
 
 void CRF_Minibatch_GradAccumulator::setObjectiveFunction(objfunctype ofunc) {
-  if (ofunc != EXPF) throw runtime_error("CRF_Minibatch_GradAccumulator: only the EXPF objective is built (the reference disables the others, CRF_GradBuilder.cpp:130-135)");
+  check_objective(ofunc, "CRF_Minibatch_GradAccumulator");
+  objective = ofunc;
 }
 
 void CRF_Minibatch_GradAccumulator::setMinibatch(QNUInt32 mb) {
@@ -849,6 +871,8 @@ double CRF_Minibatch_GradAccumulator::accumulate(double* grad, double* Zx_out, Q
   const bool dist = crf->distributed();
   if (dist && (QNUInt32)crf->distWorld() != N)
     throw runtime_error("CRF_Minibatch_GradAccumulator: " + std::to_string(N) + " streams but " + std::to_string(crf->distWorld()) + " ranks (threads must equal WORLD_SIZE)");
+  if (dist && objective == EXPFSOFT)
+    throw runtime_error("CRF_Minibatch_GradAccumulator: the soft objective is built for one process (the fused batch + all-reduce call runs the EXPF pass)");
   string local_failure;   // distributed: a rank that fails must still meet its peers in the collective (below)
   try {   // (inside the net as well: a device error here would otherwise skip the collective the peers are entering)
     if (grad && !dist) for (QNUInt32 i = 0; i < n; i++) grad[i] = 0.0;
@@ -892,7 +916,11 @@ double CRF_Minibatch_GradAccumulator::accumulate(double* grad, double* Zx_out, Q
       if (fb_rc != SCRF_OK) local_failure = string("CRF_Minibatch_GradAccumulator::accumulateGradient() caught exception: ") + scrf_last_error(e->h);
       continue;
     }
-    { ClockScope cs(2); e->check(scrf_fb_batch(e->h, g.b, nullptr, nullptr), "CRF_Minibatch_GradAccumulator::accumulateGradient()"); }
+    {
+      ClockScope cs(2);
+      if (objective == EXPFSOFT) soft_fb_batch(e, crf, g.b, utts, nullptr, nullptr, "CRF_Minibatch_GradAccumulator::accumulateGradient()");
+      else e->check(scrf_fb_batch(e->h, g.b, nullptr, nullptr), "CRF_Minibatch_GradAccumulator::accumulateGradient()");
+    }
     if (grad && !dist) {   // per-stream gradient and sums to the host (they restart with every scrf_zero_grad)
       double sums[3] = {0, 0, 0};
       e->check(scrf_get_batch_sums(e->h, sums), "accumulateGradient");
@@ -994,7 +1022,7 @@ CRF_Trainer::CRF_Trainer(CRF_Model* crf_in, CRF_FeatureStreamManager* ftr_str_mg
     : crf_ptr(crf_in), ftr_strm_mgr(ftr_str_mgr), weight_fname(wt_fname ? wt_fname : ""), weight_dir(dir_of(weight_fname)) {}
 void CRF_Trainer::train() { throw runtime_error("CRF_Trainer::train: abstract trainer"); }
 void CRF_Trainer::setObjectiveFunction(objfunctype ofunc) {
-  if (ofunc != EXPF) throw runtime_error("CRF_Trainer::setObjectiveFunction: only the EXPF objective is built (the reference disables the others, CRF_GradBuilder.cpp:130-135)");
+  check_objective(ofunc, "CRF_Trainer::setObjectiveFunction");
   objective = ofunc;
 }
 bool CRF_Trainer::touchDoneFileIter(int iter) { return touch(weight_dir + "/.done.train.i" + std::to_string(iter)); }
@@ -1041,6 +1069,7 @@ void CRF_SGTrainer::sgtrainMinibatch() {
                    : new CRF_Minibatch_GradAccumulator(crf_ptr, own_streams));
   gaccum->setMinibatch((QNUInt32)minibatch);
   gaccum->setUttReport((int)uttRpt);
+  gaccum->setObjectiveFunction(objective);
   // one process: the sums of a minibatch are read one minibatch later (SCRF_ASYNC_SUMS=0: at once, as before round 4)
   const bool defer = !crf_ptr->distributed() && !(getenv("SCRF_ASYNC_SUMS") && atoi(getenv("SCRF_ASYNC_SUMS")) == 0);
   gaccum->setDeferSums(defer);
@@ -1148,7 +1177,7 @@ void CRF_SGTrainer::sgtrainMinibatch() {
 // CRF_GradAccumulator (full batch) / CRF_LBFGSTrainer
 // ------------------------------------------------------------------------------------------
 void CRF_GradAccumulator::setObjectiveFunction(objfunctype ofunc) {
-  if (ofunc != EXPF) throw runtime_error("CRF_GradAccumulator: only the EXPF objective is built");
+  if (ofunc != EXPF) throw runtime_error("CRF_GradAccumulator: only the EXPF objective is built (the full-batch accumulator of crf_train_method=lbfgs does not take the soft objective)");
 }
 
 double CRF_GradAccumulator::accumulateGradient(CRF_FeatureStreamManager* mgr, int nStreams, double* grad, QNUInt32* uttCount) {

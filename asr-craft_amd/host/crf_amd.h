@@ -131,6 +131,10 @@ class CRF_Model {
   // and decoding keep the n-state kernels (their arc order is the frame lattice builder's), hence "training only".
   void setTrainingOnly(bool on) { training_only = on; }
   bool trainingOnly() const { return training_only; }
+  // the soft objective (EXPFSOFT): how a transcript is read, SCRF_ALIGN_RUNS (default: equal neighbours collapse, a phone takes
+  // one or more segments) or SCRF_ALIGN_ONE (crf_align_repeat=0: one segment per phone)
+  void setSoftAlignMode(int mode) { soft_mode = mode; }
+  int softAlignMode() const { return soft_mode; }
   // One process per GPU (RANK / WORLD_SIZE of the launcher): rank r is the reference's stream (thread) r.
   // The RCCL communicator is created together with the engine; its 128-byte unique id travels from rank 0
   // to the others through `id_file` (rank 0 writes it, the others poll; removed after the collective
@@ -151,6 +155,7 @@ class CRF_Model {
   int device = 0;
   uint32_t precision = SCRF_PREC_FAST;
   bool training_only = false;
+  int soft_mode = SCRF_ALIGN_RUNS;
   bool dist_on = false;
   int dist_rank = 0, dist_world = 1;
   std::string dist_id_file;
@@ -395,17 +400,30 @@ void compactLattice(const scrf_arc* arcs, size_t n, int32_t final_state, ArcList
 
 }  // namespace crf_amd
 
+// The soft objective (EXPFSOFT, CRF_NewGradBuilderSoft) lives in a unit of its own, crf_softgrad.cpp, so that
+// crf_amd.cpp stays linkable against an ABI without scrf_fb_transcript_batch.  That unit fills this slot from a static
+// initialiser; a binary without it refuses the objective (crf_amd_soft_objective_linked).  The hook forms each utterance's
+// transcript from its label stream -- the phones of the labelled frames in order, durations dropped, equal neighbours
+// collapsed under SCRF_ALIGN_RUNS -- and runs the device pass where the EXPF classes call scrf_fb_batch.  labels[u] / T[u]:
+// the label stream of utterance u; log_num / zx: [n_utts] or NULL.  Returns the engine's code; a missing label stream throws.
+typedef int (*crf_amd_soft_fb_fn)(scrf_handle h, scrf_batch b, const uint32_t* const* labels, const uint32_t* T, uint32_t n_utts,
+                                  uint32_t n_labs, int mode, double* log_num, double* zx);
+extern crf_amd_soft_fb_fn crf_amd_soft_fb;
+inline bool crf_amd_soft_objective_linked() { return crf_amd_soft_fb != nullptr; }
+#define CRF_AMD_SOFT_NOT_LINKED "crf_objective_function=softexpf: the soft-objective unit is not linked into this binary"
+
 // per-utterance gradient (CRF_GradBuilder::buildGradient, factory create())
 class CRF_GradBuilder {
  public:
   static CRF_GradBuilder* create(CRF_Model* crf, objfunctype ofunc);
-  explicit CRF_GradBuilder(CRF_Model* crf_in) : crf(crf_in) {}
+  explicit CRF_GradBuilder(CRF_Model* crf_in, objfunctype ofunc = EXPF) : objective(ofunc), crf(crf_in) {}
   virtual ~CRF_GradBuilder() {}
   // grad += observed - expected counts of the stream's CURRENT utterance; *Zx_out = log partition;
   // returns the numerator (caller forms logLi = numerator - Zx)
   virtual double buildGradient(CRF_FeatureStream* ftr_strm, double* grad, double* Zx_out);
 
  protected:
+  objfunctype objective;
   CRF_Model* crf;
 };
 
@@ -440,6 +458,7 @@ class CRF_Minibatch_GradAccumulator {
 
  protected:
   double accumulate(double* grad, double* Zx_out, QNUInt32* uttCount, bool* isEndOfIter);
+  objfunctype objective = EXPF;
   bool deferSums = false, sumsQueued = false, prevReady = false;
   double prevNumer = 0.0, prevZx = 0.0;
   CRF_Model* crf;

@@ -531,6 +531,27 @@ class Engine:
         self._chk(self.lib.scrf_transcript_stats(self.h, *[C.byref(x) for x in v]))
         return tuple(x.value for x in v)
 
+    def fb_transcript_batch(self, batch, transcripts, mode=ALIGN_RUNS, want_scalars=True):
+        """Training from transcripts (scrf_fb_transcript_batch): adds the gradient of sum_u (log_num[u] - zx[u]) -- the sum over
+        every alignment of each utterance's phone transcript against the free sum -- to the device gradient, and
+        {sum log_num, sum zx, n} to the batch sums.  transcripts as transcript_batch takes them; the batch needs no labels.
+        A transcript that does not fit is an error here.  Returns (log_num [U], zx [U]), or None without want_scalars."""
+        U = batch.n
+        if len(transcripts) != U:
+            raise ValueError("fb_transcript_batch: %d transcripts for a batch of %d utterances" % (len(transcripts), U))
+        ph, poff = self._ragged(transcripts, U)
+        ln = np.empty(U) if want_scalars else None
+        zx = np.empty(U) if want_scalars else None
+        self._chk(self.lib.scrf_fb_transcript_batch(self.h, batch.handle, _p(ph), _p(poff), C.c_int(int(mode)),
+                                                    _p(ln) if want_scalars else None, _p(zx) if want_scalars else None))
+        return (ln, zx) if want_scalars else None
+
+    def soft_stats(self):
+        """(scrf_fb_transcript_batch calls, chunks run, calls redone in the log domain) since create"""
+        v = [C.c_uint64() for _ in range(3)]
+        self._chk(self.lib.scrf_soft_stats(self.h, *[C.byref(x) for x in v]))
+        return tuple(x.value for x in v)
+
     def batch_is_fused(self, batch):
         f = C.c_int()
         self._chk(self.lib.scrf_batch_is_fused(self.h, batch.handle, C.byref(f)))

@@ -429,6 +429,45 @@ int scrf_transcript_batch(scrf_handle h, scrf_batch b, const uint32_t* phones, c
  * above, computeAlignedAlphaBeta's, lost every path of a fitting transcript to underflow, or the free recursion gave up) */
 int scrf_transcript_stats(scrf_handle h, uint64_t* n_calls, uint64_t* n_chunks, uint64_t* n_redone);
 
+/* ---- training from transcripts ---------------------------------------------------------------------- */
+/* replaces: CRF_NewGradBuilderSoft::buildGradient (trainers/gradbuilders/CRF_NewGradBuilderSoft.cpp:30-116, the objective
+ * crf_objective_function=softexpf): training on utterances that have a phone transcript and no segmentation.  The numerator
+ * sums of :44-58 (getAlignmentGammas / computeAlignedAlphaBeta) are those of scrf_transcript_batch; :99-110 subtracts the
+ * free expectation from the aligned one, which is what this call adds to the gradient.
+ * The objective.  Let A(q) be scrf_transcript_batch's log_num, the fp64 log-sum over the alignments of q under `mode`, by
+ * exactly that section's recursion, and Zx the free log-partition sum.  The device gradient accumulates (+=) the sum over the
+ * utterances of d(A - Zx)/d lambda = E[f | x, transcript] - E[f | x].  Written as counts, with g, aE, bB of the section above,
+ * gamma / xi the free posteriors of scrf_fb_batch, and the transition into a segment scored with M of its first frame:
+ *   state weights of label l, window (t,d):    [ sum over k with q_k = l of g(t,d,k) ]  -  gamma(t,d,l)
+ *   transition weights (p,c) at boundary t>=1: [ sum over k of xa(t,k) [p = q_{k-1}, c = q_k] + xs(t,k) [p = c = q_k] ]  -  xi(t,p,c)
+ *     xa(t,k) = exp( aE(t-1,k-1) + M_t(q_{k-1},q_k) + bB(t,k) - A )       advance, k >= 1
+ *     xs(t,k) = exp( aE(t-1,k)   + M_t(q_k,q_k)     + bB(t,k) - A )       stay, SCRF_ALIGN_RUNS only
+ * Each side is multiplied by the same feature vectors and biases as in scrf_fb_batch: the state window, and for transition
+ * features the next node's first window.  The sum over (p,c) of the transition numerator at boundary t is end_post[t-1].
+ * The batch sums (scrf_get_batch_sums) gain {sum log_num, sum zx, n_utts}: a trainer's logLi = numer - zx works unchanged.
+ * log_num and zx (host, [n_utts], either may be NULL) deliver them per utterance.
+ * The batch needs no labels; labels it carries are ignored (the result is the same bytes).
+ * Errors as scrf_fb_batch: the gradient of a batch is staged and nothing is committed on a failed batch, the first failed
+ * utterance is named.  A SCRF_ERR_NUMERIC status on the linear-domain tiers -- the free recursion's, or the transcript sweep's
+ * guard against a live term lost to underflow -- sends the WHOLE pass through the log-domain redo; scrf_train_stats and
+ * n_redone below count it.
+ * SCRF_ERR_INVALID, all checked before any launch: an unknown mode, q_k >= num_labs, descending offsets, equal neighbours
+ * with SCRF_ALIGN_RUNS (scrf_transcript_batch's checks and messages), and -- unlike scrf_transcript_batch -- a transcript
+ * that does not fit (scrf_align_batch's rule, T = 0 included): it would have no numerator, so in training it is an error;
+ * the message names the utterance.
+ * Models: as scrf_transcript_batch (SCRF_STDFRAME, SCRF_STDSEG_NO_DUR_NO_TRANSFTR, SCRF_STDSEG_NO_DUR_NO_SEGTRANSFTR with
+ * one state per label), dense and sparse maps, batches of frames or of windows; chunks under scratch_bytes, of which
+ * 32 bytes per frame x transcript position and 8 bytes per window row x label are part.
+ * Every train_precision is accepted.  A SCRF_PREC_FASTLIN handle runs this pass in the SCRF_PREC_FAST form: the six-block
+ * Z of the linear-average form exists only inside the fused posterior walk, which runs before the numerators are added.
+ * For the duration of the call the batch reads as unlabelled: no other thread may use the same batch (or handle) meanwhile.
+ * The pass runs on one stream: no second lane, no side route, no all-reduce overlap.  No floating-point atomics, every sum
+ * in a fixed order: two runs give the same bytes; log_num does not depend on the chunking. */
+int scrf_fb_transcript_batch(scrf_handle h, scrf_batch b, const uint32_t* phones, const uint64_t* phone_off /* [n_utts+1] */,
+                             int mode, double* log_num /* [n_utts] or NULL */, double* zx /* [n_utts] or NULL */);
+/* since scrf_create: calls; chunks run (a redone call runs its chunks twice); calls redone in the log domain */
+int scrf_soft_stats(scrf_handle h, uint64_t* n_calls, uint64_t* n_chunks, uint64_t* n_redone);
+
 /* ---- N-best decoding ------------------------------------------------------------------------------ */
 /* replaces: ShortestPath(lat, n) over buildLattice's lattice, for every utterance of the batch.  The hypotheses are the
  * complete paths of the lattice exactly as scrf_lattice_arcs(..., norm = 0, ...) defines it, with its float weights.  The
@@ -526,7 +565,7 @@ int scrf_sgd_step(scrf_handle h, double lr_or_eta, int use_adagrad, double eps);
  * kernel (the three that dominate a step). */
 #define SCRF_N_PHASES 10
 int scrf_last_timing(scrf_handle h, float* ms, uint32_t* n_launch);
-/* HIP-event time of every kernel of the last timed scrf_fb_batch / scrf_posteriors_batch / scrf_viterbi_batch / scrf_lattice_prune_batch / scrf_align_batch / scrf_transcript_batch, one line per kernel
+/* HIP-event time of every kernel of the last timed scrf_fb_batch / scrf_posteriors_batch / scrf_viterbi_batch / scrf_lattice_prune_batch / scrf_align_batch / scrf_transcript_batch / scrf_fb_transcript_batch, one line per kernel
  * name: "name\tmilliseconds\tlaunches\n" (events recorded on the stream the kernel is launched on) */
 int scrf_kernel_timing(scrf_handle h, char* buf, size_t cap);
 int scrf_enable_timing(scrf_handle h, int on);
