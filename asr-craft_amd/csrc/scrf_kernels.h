@@ -5,6 +5,7 @@
 #include "scrf_arcw.h"
 #include "scrf_common.h"
 #include "scrf_knobs.h"
+#include "scrf_mfma_plan.h"
 
 #include <vector>
 
@@ -59,9 +60,7 @@ void launch_scores_mfma(hipStream_t st, const ScrfKnobs& kn, const float* X, uin
 void launch_expf_mfma(hipStream_t st, const ScrfKnobs& kn, const double* A, uint32_t n_out, const float* X, uint32_t F,
                       const uint64_t* xrow, uint64_t n_rows, const ScrfLayout& lay, const ScrfGemmSpec& sp,
                       uint64_t rows_per_chunk, uint32_t n_chunks, double* slab, int f32 = 0);
-// workgroups launch_expf_mfma starts per row chunk when it takes the 8-wavefront form (one workgroup per CU), else 0:
-// the engine sizes the number of row chunks so that the launch fills whole rounds of the chip's CUs
-uint32_t expf_mfma_wide_tiles(uint32_t n_out, uint32_t nfun, int f32);
+// (which instantiations the two launch, and expf_mfma_wide_tiles for the engine's row chunks: scrf_mfma_plan.h)
 
 // scrf_dp.hip: wavefront-per-utterance DP and the parallel posterior kernels
 int dp_wave_supported(const ScrfLayout& lay);

@@ -14,6 +14,7 @@
 //   - row-major floats with stride == 2 (mod 32) words for the A operand of the score kernel.
 #include "scrf_kernels.h"
 
+#include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
 
@@ -28,11 +29,7 @@ struct __attribute__((packed, aligned(8))) d2u { double x, y; };
 #ifndef MM_PRIO
 #define MM_PRIO 1    // s_setprio level of the staging phases (0 = no priority play; A/B knob)
 #endif
-#define SM_ROWS 256  // rows per workgroup (4 waves x 4 M-tiles)
-#define SM_KC 32     // features per staged chunk (8 MFMA k-steps)
-#define SM_XS 34     // float row stride of the X image (== 2 mod 32: conflict-free A fragments)
-#define SM_NO 48     // outputs per workgroup (3 N-tiles)
-#define SM_WS 49     // double row stride of the lambda image [k][SM_WS]: transposed stores stay <= 2-way
+// (tile geometry -- SM_*, SW_*, EM_*, EW_* -- is in scrf_mfma_plan.h, shared with the choice of the form)
 
 // Software pipeline: while the MFMAs of chunk i run from LDS, the global loads of chunk i+1
 // are in flight into registers (8 x 16 B of X and 6 x 8 B of lambda per thread).
@@ -207,10 +204,6 @@ __global__ __launch_bounds__(256, 2) void k_scores_mfma(const float* __restrict_
 // rows 32 w, all 7 N-tiles: 112 outputs per workgroup (14 MFMAs per 2 + 7 reads).  An output count of 16 T is cut into
 // a tiles of 6 and b tiles of 7 N-tiles (T = 6a + 7b: 200 outputs = 96 + 112 with 8 masked), so that no thin remainder
 // launch re-reads all of X for a handful of outputs (config 5: 9 ms for 8 of 200).
-#define SW_ROWS 256
-#define SW_NO 96
-#define SW_WS 113
-#define SW_IMG (sizeof(float) * SW_ROWS * SM_XS + sizeof(double) * SM_KC * SW_WS)
 template <int MW, int NTW>
 __global__ __launch_bounds__(768) void k_scores_mfma_ws(const float* __restrict__ X, uint32_t F,
                                                        const uint64_t* __restrict__ xrow, uint64_t n_rows,
@@ -340,68 +333,48 @@ __global__ __launch_bounds__(768) void k_scores_mfma_ws(const float* __restrict_
   }
 }
 
+// the form is chosen by scrf_scores_mfma_plan (scrf_mfma_plan.h); here each planned launch finds its instantiation
+[[noreturn]] static void mfma_no_kernel(const char* what, const ScrfMfmaLaunch& p) {
+  fprintf(stderr, "scrf_mfma: no %s kernel for %s f32=%d nt=%d mw=%d ntw=%d xrow=%d nw=%d kc=%d mt=%d mtw=%d\n", what, scrf_mfma_kernel_name(p.kernel),
+          p.f32, p.nt, p.mw, p.ntw, p.has_xrow, p.nw, p.kc, p.mt, p.mtw);
+  abort();
+}
+#define SCORES_ARGS X, F, xrow, n_rows, lambda, lay, sp, n_out, p.o_base, p.gy, out
+template <int MW, int NTW>
+static void launch_scores_mfma_ws(hipStream_t st, const ScrfMfmaLaunch& p, uint32_t gx, const float* X, uint32_t F, const uint64_t* xrow, uint64_t n_rows,
+                                  const double* lambda, const ScrfLayout& lay, const ScrfGemmSpec& sp, uint32_t n_out, double* out) {
+  hipFuncSetAttribute((const void*)k_scores_mfma_ws<MW, NTW>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)p.lds);
+  hipLaunchKernelGGL((k_scores_mfma_ws<MW, NTW>), dim3(gx * p.gy), dim3(768), p.lds, st, SCORES_ARGS);
+}
 template <int F32>
-static void launch_scores_mfma_f(hipStream_t st, const ScrfKnobs& kn, const float* X, uint32_t F, const uint64_t* xrow, uint64_t n_rows,
+static void launch_scores_mfma_f(hipStream_t st, const ScrfMfmaLaunch& p, uint32_t gx, const float* X, uint32_t F, const uint64_t* xrow, uint64_t n_rows,
                                  const double* lambda, const ScrfLayout& lay, const ScrfGemmSpec& sp, uint32_t n_out, double* out) {
-  const uint32_t gx = (uint32_t)((n_rows + SM_ROWS - 1) / SM_ROWS);
-  uint32_t o_base = 0;
-  // SCRF_SCORES_MFMA_WS=0 for A/B runs (from 192 features on: with only a few 32-feature chunks the role split is all prologue -- the 40-feature per-window
-  // transition scores of STDSEG_NO_DUR: 5.8 ms single-role, 6.1 split)
-  if (!F32 && kn.scores_mfma_ws && n_out >= SW_NO && sp.nfe >= 192) {
-    // the wave-specialised form: 16 T outputs as a tiles of 96 and b tiles of 112 (T = 6a + 7b, fewest masked outputs); when
-    // the count does not split that way, the whole 96-output tiles go here and the rest to the single-role kernels below
-    const uint32_t T = (n_out + 15) / 16;
-    uint32_t a = n_out / SW_NO, bt = 0;
-    for (uint32_t b7 = 0; b7 < 6 && 7 * b7 <= T; b7++)
-      if ((T - 7 * b7) % 6 == 0) { a = (T - 7 * b7) / 6; bt = b7; break; }
-    if (a) {
-      hipFuncSetAttribute((const void*)k_scores_mfma_ws<4, 3>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(2 * SW_IMG));
-      hipLaunchKernelGGL((k_scores_mfma_ws<4, 3>), dim3(gx * a), dim3(768), 2 * SW_IMG, st, X, F, xrow, n_rows, lambda, lay, sp, n_out, 0u, a, out);
-    }
-    if (bt) {
-      hipFuncSetAttribute((const void*)k_scores_mfma_ws<2, 7>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(2 * SW_IMG));
-      hipLaunchKernelGGL((k_scores_mfma_ws<2, 7>), dim3(gx * bt), dim3(768), 2 * SW_IMG, st, X, F, xrow, n_rows, lambda, lay, sp, n_out, a * SW_NO, bt, out);
-    }
-    o_base = a * SW_NO + bt * 112;
-    if (o_base >= n_out) return;
+  switch (p.nt) {
+    case 3: hipLaunchKernelGGL((k_scores_mfma<F32, 3>), dim3(gx * p.gy), dim3(256), 0, st, SCORES_ARGS); return;
+    case 2: hipLaunchKernelGGL((k_scores_mfma<F32, 2>), dim3(gx * p.gy), dim3(256), 0, st, SCORES_ARGS); return;
+    case 1: hipLaunchKernelGGL((k_scores_mfma<F32, 1>), dim3(gx * p.gy), dim3(256), 0, st, SCORES_ARGS); return;
   }
-  const uint32_t left = n_out - o_base;
-  const uint32_t n_full = left / SM_NO, rem = left % SM_NO;
-  if (n_full)
-    hipLaunchKernelGGL((k_scores_mfma<F32, 3>), dim3(gx * n_full), dim3(256), 0, st, X, F, xrow, n_rows, lambda, lay, sp, n_out, o_base, n_full, out);
-  // the outputs past the last full 48: a launch whose workgroups carry only the N-tiles that hold outputs
-  if (rem > 32)
-    hipLaunchKernelGGL((k_scores_mfma<F32, 3>), dim3(gx), dim3(256), 0, st, X, F, xrow, n_rows, lambda, lay, sp, n_out, o_base + n_full * SM_NO, 1u, out);
-  else if (rem > 16)
-    hipLaunchKernelGGL((k_scores_mfma<F32, 2>), dim3(gx), dim3(256), 0, st, X, F, xrow, n_rows, lambda, lay, sp, n_out, o_base + n_full * SM_NO, 1u, out);
-  else if (rem > 0)
-    hipLaunchKernelGGL((k_scores_mfma<F32, 1>), dim3(gx), dim3(256), 0, st, X, F, xrow, n_rows, lambda, lay, sp, n_out, o_base + n_full * SM_NO, 1u, out);
+  mfma_no_kernel("score", p);
 }
 void launch_scores_mfma(hipStream_t st, const ScrfKnobs& kn, const float* X, uint32_t F, const uint64_t* xrow, uint64_t n_rows,
                         const double* lambda, const ScrfLayout& lay, const ScrfGemmSpec& sp, uint32_t n_out,
                         double* out, int f32) {
   if (n_rows == 0 || n_out == 0) return;
-  if (f32) launch_scores_mfma_f<1>(st, kn, X, F, xrow, n_rows, lambda, lay, sp, n_out, out);
-  else launch_scores_mfma_f<0>(st, kn, X, F, xrow, n_rows, lambda, lay, sp, n_out, out);
+  const uint32_t gx = (uint32_t)((n_rows + SM_ROWS - 1) / SM_ROWS);
+  ScrfMfmaLaunch plan[SCRF_MFMA_MAX_LAUNCHES];
+  const int n = scrf_scores_mfma_plan(kn, n_out, sp.nfe, f32 ? 1 : 0, plan);
+  for (int i = 0; i < n; i++) {
+    const ScrfMfmaLaunch& p = plan[i];
+    if (p.kernel == SCRF_MK_WS && p.mw == 4 && p.ntw == 3) launch_scores_mfma_ws<4, 3>(st, p, gx, X, F, xrow, n_rows, lambda, lay, sp, n_out, out);
+    else if (p.kernel == SCRF_MK_WS && p.mw == 2 && p.ntw == 7) launch_scores_mfma_ws<2, 7>(st, p, gx, X, F, xrow, n_rows, lambda, lay, sp, n_out, out);
+    else if (p.kernel == SCRF_MK_SINGLE && p.f32) launch_scores_mfma_f<1>(st, p, gx, X, F, xrow, n_rows, lambda, lay, sp, n_out, out);
+    else if (p.kernel == SCRF_MK_SINGLE) launch_scores_mfma_f<0>(st, p, gx, X, F, xrow, n_rows, lambda, lay, sp, n_out, out);
+    else mfma_no_kernel("score", p);
+  }
 }
+#undef SCORES_ARGS
 
 // ------------------------------------------------------------------------------------------
-// M-tiles (16 outputs each) of a workgroup tile of the unsplit form.  f64: 4 -- a wavefront carries 64 outputs x 48 feature
-// columns, 12 MFMAs per 7 operand loads and 96 per barrier (3: 9 per 6, 72 per barrier; measured at the TIMIT transition
-// counts 14.8 -> 13.5 ms, config 5's state counts 96.6 -> 91.1 ms; 231 VGPRs, no spills).  The f32 form spills at 4 and stays at 3.
-#ifndef EM_MTF
-#define EM_MTF 4
-#endif
-// (the narrow forms keep 3: with 1-4 wavefronts per workgroup a 64-wide posterior image means a third more staging
-// registers per thread -- the frame model's 40-column count contraction went from 0.58 to 1.54 ms with it)
-#define EM_MTW(F32, NW) (((F32) || (NW) < 8) ? 3 : EM_MTF)
-#define EM_SPLIT_NO 48        // outputs per wavefront of the split form (3 M-tiles)
-// row stride (doubles) of the posterior image [k][outputs]: == 16 (mod 32), so that the two k rows a 32-lane half of a
-// ds_read_b64 fragment read covers fall on disjoint bank halves (a stride of 64 or 192 doubles puts them on the same banks)
-// (only the 64-wide image of the wide form is padded: the split form's 192-wide image measured FASTER unpadded, 4.8 against
-// 6.6 ms at the per-window transition counts of STDSEG_NO_DUR)
-constexpr int em_rss(int no) { return no == 64 ? 80 : no; }
-
 // NW wavefronts per workgroup, each owning 48 feature columns (3 N-tiles): NW = 8 covers 384
 // columns (the full 338-wide state block of config 2 in one workgroup, so R is read once);
 // narrow contractions (factorised max/min/dur block, per-frame projections) use fewer waves.
@@ -615,12 +588,6 @@ __global__ __launch_bounds__(64 * NW) void k_expf_mfma(const double* __restrict_
 // store the next one into the other image pair: 192 of their threads own one 16-byte column of the X tile and 16 of its
 // rows each (column masks are per-thread constants), 64 own two columns of the posterior tile.  One barrier per chunk.
 // MT: M-tiles that hold outputs (the remainder launch carries fewer).
-#define EW_KC 32
-#define EW_NO 64
-#define EW_NF 384
-#define EW_XS (EW_NF + 16)
-#define EW_RS 80   // em_rss(EW_NO)
-#define EW_IMG (sizeof(double) * EW_KC * EW_RS + sizeof(float) * EW_KC * EW_XS)
 template <int HAS_XROW, int MT>
 __global__ __launch_bounds__(768) void k_expf_mfma_ws(const double* __restrict__ A, uint32_t n_out,
                                                      const float* __restrict__ X, uint32_t F,
@@ -764,112 +731,79 @@ __global__ __launch_bounds__(768) void k_expf_mfma_ws(const double* __restrict__
   }
 }
 
+// the form is chosen by scrf_expf_mfma_plan (scrf_mfma_plan.h); here the planned launch finds its instantiation
+#define EXPF_ARGS A, n_out, X, F, xrow, n_rows, lay, sp, rows_per_chunk, slab, p.o_base, p.gx, p.gy, p.o_step
+#define EXPF_PARAMS const double* A, uint32_t n_out, const float* X, uint32_t F, const uint64_t* xrow, uint64_t n_rows, const ScrfLayout& lay, \
+                    const ScrfGemmSpec& sp, uint64_t rows_per_chunk, uint32_t n_chunks, double* slab
+#define EXPF_PASS A, n_out, X, F, xrow, n_rows, lay, sp, rows_per_chunk, n_chunks, slab
 template <int HAS_XROW, int NW, int KC, int F32, int MT>
-static void launch_expf_mfma_one(hipStream_t st, const ScrfKnobs& kn, dim3 grid, size_t sm, const double* A, uint32_t n_out, const float* X, uint32_t F,
-                                 const uint64_t* xrow, uint64_t n_rows, const ScrfLayout& lay, const ScrfGemmSpec& sp,
-                                 uint64_t rows_per_chunk, double* slab, uint32_t o_base, uint32_t o_step = 16 * EM_MTW(F32, NW)) {
-  constexpr int DB = NW == 8 ? 1 : 0;   // the 8-wave workgroup has its CU to itself: room for a second image pair
+static void launch_expf_mfma_one(hipStream_t st, const ScrfMfmaLaunch& p, EXPF_PARAMS) {
   constexpr int MTW = EM_MTW(F32, NW);
-  if (NW == 8 && !F32 && KC == EW_KC && MTW * 16 == EW_NO && kn.expf_mfma_ws) {
-    constexpr int MTC = MT > 4 ? 4 : MT;
-    hipFuncSetAttribute((const void*)k_expf_mfma_ws<HAS_XROW, MTC>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(2 * EW_IMG));
-    hipLaunchKernelGGL((k_expf_mfma_ws<HAS_XROW, MTC>), dim3(grid.x * grid.y * grid.z), dim3(768), 2 * EW_IMG, st, A, n_out, X, F, xrow, n_rows, lay, sp,
-                       rows_per_chunk, slab, o_base, grid.x, grid.y, o_step);
-    return;
+  const dim3 grid(p.gx * p.gy * n_chunks);
+  if (p.mtw != MTW || p.mt != MT) mfma_no_kernel("count", p);
+  if constexpr (NW == 8 && !F32 && KC == EW_KC && MTW * 16 == EW_NO) {
+    if (p.kernel == SCRF_MK_WS) {
+      hipFuncSetAttribute((const void*)k_expf_mfma_ws<HAS_XROW, MT>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)p.lds);
+      hipLaunchKernelGGL((k_expf_mfma_ws<HAS_XROW, MT>), grid, dim3(768), p.lds, st, EXPF_ARGS);
+      return;
+    }
   }
-  if (DB && kn.expf_db) {
-    hipFuncSetAttribute((const void*)k_expf_mfma<HAS_XROW, NW, KC, F32, 0, MT, DB, MTW>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(2 * sm));
-    hipLaunchKernelGGL((k_expf_mfma<HAS_XROW, NW, KC, F32, 0, MT, DB, MTW>), dim3(grid.x * grid.y * grid.z), dim3(64 * NW), 2 * sm, st, A, n_out, X, F, xrow,
-                       n_rows, lay, sp, rows_per_chunk, slab, o_base, grid.x, grid.y, o_step);
-    return;
+  if constexpr (NW == 8) {
+    if (p.kernel == SCRF_MK_DB) {
+      hipFuncSetAttribute((const void*)k_expf_mfma<HAS_XROW, NW, KC, F32, 0, MT, 1, MTW>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)p.lds);
+      hipLaunchKernelGGL((k_expf_mfma<HAS_XROW, NW, KC, F32, 0, MT, 1, MTW>), grid, dim3(64 * NW), p.lds, st, EXPF_ARGS);
+      return;
+    }
   }
-  hipFuncSetAttribute((const void*)k_expf_mfma<HAS_XROW, NW, KC, F32, 0, MT, 0, MTW>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sm);
-  hipLaunchKernelGGL((k_expf_mfma<HAS_XROW, NW, KC, F32, 0, MT, 0, MTW>), dim3(grid.x * grid.y * grid.z), dim3(64 * NW), sm, st, A, n_out, X, F, xrow,
-                     n_rows, lay, sp, rows_per_chunk, slab, o_base, grid.x, grid.y, o_step);
+  if (p.kernel != SCRF_MK_PLAIN) mfma_no_kernel("count", p);
+  hipFuncSetAttribute((const void*)k_expf_mfma<HAS_XROW, NW, KC, F32, 0, MT, 0, MTW>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)p.lds);
+  hipLaunchKernelGGL((k_expf_mfma<HAS_XROW, NW, KC, F32, 0, MT, 0, MTW>), grid, dim3(64 * NW), p.lds, st, EXPF_ARGS);
 }
-// (a mixed tiling of the outputs -- 200 = 64 + 3 x 48 instead of 3 x 64 + a thin 8-output launch -- was measured at config 5:
-// 81.8 against 80.0 ms; the thin launch costs less than the thirteenth M-tile)
 template <int HAS_XROW, int NW, int KC, int F32>
-static void launch_expf_mfma_x(hipStream_t st, const ScrfKnobs& kn, const double* A, uint32_t n_out, const float* X, uint32_t F,
-                               const uint64_t* xrow, uint64_t n_rows, const ScrfLayout& lay, const ScrfGemmSpec& sp,
-                               uint64_t rows_per_chunk, uint32_t n_chunks, double* slab) {
-  const uint32_t nfun = sp.nfun();
-  const uint32_t gx = (nfun + 48 * NW - 1) / (48 * NW);
-  constexpr int MTW = EM_MTW(F32, NW);
-  constexpr uint32_t NO = 16 * MTW;
-  const size_t sm = sizeof(double) * KC * em_rss((int)NO) + sizeof(float) * KC * (48 * NW + 16);
-  const uint32_t n_full = n_out / NO, rem = n_out % NO;
-  if (n_full)
-    launch_expf_mfma_one<HAS_XROW, NW, KC, F32, MTW>(st, kn, dim3(gx, n_full, n_chunks), sm, A, n_out, X, F, xrow, n_rows, lay, sp, rows_per_chunk, slab, 0u);
-  // the outputs past the last full tile: workgroups that carry only the M-tiles holding outputs
-  if (MTW > 3 && rem > 48)
-    launch_expf_mfma_one<HAS_XROW, NW, KC, F32, MTW>(st, kn, dim3(gx, 1, n_chunks), sm, A, n_out, X, F, xrow, n_rows, lay, sp, rows_per_chunk, slab, n_full * NO);
-  else if (rem > 32)
-    launch_expf_mfma_one<HAS_XROW, NW, KC, F32, 3>(st, kn, dim3(gx, 1, n_chunks), sm, A, n_out, X, F, xrow, n_rows, lay, sp, rows_per_chunk, slab, n_full * NO);
-  else if (rem > 16)
-    launch_expf_mfma_one<HAS_XROW, NW, KC, F32, 2>(st, kn, dim3(gx, 1, n_chunks), sm, A, n_out, X, F, xrow, n_rows, lay, sp, rows_per_chunk, slab, n_full * NO);
-  else if (rem > 0)
-    launch_expf_mfma_one<HAS_XROW, NW, KC, F32, 1>(st, kn, dim3(gx, 1, n_chunks), sm, A, n_out, X, F, xrow, n_rows, lay, sp, rows_per_chunk, slab, n_full * NO);
+static void launch_expf_mfma_x(hipStream_t st, const ScrfMfmaLaunch& p, EXPF_PARAMS) {
+  if constexpr (NW == EM_SPLIT_NW && KC == EM_SPLIT_KC) {   // 16-row chunks: the split form alone
+    if (p.kernel != SCRF_MK_SPLIT) mfma_no_kernel("count", p);
+    hipLaunchKernelGGL((k_expf_mfma<HAS_XROW, NW, KC, F32, 1>), dim3(p.gx * p.gy * n_chunks), dim3(64 * NW), p.lds, st, EXPF_ARGS);
+  } else {
+    switch (p.kernel == SCRF_MK_SPLIT ? 0 : p.mt) {
+      case 1: launch_expf_mfma_one<HAS_XROW, NW, KC, F32, 1>(st, p, EXPF_PASS); return;
+      case 2: launch_expf_mfma_one<HAS_XROW, NW, KC, F32, 2>(st, p, EXPF_PASS); return;
+      case 3: launch_expf_mfma_one<HAS_XROW, NW, KC, F32, 3>(st, p, EXPF_PASS); return;
+      case 4:
+        if constexpr (EM_MTW(F32, NW) >= 4) { launch_expf_mfma_one<HAS_XROW, NW, KC, F32, 4>(st, p, EXPF_PASS); return; }
+        break;
+    }
+    mfma_no_kernel("count", p);
+  }
 }
-template <int NW, int KC, int F32>
-static void launch_expf_mfma_nw(hipStream_t st, const ScrfKnobs& kn, const double* A, uint32_t n_out, const float* X, uint32_t F,
-                                const uint64_t* xrow, uint64_t n_rows, const ScrfLayout& lay, const ScrfGemmSpec& sp,
-                                uint64_t rows_per_chunk, uint32_t n_chunks, double* slab) {
-  if (xrow) launch_expf_mfma_x<1, NW, KC, F32>(st, kn, A, n_out, X, F, xrow, n_rows, lay, sp, rows_per_chunk, n_chunks, slab);
-  else launch_expf_mfma_x<0, NW, KC, F32>(st, kn, A, n_out, X, F, xrow, n_rows, lay, sp, rows_per_chunk, n_chunks, slab);
-}
-
-// few feature functions (<= 48) and many outputs: 4 wavefronts share the feature tile and split 192 outputs
-template <int F32>
-static void launch_expf_mfma_split(hipStream_t st, const double* A, uint32_t n_out, const float* X, uint32_t F,
-                                   const uint64_t* xrow, uint64_t n_rows, const ScrfLayout& lay, const ScrfGemmSpec& sp,
-                                   uint64_t rows_per_chunk, uint32_t n_chunks, double* slab) {
-  constexpr int NW = 4, KC = 16;
-  dim3 grid(1, (n_out + EM_SPLIT_NO * NW - 1) / (EM_SPLIT_NO * NW), n_chunks);
-  const size_t sm = sizeof(double) * KC * em_rss(EM_SPLIT_NO * NW) + sizeof(float) * KC * (48 + 16);
-  if (xrow)
-    hipLaunchKernelGGL((k_expf_mfma<1, NW, KC, F32, 1>), dim3(grid.x * grid.y * grid.z), dim3(64 * NW), sm, st, A, n_out, X, F, xrow, n_rows, lay, sp,
-                       rows_per_chunk, slab, 0u, grid.x, grid.y, (uint32_t)(EM_SPLIT_NO * NW));
-  else
-    hipLaunchKernelGGL((k_expf_mfma<0, NW, KC, F32, 1>), dim3(grid.x * grid.y * grid.z), dim3(64 * NW), sm, st, A, n_out, X, F, xrow, n_rows, lay, sp,
-                       rows_per_chunk, slab, 0u, grid.x, grid.y, (uint32_t)(EM_SPLIT_NO * NW));
-}
-uint32_t expf_mfma_wide_tiles(uint32_t n_out, uint32_t nfun, int f32) {
-  const uint32_t tiles = (nfun + 47) / 48;
-  if (tiles <= 4) return 0;   // split and narrow forms: several workgroups per CU, no round structure to fit
-  const uint32_t gx = (nfun + 48 * 8 - 1) / (48 * 8);
-  const uint32_t NO = 16 * (uint32_t)EM_MTW(f32, 8);
-  return gx * ((n_out + NO - 1) / NO);
+template <int NW, int KC>
+static void launch_expf_mfma_nw(hipStream_t st, const ScrfMfmaLaunch& p, EXPF_PARAMS) {
+  if (p.f32) {
+    if (p.has_xrow) launch_expf_mfma_x<1, NW, KC, 1>(st, p, EXPF_PASS);
+    else launch_expf_mfma_x<0, NW, KC, 1>(st, p, EXPF_PASS);
+  } else {
+    if (p.has_xrow) launch_expf_mfma_x<1, NW, KC, 0>(st, p, EXPF_PASS);
+    else launch_expf_mfma_x<0, NW, KC, 0>(st, p, EXPF_PASS);
+  }
 }
 
 void launch_expf_mfma(hipStream_t st, const ScrfKnobs& kn, const double* A, uint32_t n_out, const float* X, uint32_t F,
                       const uint64_t* xrow, uint64_t n_rows, const ScrfLayout& lay, const ScrfGemmSpec& sp,
                       uint64_t rows_per_chunk, uint32_t n_chunks, double* slab, int f32) {
   if (n_rows == 0 || n_chunks == 0) return;
-  const uint32_t nfun = sp.nfun();
-  const uint32_t tiles = (nfun + 47) / 48;  // 48-column wave tiles needed
-#define EXPF_ARGS A, n_out, X, F, xrow, n_rows, lay, sp, rows_per_chunk, n_chunks, slab
-  if (tiles <= 1 && n_out >= 4 * EM_SPLIT_NO) {
-    if (f32) launch_expf_mfma_split<1>(st, EXPF_ARGS);
-    else launch_expf_mfma_split<0>(st, EXPF_ARGS);
-    return;
+  ScrfMfmaLaunch plan[SCRF_MFMA_MAX_LAUNCHES];
+  const int n = scrf_expf_mfma_plan(kn, n_out, sp.nfun(), f32 ? 1 : 0, xrow != nullptr, plan);
+  for (int i = 0; i < n; i++) {
+    const ScrfMfmaLaunch& p = plan[i];
+    if (p.nw == 1 && p.kc == 32) launch_expf_mfma_nw<1, 32>(st, p, EXPF_PASS);
+    else if (p.nw == 2 && p.kc == 64) launch_expf_mfma_nw<2, 64>(st, p, EXPF_PASS);
+    else if (p.nw == 3 && p.kc == 64) launch_expf_mfma_nw<3, 64>(st, p, EXPF_PASS);
+    else if (p.nw == 4 && p.kc == 64) launch_expf_mfma_nw<4, 64>(st, p, EXPF_PASS);
+    else if (p.nw == 8 && p.kc == 32) launch_expf_mfma_nw<8, 32>(st, p, EXPF_PASS);
+    else if (p.nw == EM_SPLIT_NW && p.kc == EM_SPLIT_KC) launch_expf_mfma_nw<EM_SPLIT_NW, EM_SPLIT_KC>(st, p, EXPF_PASS);
+    else mfma_no_kernel("count", p);
   }
-  if (f32) {
-    if (tiles <= 1) launch_expf_mfma_nw<1, 32, 1>(st, kn, EXPF_ARGS);
-    else if (tiles <= 2) launch_expf_mfma_nw<2, 64, 1>(st, kn, EXPF_ARGS);
-    else if (tiles <= 3) launch_expf_mfma_nw<3, 64, 1>(st, kn, EXPF_ARGS);
-    else if (tiles <= 4) launch_expf_mfma_nw<4, 64, 1>(st, kn, EXPF_ARGS);
-    else launch_expf_mfma_nw<8, 32, 1>(st, kn, EXPF_ARGS);
-  } else {
-    if (tiles <= 1) launch_expf_mfma_nw<1, 32, 0>(st, kn, EXPF_ARGS);
-    else if (tiles <= 2) launch_expf_mfma_nw<2, 64, 0>(st, kn, EXPF_ARGS);
-    else if (tiles <= 3) launch_expf_mfma_nw<3, 64, 0>(st, kn, EXPF_ARGS);
-    else if (tiles <= 4) launch_expf_mfma_nw<4, 64, 0>(st, kn, EXPF_ARGS);
-    else {
-      // (64-row chunks for the 8-wave form were tried: 256 VGPRs + 336 bytes of spills)
-      // (two 4-wave workgroups per CU with 64-row chunks instead: 18.1 ms against 14.4 at the TIMIT transition counts)
-      launch_expf_mfma_nw<8, 32, 0>(st, kn, EXPF_ARGS);
-    }
-  }
-#undef EXPF_ARGS
 }
+#undef EXPF_ARGS
+#undef EXPF_PARAMS
+#undef EXPF_PASS
