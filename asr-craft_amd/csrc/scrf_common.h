@@ -149,7 +149,7 @@ struct ScrfFusedArgs {
   uint32_t TB, W;
   const double* dtab;         // k_dur_table's output ([output block][D][50]), or nullptr: the score kernel builds it per tile
   const void* rtab;           // k_tile_tables' output (records, row bases, rowmap of a steady-state tile), or nullptr
-  uint32_t dma;               // score kernel: 1 = the form that stages tables, frames and P rows by LDS-DMA (given dtab and rtab)
+  uint32_t pad_;              // (keeps the kernels' argument layout)
 };
 
 // Decode mode of the fused score kernel: instead of the fp64 scores it writes the float arc

@@ -466,7 +466,7 @@ extern "C" int scrf_create(const scrf_config* cfg, scrf_handle* out) {
   CRCHK(h->d_grad.reserve(n_lam));
   CRCHK(h->d_m0.reserve(LL));
   CRCHK(h->d_w1.reserve(lay.L));
-  if (lay.D <= 40) CRCHK(h->d_dtab.reserve(fused_dur_table_doubles(lay)));
+  if (lay.D <= 40) CRCHK(h->d_dtab.reserve(fused_dur_table_doubles(fused_shape(lay))));
   if (cfg->map_type >= SCRF_STDSPARSE) {
     CRCHK(h->d_lamT[0].reserve(((size_t)lay.nsfe + lay.use_sb) * lay.L));
     CRCHK(h->d_lamT[1].reserve(((size_t)lay.ntfe + lay.use_tb) * LL));
@@ -922,7 +922,7 @@ extern "C" int scrf_batch_create(scrf_handle h, const scrf_utt* utts, uint32_t n
   const bool hybrid_first = !sparse_map && h->kn.hybrid_first() && lay.L > 64 && n_streams == 1 && !lay.use_tf;
   const bool seg_stream0 = !sparse_map && !hybrid_first && !by_windows && n_streams >= 1 && h->cfg.model_type != SCRF_STDSEG_NO_DUR && h->cfg.model_type != SCRF_STDSEG && lay.use_sf &&
                            recipes[0].extract_seg_ftr && !recipes[0].left_ctx && !recipes[0].right_ctx && lay.sfs == 0 &&
-                           lay.nsfe == 8 * recipes[0].in_width + lay.D && fused_supported(h->kn, lay, recipes[0].in_width, f32_cfg);
+                           lay.nsfe == 8 * recipes[0].in_width + lay.D && fused_supported(h->kn, fused_shape(lay), recipes[0].in_width, f32_cfg);
   // "mixed" (round 4, BASELINE config 3's shape): the state features are exactly stream 0's segment-recipe window and the
   // transition features live in the other streams' columns -- the state part takes the fused kernels, the transition
   // part keeps the materialised first-row windows and the dense contractions
@@ -932,7 +932,7 @@ extern "C" int scrf_batch_create(scrf_handle h, const scrf_utt* utts, uint32_t n
   // counts through the per-frame sums Z (k_lin_z, Z^T F), exactly as on the fused path.
   b->hybrid_ok = !sparse_map && !by_windows && n_streams == 1 && h->cfg.model_type != SCRF_STDSEG_NO_DUR && h->cfg.model_type != SCRF_STDSEG && lay.use_sf &&
                  !lay.use_tf && recipes[0].extract_seg_ftr && !recipes[0].left_ctx && !recipes[0].right_ctx && lay.sfs == 0 && lay.D >= 2 &&
-                 lay.nsfe == 8 * recipes[0].in_width + lay.D && (hybrid_first || !fused_supported(h->kn, lay, recipes[0].in_width, f32_cfg));
+                 lay.nsfe == 8 * recipes[0].in_width + lay.D && (hybrid_first || !fused_supported(h->kn, fused_shape(lay), recipes[0].in_width, f32_cfg));
   const bool mixed_ok = seg_stream0 && n_streams >= 2 && lay.use_tf && lay.tfs >= lay.nsfe && h->kn.fuse_mixed;
   if ((seg_stream0 && n_streams == 1 && !lay.use_tf && lay.nsfe == lay.F) || mixed_ok) {
     b->fused_ok = true;
@@ -951,11 +951,12 @@ extern "C" int scrf_batch_create(scrf_handle h, const scrf_utt* utts, uint32_t n
       BSYNC();
     }
     // score tiles: the windows of TB whole frames; expected-count tiles: those of TBE whole frames (<= 64 windows)
-    const uint32_t D = lay.D, TB = fused_scores_tb(recipes[0].in_width, D), TBE = fused_expf_frames(D);
+    const uint32_t D = lay.D, TB = fused_scores_tb(recipes[0].in_width, D);
+    const uint32_t TBE = fused_expf_plan(h->kn, fused_shape(lay), recipes[0].in_width, f32_cfg, 0, 1).frames;   // (tile list 1 without the linear average)
     // a third list when the engine trains with the linear window average and its count kernel walks taller tiles
     uint32_t TBL = 0;
-    if (h->cfg.train_precision == SCRF_PREC_FASTLIN && fused_la_supported(h->kn, lay, recipes[0].in_width)) {
-      const ScrfFusedExpfPlan plan = fused_expf_plan(h->kn, lay, recipes[0].in_width, 0, 1);
+    if (h->cfg.train_precision == SCRF_PREC_FASTLIN && fused_la_supported(h->kn, fused_shape(lay), recipes[0].in_width)) {
+      const ScrfFusedExpfPlan plan = fused_expf_plan(h->kn, fused_shape(lay), recipes[0].in_width, 0, 1, 1);
       if (plan.tile_list == 2) TBL = plan.frames;
     }
     for (int k = 0; k < (TBL ? 3 : 2); k++) {
@@ -1338,9 +1339,9 @@ static void chunk_layout(scrf_handle h, scrf_batch b, uint32_t u0, uint32_t u1, 
       cb->nch_s = (uint32_t)((nseg + cb->rpc_s - 1) / cb->rpc_s);
       if (!sparse(h)) cb->slab_s = a.take<double>((size_t)(nd.fused ? 512 : cb->nch_s) * l.L * l.nsf);
       if (nd.fused && cb->slab_s) {   // the fused count kernel's plan lives inside its 512 slabs: nothing of it is measured
-        const ScrfFusedExpfPlan& plan = cb->expf_plan = fused_expf_plan(h->kn, l, b->recipe[0].in_width, h->cfg.train_precision == SCRF_PREC_FAST32, nd.la);
-        cb->nch_s = fused_expf_blocks(h->kn, l, b->recipe[0].in_width, h->cfg.train_precision == SCRF_PREC_FAST32,
-                                      b->tile_off[plan.tile_list][u1] - b->tile_off[plan.tile_list][u0], nd.la);
+        const ScrfFusedExpfPlan& plan = cb->expf_plan = fused_expf_plan(h->kn, fused_shape(l), b->recipe[0].in_width, h->cfg.train_precision == SCRF_PREC_FAST32,
+                                                                        nd.la, ((uintptr_t)cb->R & 15) == 0);
+        cb->nch_s = fused_expf_blocks(plan, b->tile_off[plan.tile_list][u1] - b->tile_off[plan.tile_list][u0]);
         // dense columns + durations + bias <= nsf: the duration slab fits behind the dense one
         cb->slab_d = cb->slab_s + (size_t)cb->nch_s * l.L * plan.ncol;
       }
@@ -1484,7 +1485,6 @@ static ScrfFusedArgs fused_args(scrf_handle h, scrf_batch b, uint32_t u0, int wh
   fa.row_base = b->seg_off[u0];
   fa.frame_base = b->frame_off[u0];
   fa.W = b->recipe[0].in_width;
-  fa.TB = fused_scores_tb(fa.W, h->lay.D);
   return fa;
 }
 
@@ -1537,7 +1537,10 @@ static int run_scores(scrf_handle h, scrf_batch b, uint32_t u0, uint32_t u1, Chu
     PhaseTimer tm(h, PH_SCORE, cb.st);
     const uint32_t W0 = b->recipe[0].in_width;
     ScrfFusedArgs fa = fused_args(h, b, u0, 0);
-    if (h->d_dtab && h->kn.dtab) {
+    const bool tabs = h->d_dtab && h->kn.dtab;   // the launch tables: k_dur_table's and (SCRF_RTAB) k_tile_tables'
+    const ScrfFusedScoresPlan sp = fused_scores_plan(h->kn, fused_shape(l), W0, f32, cb.Wn ? 1 : 0, cb.la ? 1 : 0, tabs, tabs && h->kn.rtab);
+    fa.TB = sp.tb;
+    if (tabs) {
       launch_dur_table(cb.st, l, W0, h->d_lambda, h->d_dtab);
       fa.dtab = h->d_dtab;
       const size_t nb = fused_tile_table_bytes(l.D, fa.TB);
@@ -1552,7 +1555,6 @@ static int run_scores(scrf_handle h, scrf_batch b, uint32_t u0, uint32_t u1, Chu
         h->rtab.stream = cb.st;
       } else if (cb.st != h->rtab.stream) HIPCHK(h, hipStreamWaitEvent(cb.st, h->rtab.ev, 0));
       if (h->kn.rtab) fa.rtab = h->rtab.tab;
-      fa.dma = h->kn.scores_dma ? 1 : 0;
     }
     // per-frame projections of the five sampled blocks, then the dense part + gather
     if (pframe_supported(W0))
@@ -1574,18 +1576,18 @@ static int run_scores(scrf_handle h, scrf_batch b, uint32_t u0, uint32_t u1, Chu
       // epilogue adds).  1 % covers gamma's denominator and the rounding of the bound itself.
       dz.bound_scale = h->kn.decode_bound_scale * 1.01 * 0x1p-53 * (double)(l.nsfe + 1 + 3 * W0 + 8);
       PhaseTimer tk(h, PH_K_SCORE, cb.st);
-      KT_RUN("k_scores_fused(decode)", cb.st, launch_scores_fused_decode(cb.st, fa, l, h->d_lambda, cb.P, b->tile_off[0][u1] - b->tile_off[0][u0], dz));
+      KT_RUN("k_scores_fused(decode)", cb.st, launch_scores_fused_decode(cb.st, sp, fa, l, h->d_lambda, cb.P, b->tile_off[0][u1] - b->tile_off[0][u0], dz));
       tk.stop(1);
       tm.stop(3);
       HIPCHK(h, hipGetLastError());
       return SCRF_OK;
     }
     // on the linear-domain path the epilogue already exponentiates the rows (L <= 48)
-    cb.es_ready = cb.lin && l.L <= 48;
+    cb.es_ready = cb.lin && sp.smax;
     {
       PhaseTimer tk(h, PH_K_SCORE, cb.st);
-      KT_RUN("k_scores_fused", cb.st, launch_scores_fused(cb.st, fa, l, h->d_lambda, cb.P, b->tile_off[0][u1] - b->tile_off[0][u0], cb.S, f32,
-                          cb.es_ready ? cb.smax : nullptr, cb.s_true, b->d_labels, cb.la ? 1 : 0));
+      KT_RUN("k_scores_fused", cb.st, launch_scores_fused(cb.st, sp, fa, l, h->d_lambda, cb.P, b->tile_off[0][u1] - b->tile_off[0][u0], cb.S,
+                          cb.es_ready ? cb.smax : nullptr, cb.s_true, b->d_labels));
       tk.stop(1);
     }
     tm.stop(2);
@@ -2120,7 +2122,7 @@ static BatchForm batch_form(scrf_handle h, scrf_batch b) {
   f.fusable = b->fused_ok && h->kn.fuse;
   f.hybrid = !f.fusable && b->hybrid_ok && h->kn.hybrid_on() && h->kn.fuse && prec >= SCRF_PREC_FAST && prec != SCRF_PREC_FAST32 && h->kn.lindp &&
              wave_path(h, true);
-  f.la = prec == SCRF_PREC_FASTLIN && h->kn.lindp && wave_path(h, true) && fused_la_supported(h->kn, h->lay, b->recipe[0].in_width);
+  f.la = prec == SCRF_PREC_FASTLIN && h->kn.lindp && wave_path(h, true) && fused_la_supported(h->kn, fused_shape(h->lay), b->recipe[0].in_width);
   return f;
 }
 static void set_batch_form(scrf_handle h, scrf_batch b, Need* nd) {
@@ -2257,7 +2259,7 @@ static int count_fused(scrf_handle h, scrf_batch b, uint32_t u0, uint32_t u1, Ch
   }
   {
     PhaseTimer tk(h, PH_K_EXPF, cb.st);
-    KT_RUN("k_expf_fused", cb.st, launch_expf_fused(cb.st, h->kn, fa, l, cb.R, b->tile_off[plan.tile_list][u1] - b->tile_off[plan.tile_list][u0], cb.slab_s, cb.slab_d, prec_f32(h), cb.la ? 1 : 0));
+    KT_RUN("k_expf_fused", cb.st, launch_expf_fused(cb.st, plan, fa, l, cb.R, b->tile_off[plan.tile_list][u1] - b->tile_off[plan.tile_list][u0], cb.slab_s, cb.slab_d));
     tk.stop(1);
   }
   if (plan.ndur) {
@@ -2290,9 +2292,9 @@ static void count_hybrid(scrf_handle h, scrf_batch b, uint32_t u0, uint32_t u1, 
     tk.stop(1);
   }
   cc->owe(cb.slab_s, cb.nch_s, l.L, spec_stats_x(l, W0));
-  KT_RUN("k_lin_z5", cb.st, launch_lin_z5(cb.st, l, b->view(), u0, nutt, t_max, nfr, cb.R, cb.Z, cb.slab_d));
-  int seg_len = 0;
-  cc->owe(cb.slab_d, nutt * lin_z5_segments(nutt, l.L, l.D, t_max, &seg_len), l.L, spec_dur_bias(l, W0));
+  const ScrfFusedWalkPlan zp = fused_lin_z5_plan(fused_shape(l), nutt, t_max);
+  KT_RUN("k_lin_z5", cb.st, launch_lin_z5(cb.st, zp, l, b->view(), u0, nfr, cb.R, cb.Z, cb.slab_d));
+  cc->owe(cb.slab_d, nutt * zp.nz, l.L, spec_dur_bias(l, W0));
   if (pframe_supported(W0)) KT_RUN("k_ztf", cb.st, launch_ztf(cb.st, cb.Z, 5 * l.L, fr0, W0, nfr, cb.rpc_l, cb.nch_l, cb.slab_l));
   else KT_RUN("k_expf_mfma(samples)", cb.st, launch_expf_mfma(cb.st, h->kn, cb.Z, 5 * l.L, fr0, W0, nullptr, nfr, l, spec_samples(W0), cb.rpc_l, cb.nch_l, cb.slab_l));
   cc->owe(cb.slab_l, cb.nch_l, 5 * l.L, spec_samples(W0));

@@ -34,19 +34,7 @@
 typedef double v4f64 __attribute__((ext_vector_type(4)));
 typedef float v4f32 __attribute__((ext_vector_type(4)));
 
-#define FU_GC 40        // columns per dense chunk of the score kernel
-#define FU_XS 42        // float row stride of the chunk image (== 2 mod 4: conflict-free A fragments)
-#define FU_WS 49        // row stride of the transposed lambda image
-#define FU_ROWS SCRF_FUSED_ROWS_SCORES
-#define FE_ROWS SCRF_FUSED_ROWS_EXPF
-#define FE_RSF 80       // float row stride of the R image in the f32 form: == 16 (mod 32), the b32 counterpart
-#define FE_RS 48        // double row stride of the R image: 96 dwords = 32 (mod 64), so the two k-rows a 32-lane half of a
-                        // ds_read_b64 A-fragment covers fall on disjoint banks (50 overlapped four of them)
-
-__host__ __device__ inline uint32_t fu_sample_step(uint32_t d, int k) {
-  const float ot = (float)((double)d * 0.1);
-  return (uint32_t)ceilf(ot * (float)(2 * k + 1)) - 1u;
-}
+// (tile geometry -- FU_* / FE_* / FW_* row counts, strides and thread counts -- and fu_sample_step, fu_p_rows: scrf_fused_plan.h)
 __device__ __forceinline__ uint32_t fu_div(uint32_t i, uint32_t magic) { return magic ? __umulhi(i, magic) : i; }   // magic 0: d == 1 (2^32 does not fit)
 __device__ __forceinline__ uint32_t fu_magic(uint32_t d) { return d < 2 ? 0u : 0xffffffffu / d + 1u; }   // ceil(2^32 / d) in 32-bit arithmetic
 // FU_PROF (debug builds only): wave 0 of every workgroup stamps the phase boundaries with s_memtime and adds the
@@ -121,7 +109,6 @@ __device__ __forceinline__ double fu_exp(double x, const FuExpC& k) {
 // polynomial is exact to 4e-17 and the whole thing is 14 vector instructions and one LDS read instead of 21.  The
 // reduction uses ln2/256 as one constant: its rounding error times n is below 1e-14 for every x above -100 (what lies
 // further down is below e^-100 of the row maximum).
-#define FU_EXPT_N 256
 __device__ __forceinline__ double fu_exp_tab(double x, const double* tab) {
   x = fmax(x, -1000.0);
   const double n = rint(x * 369.32993046756268);             // 256 / ln 2
@@ -254,15 +241,11 @@ __device__ __forceinline__ void fu_dma_copy16(uint32_t wave, uint32_t lane, cons
 // a time (one thread per (frame, column)); the next chunk's lambda slice is fetched under the MFMAs.
 // After the last chunk the tile's rows of P are staged over the dead operand images for the gather.
 // ------------------------------------------------------------------------------------------
-#define FU_NT 512
 // experiment switches (defaults = the shipped configuration)
 #ifndef FU_PHI
 #define FU_PHI 1        // 1: a lane's outputs are the pairs 8j + 2lk + {0,1}: the 4 lanes of a row store 64 contiguous bytes
 #endif                  //    per instruction; 0: 12 consecutive outputs per lane (96-byte pieces 96 bytes apart)
-#ifndef FU_EXPTAB
-#define FU_EXPTAB 0     // 1: table-based exp in the epilogue (14 instructions + a gathered LDS read instead of 21; measured
-                        // equal -- the epilogue is not instruction-bound -- and the table costs 2 KB of LDS and bank conflicts)
-#endif
+// (FU_EXPTAB enters the LDS size: scrf_fused_plan.h)
 #ifndef FU_FULLSCAN
 #define FU_FULLSCAN 1   // steady-state scan without clamps and dumps
 #endif
@@ -285,9 +268,6 @@ __device__ __forceinline__ void fu_dma_copy16(uint32_t wave, uint32_t lane, cons
 #define FU_ABL 0        // ablations (wrong results): 1 = no global loads in the P staging, 2 = nor in the frame staging;
                         // count kernel: 3 = no consumer MFMAs, 4 = no producer builds, 5 = no R loads, 6 = no window scans
 #endif
-#define FU_DS 50        // double row stride of the P image and of the duration-weight table: 25 16-byte slots, odd, so
-                        // that the rows of consecutive frames / durations a ds_read_b128 lane group gathers start on
-                        // distinct slots (48 would put them on two)
 typedef double v2f64 __attribute__((ext_vector_type(2)));
 typedef float v2f32 __attribute__((ext_vector_type(2)));
 // smax != nullptr (n_out <= 48 only): the epilogue writes exp(S - smax[row]) instead of S, with
@@ -300,12 +280,6 @@ typedef float v2f32 __attribute__((ext_vector_type(2)));
 // (o = 12 lk + 4 n + r) instead of 3 outputs of 8 rows, so everything the epilogue does per row -- the five gather
 // offsets, the duration weights, the row maximum, the label test -- is paid once per 12 outputs, the gathers and the
 // stores are 16-byte accesses, and the row maximum needs two lane swaps.
-// rows of the staged P image: block k holds the frames sample position k can reach, TB + off_k(D) of them
-__host__ __device__ inline uint32_t fu_p_rows(uint32_t D, uint32_t TB) {
-  uint32_t n = 0;
-  for (int k = 0; k < 5; k++) n += TB + (D - 1 - fu_sample_step(D, k));
-  return n;
-}
 #define FU_NPQ 12       // P rows per thread held in registers between their loads and their LDS stores (slot + 10 q)
 // LA (linear window average, SCRF_PREC_FASTLIN): the avg block leaves the dense contraction.  The average is linear in
 // the frames, so its share of the score is (C[t] - C[t-d]) / d with C the per-utterance prefix sum of the per-frame
@@ -313,7 +287,6 @@ __host__ __device__ inline uint32_t fu_p_rows(uint32_t D, uint32_t TB) {
 // running float sum and the quotient to float (io/CRF_InFtrStream_SeqMultiWindow.cpp:609-646); this form does not, which
 // makes it a precision tier of its own (measured 3e-8 relative on the gradient against the reference arithmetic; contract 1e-4).
 // Block 5 of the staged P image holds C for the frames t0 - D .. t0 + nfr - 1 (zero rows before the utterance).
-__host__ __device__ inline uint32_t fu_p_rows_la(uint32_t D, uint32_t TB) { return fu_p_rows(D, TB) + TB + D; }
 #define FU_NPQ_LA 15
 
 template <int DMAX, int F32, int DEC, int LA, int DMA>
@@ -395,7 +368,7 @@ __global__ __launch_bounds__(FU_NT, 4) void k_scores_fused(ScrfFusedArgs fa, Scr
     }
   };
   FU_SETPRIO(1);
-  // DMA (the launcher: fa.dma with both tables present): what does not depend on the tile -- the duration table of this output block and the steady-state tile's
+  // DMA (fused_scores_plan: SCRF_SCORES_DMA with both tables present): what does not depend on the tile -- the duration table of this output block and the steady-state tile's
   // records, row bases and rowmap -- leaves for LDS by DMA now, in the round trip of the descriptor and the first lambda
   // slice.  The regions lie outside the operand union; an edge tile overwrites the three tile tables after they landed.
   constexpr bool dma = DMA != 0;
@@ -857,33 +830,6 @@ __global__ __launch_bounds__(FU_NT, 4) void k_scores_fused(ScrfFusedArgs fa, Scr
 #undef FU_OL
 }
 
-static size_t fused_scores_smem_tb(uint32_t W, uint32_t D, uint32_t TB) {
-  const uint32_t nfmax = TB + D - 1;
-  size_t opn = sizeof(float) * (FU_ROWS + 1) * FU_XS + sizeof(double) * FU_GC * FU_WS + sizeof(float) * nfmax * W;
-  const uint32_t npr = fu_p_rows_la(D, TB);   // one tile plan for every form of the kernel
-  const size_t pb = sizeof(double) * npr * FU_DS;
-  if (pb > opn) opn = pb;
-  opn = (opn + 15) & ~(size_t)15;
-  // rbase and rowmap in whole 16-byte chunks (the kernel's layout = k_tile_tables' layout in memory).  The spare at the
-  // end shrinks by what that padding took over 4-entry padding (0, 8 or 16 of its 16 bytes), so the total -- and with it
-  // the tile plan -- is what it was before the tables were padded.
-  const size_t t4 = sizeof(uint16_t) * (((TB + 3) & ~3u) + ((npr + 3) & ~3u));
-  const size_t t8 = sizeof(uint16_t) * (((TB + 7) & ~7u) + ((npr + 7) & ~7u));
-  const size_t spare = 16 - (t8 - t4);
-  return opn + sizeof(double) * D * FU_DS + sizeof(uint4) * FU_ROWS + t8 + (FU_EXPTAB ? sizeof(double) * FU_EXPT_N : 0) + spare;
-}
-// frames per score tile: as many whole frames as give <= 256 rows and keep the workgroup's LDS
-// (the staged P rows grow with TB + D - 1) within 80 KB, i.e. two workgroups per CU; 0 = no fit
-uint32_t fused_scores_tb(uint32_t W, uint32_t D) {
-  for (uint32_t TB = FU_ROWS / D; TB >= 1; TB--)
-    if (fused_scores_smem_tb(W, D, TB) <= 80 * 1024) return TB;
-  // long durations with wide frames (D = 32 at W = 39): one workgroup per CU, as many frames as fit
-  for (uint32_t TB = FU_ROWS / D; TB >= 1; TB--)
-    if (fused_scores_smem_tb(W, D, TB) <= 156 * 1024) return TB;
-  return 0;
-}
-static size_t fused_scores_smem(uint32_t W, uint32_t D) { return fused_scores_smem_tb(W, D, fused_scores_tb(W, D)); }
-
 // dtab[y][d][FU_DS]: one-hot duration weight + bias term of output 48 y + o (slots 0..47; -1e300 past n_out), 1/(d+1) in
 // slot 48 -- what k_scores_fused stages per tile, built once per launch
 __global__ void k_dur_table(ScrfLayout lay, uint32_t W, const double* __restrict__ lambda, double* __restrict__ dtab) {
@@ -938,62 +884,61 @@ __global__ void k_tile_tables(uint32_t D, uint32_t TB, int la, unsigned char* __
     mg[r] = (uint16_t)((la ? 6 : 5) * (pf0[k] + r - prow0[k] + 1) + k);
   }
 }
-size_t fused_tile_table_bytes(uint32_t D, uint32_t TB) {
-  return sizeof(uint4) * FU_ROWS + sizeof(uint16_t) * (((TB + 7) & ~7u) + ((fu_p_rows_la(D, TB) + 7) & ~7u)) + 64;
-}
 void launch_tile_tables(hipStream_t st, uint32_t D, uint32_t TB, int la, void* rtab) {
   hipLaunchKernelGGL(k_tile_tables, dim3(1), dim3(256), 0, st, D, TB, la, (unsigned char*)rtab);
 }
-size_t fused_dur_table_doubles(const ScrfLayout& lay) { return (size_t)((lay.L + 47) / 48) * lay.D * FU_DS; }
 void launch_dur_table(hipStream_t st, const ScrfLayout& lay, uint32_t W, const double* lambda, double* dtab) {
   hipLaunchKernelGGL(k_dur_table, dim3((lay.L + 47) / 48), dim3(256), 0, st, lay, W, lambda, dtab);
 }
 
+static_assert(sizeof(uint4) == FU_REC_BYTES, "row record of the score tile");
+static_assert(SCRF_FUSED_LDS_BYTES == SCRF_LDS_BYTES, "the plan header's LDS size");
 template <int DMAX, int F32, int DEC, int LA, int DMA>
-static void launch_scores_fused_d(hipStream_t st, const ScrfFusedArgs& fa, const ScrfLayout& lay, const double* lambda,
-                                  const double* P, uint64_t n_tiles, double* S, double* smax, double* s_true,
+static void launch_scores_fused_d(hipStream_t st, const ScrfFusedScoresPlan& p, const ScrfFusedArgs& fa, const ScrfLayout& lay,
+                                  const double* lambda, const double* P, uint64_t n_tiles, double* S, double* smax, double* s_true,
                                   const uint32_t* labels, const ScrfDecodeOut& dz) {
-  const size_t sm = fused_scores_smem(fa.W, lay.D);
-  dim3 grid((uint32_t)n_tiles, (lay.L + 47) / 48);
-  hipFuncSetAttribute((const void*)k_scores_fused<DMAX, F32, DEC, LA, DMA>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sm);
-  hipLaunchKernelGGL((k_scores_fused<DMAX, F32, DEC, LA, DMA>), grid, dim3(FU_NT), sm, st, fa, lay, lambda, P, lay.L, S, smax,
+  dim3 grid((uint32_t)n_tiles, p.gy);
+  hipFuncSetAttribute((const void*)k_scores_fused<DMAX, F32, DEC, LA, DMA>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)p.lds);
+  hipLaunchKernelGGL((k_scores_fused<DMAX, F32, DEC, LA, DMA>), grid, dim3(p.threads), p.lds, st, fa, lay, lambda, P, lay.L, S, smax,
                      s_true, labels, dz);
 }
-// the LDS-DMA form copies both launch tables, so it needs both
-template <int DMAX, int F32, int DEC, int LA>
-static void launch_scores_fused_t(hipStream_t st, const ScrfFusedArgs& fa, const ScrfLayout& lay, const double* lambda,
-                                  const double* P, uint64_t n_tiles, double* S, double* smax, double* s_true,
+// from the plan's fields to the instantiation (the forms that exist: fp64, f32, la and decode, each with and without DMA)
+template <int DMAX>
+static void launch_scores_fused_t(hipStream_t st, const ScrfFusedScoresPlan& p, const ScrfFusedArgs& fa, const ScrfLayout& lay,
+                                  const double* lambda, const double* P, uint64_t n_tiles, double* S, double* smax, double* s_true,
                                   const uint32_t* labels, const ScrfDecodeOut& dz) {
-  if (fa.dma && fa.dtab && fa.rtab) launch_scores_fused_d<DMAX, F32, DEC, LA, 1>(st, fa, lay, lambda, P, n_tiles, S, smax, s_true, labels, dz);
-  else launch_scores_fused_d<DMAX, F32, DEC, LA, 0>(st, fa, lay, lambda, P, n_tiles, S, smax, s_true, labels, dz);
+#define FS_CASE(F32, DEC, LA, DMA) \
+  case (F32) * 8 + (DEC) * 4 + (LA) * 2 + (DMA): launch_scores_fused_d<DMAX, F32, DEC, LA, DMA>(st, p, fa, lay, lambda, P, n_tiles, S, smax, s_true, labels, dz); break
+  switch (p.f32 * 8 + p.dec * 4 + p.la * 2 + p.dma) {
+    FS_CASE(0, 0, 0, 0); FS_CASE(0, 0, 0, 1);
+    FS_CASE(1, 0, 0, 0); FS_CASE(1, 0, 0, 1);
+    FS_CASE(0, 0, 1, 0); FS_CASE(0, 0, 1, 1);
+    FS_CASE(0, 1, 0, 0); FS_CASE(0, 1, 0, 1);
+  }
+#undef FS_CASE
+}
+static void launch_scores_fused_p(hipStream_t st, const ScrfFusedScoresPlan& p, const ScrfFusedArgs& fa, const ScrfLayout& lay,
+                                  const double* lambda, const double* P, uint64_t n_tiles, double* S, double* smax, double* s_true,
+                                  const uint32_t* labels, const ScrfDecodeOut& dz) {
+  if (n_tiles == 0) return;
+  switch (p.dmax) {
+    case 12: launch_scores_fused_t<12>(st, p, fa, lay, lambda, P, n_tiles, S, smax, s_true, labels, dz); break;
+    case 25: launch_scores_fused_t<25>(st, p, fa, lay, lambda, P, n_tiles, S, smax, s_true, labels, dz); break;
+    case 40: launch_scores_fused_t<40>(st, p, fa, lay, lambda, P, n_tiles, S, smax, s_true, labels, dz); break;
+  }
 }
 
-// la (SCRF_PREC_FASTLIN, fp64 only): P carries 6 groups per frame, the sixth summed along the utterance (k_avg_prefix)
-void launch_scores_fused(hipStream_t st, const ScrfFusedArgs& fa, const ScrfLayout& lay, const double* lambda,
-                         const double* P, uint64_t n_tiles, double* S, int f32, double* smax, double* s_true,
-                         const uint32_t* labels, int la) {
-  if (n_tiles == 0) return;
-  if (lay.L > 48) smax = nullptr;   // a row spans several workgroups: the caller runs k_exp_rows instead
+// p: fused_scores_plan of the launch (fa.TB = p.tb).  smax is used only where p.smax says the epilogue can form it.
+void launch_scores_fused(hipStream_t st, const ScrfFusedScoresPlan& p, const ScrfFusedArgs& fa, const ScrfLayout& lay, const double* lambda,
+                         const double* P, uint64_t n_tiles, double* S, double* smax, double* s_true, const uint32_t* labels) {
   ScrfDecodeOut off;
   memset(&off, 0, sizeof(off));
-#define FS_GO(N)                                                                        \
-  do {                                                                                  \
-    if (la) launch_scores_fused_t<N, 0, 0, 1>(st, fa, lay, lambda, P, n_tiles, S, smax, s_true, labels, off); \
-    else if (f32) launch_scores_fused_t<N, 1, 0, 0>(st, fa, lay, lambda, P, n_tiles, S, smax, s_true, labels, off);   \
-    else launch_scores_fused_t<N, 0, 0, 0>(st, fa, lay, lambda, P, n_tiles, S, smax, s_true, labels, off);       \
-  } while (0)
-  if (lay.D <= 12) FS_GO(12);
-  else if (lay.D <= 25) FS_GO(25);
-  else FS_GO(40);
-#undef FS_GO
+  launch_scores_fused_p(st, p, fa, lay, lambda, P, n_tiles, S, p.smax ? smax : nullptr, s_true, labels, off);
 }
 
-void launch_scores_fused_decode(hipStream_t st, const ScrfFusedArgs& fa, const ScrfLayout& lay, const double* lambda,
-                                const double* P, uint64_t n_tiles, const ScrfDecodeOut& dz) {
-  if (n_tiles == 0) return;
-  if (lay.D <= 12) launch_scores_fused_t<12, 0, 1, 0>(st, fa, lay, lambda, P, n_tiles, nullptr, nullptr, nullptr, nullptr, dz);
-  else if (lay.D <= 25) launch_scores_fused_t<25, 0, 1, 0>(st, fa, lay, lambda, P, n_tiles, nullptr, nullptr, nullptr, nullptr, dz);
-  else launch_scores_fused_t<40, 0, 1, 0>(st, fa, lay, lambda, P, n_tiles, nullptr, nullptr, nullptr, nullptr, dz);
+void launch_scores_fused_decode(hipStream_t st, const ScrfFusedScoresPlan& p, const ScrfFusedArgs& fa, const ScrfLayout& lay,
+                                const double* lambda, const double* P, uint64_t n_tiles, const ScrfDecodeOut& dz) {
+  launch_scores_fused_p(st, p, fa, lay, lambda, P, n_tiles, nullptr, nullptr, nullptr, nullptr, dz);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -1220,31 +1165,15 @@ __global__ __launch_bounds__(384) void k_lin_z5(ScrfLayout lay, ScrfBatchView bv
   else if (wave == 4) lz5_role<4, DMAX>(rows, Ru, Zu + 4 * (size_t)L, dout, lay, T, fa, fb, ocols, o, act, lane);
   else lz5_role<5, DMAX>(rows, Ru, Zu, dout, lay, T, fa, fb, ocols, o, act, lane);
 }
-// frame segments per utterance so that the launch has about 1024 workgroups, none shorter than 2 D frames
-uint32_t lin_z5_segments(uint32_t n_utts, uint32_t L, uint32_t D, uint32_t t_max, int* seg_len) {
-  const uint64_t wgs = (uint64_t)n_utts * ((L + 63) / 64);
-  uint32_t want = wgs >= 1024 ? 1 : (uint32_t)((1024 + wgs - 1) / wgs);
-  int sl = (int)((t_max + want - 1) / (want ? want : 1));
-  if (sl < (int)(2 * D)) sl = (int)(2 * D);
-  if (sl < 1) sl = 1;
-  *seg_len = sl;
-  const uint32_t nz = (t_max + sl - 1) / sl;
-  return nz ? nz : 1;
-}
-void launch_lin_z5(hipStream_t st, const ScrfLayout& lay, ScrfBatchView bv, uint32_t u0, uint32_t n_utts, uint32_t t_max, uint64_t n_frames,
+// p: fused_lin_z5_plan of the chunk
+void launch_lin_z5(hipStream_t st, const ScrfFusedWalkPlan& p, const ScrfLayout& lay, ScrfBatchView bv, uint32_t u0, uint64_t n_frames,
                    const double* R, double* Z, double* dslab) {
-  if (n_utts == 0) return;
-  int seg_len = 0;
-  const uint32_t nz = lin_z5_segments(n_utts, lay.L, lay.D, t_max, &seg_len);
-  if (nz > 1) hipMemsetAsync(Z, 0, sizeof(double) * n_frames * 5 * lay.L, st);
-  dim3 grid(n_utts, (lay.L + 63) / 64, nz);
-#define LZ5_GO(N) hipLaunchKernelGGL(k_lin_z5<N>, grid, dim3(384), 0, st, lay, bv, u0, R, Z, dslab, seg_len)
-  if (lay.D <= 8) LZ5_GO(8);
-  else if (lay.D <= 16) LZ5_GO(16);
-  else if (lay.D <= 25) LZ5_GO(25);
-  else if (lay.D <= 32) LZ5_GO(32);
-  else LZ5_GO(40);
-#undef LZ5_GO
+  if (p.gx == 0) return;
+  if (p.clear_z) hipMemsetAsync(Z, 0, sizeof(double) * n_frames * 5 * lay.L, st);
+  dim3 grid(p.gx, p.gy, p.nz);
+#define LZ5_CASE(N) case N: hipLaunchKernelGGL(k_lin_z5<N>, grid, dim3(384), 0, st, lay, bv, u0, R, Z, dslab, p.seg_len); break
+  switch (p.dmax) { LZ5_CASE(8); LZ5_CASE(16); LZ5_CASE(25); LZ5_CASE(32); LZ5_CASE(40); }
+#undef LZ5_CASE
 }
 
 // k_add_p_exp (hybrid path: materialised dense statistics, L <= 256): the sampled blocks' share of the scores,
@@ -1315,14 +1244,11 @@ void launch_add_p_exp(hipStream_t st, const ScrfLayout& lay, ScrfBatchView bv, c
 void launch_lin_z(hipStream_t st, const ScrfLayout& lay, ScrfBatchView bv, uint32_t u0, uint32_t n_utts,
                   const double* R, double* Z) {
   if (n_utts == 0) return;
-  dim3 grid(n_utts, (lay.L + 63) / 64);
-#define LZ_GO(N) hipLaunchKernelGGL(k_lin_z<N>, grid, dim3(64), 0, st, lay, bv, u0, R, Z)
-  if (lay.D <= 8) LZ_GO(8);
-  else if (lay.D <= 16) LZ_GO(16);
-  else if (lay.D <= 25) LZ_GO(25);
-  else if (lay.D <= 32) LZ_GO(32);
-  else LZ_GO(40);
-#undef LZ_GO
+  const ScrfFusedWalkPlan p = fused_lin_z_plan(fused_shape(lay), n_utts);
+  dim3 grid(p.gx, p.gy);
+#define LZ_CASE(N) case N: hipLaunchKernelGGL(k_lin_z<N>, grid, dim3(64), 0, st, lay, bv, u0, R, Z); break
+  switch (p.dmax) { LZ_CASE(8); LZ_CASE(16); LZ_CASE(25); LZ_CASE(32); LZ_CASE(40); }
+#undef LZ_CASE
 }
 
 // ------------------------------------------------------------------------------------------
@@ -1333,7 +1259,6 @@ void launch_lin_z(hipStream_t st, const ScrfLayout& lay, ScrfBatchView bv, uint3
 // A wavefront owns 80 outputs (5 MFMA tiles).  k_pframe keeps its slice of lambda in registers and
 // streams 16-frame tiles; k_ztf streams its frame range four frames at a time.
 // ------------------------------------------------------------------------------------------
-#define PF_MT 4      // output tiles per wavefront (64 outputs)
 template <int KS>   // k-steps: ceil(W / 4)
 __global__ __launch_bounds__(64) void k_pframe(const float* __restrict__ F, uint32_t W, uint64_t n_frames,
                                                uint64_t frames_per_wave, const double* __restrict__ lambda,
@@ -1405,19 +1330,12 @@ __global__ __launch_bounds__(64) void k_pframe(const float* __restrict__ F, uint
 void launch_pframe(hipStream_t st, const float* F, uint32_t W, uint64_t n_frames, const double* lambda,
                    const ScrfLayout& lay, uint32_t n_out, double* P) {
   if (n_frames == 0) return;
-  // about 2048 wavefronts per output group, whole pairs of 16-frame tiles each
-  uint64_t fpw = ((n_frames + 2047) / 2048 + 31) & ~31ull;
-  if (fpw < 64) fpw = 64;
-  dim3 grid((uint32_t)((n_frames + fpw - 1) / fpw), (n_out + 16 * PF_MT - 1) / (16 * PF_MT));
-  const uint32_t ks = (W + 3) / 4;
-#define PF_GO(N) hipLaunchKernelGGL(k_pframe<N>, grid, dim3(64), 0, st, F, W, n_frames, fpw, lambda, lay, n_out, P)
-  if (ks <= 4) PF_GO(4);
-  else if (ks <= 10) PF_GO(10);
-  else if (ks <= 16) PF_GO(16);
-  else PF_GO(20);
-#undef PF_GO
+  const ScrfPframePlan p = fused_pframe_plan(W, n_frames, n_out);
+  dim3 grid(p.gx, p.gy);
+#define PF_CASE(N) case N: hipLaunchKernelGGL(k_pframe<N>, grid, dim3(64), 0, st, F, W, n_frames, p.fpw, lambda, lay, n_out, P); break
+  switch (p.ks) { PF_CASE(4); PF_CASE(10); PF_CASE(16); PF_CASE(20); }
+#undef PF_CASE
 }
-int pframe_supported(uint32_t W) { return W <= 80; }
 
 // k_avg_prefix (SCRF_PREC_FASTLIN): group 5 of P (the projection of every frame on the avg weights) summed in place along
 // each utterance, C[f][o] = sum_{f' <= f} Q[f'][o].  One wavefront per (utterance, 64 outputs), eight frames' loads in
@@ -1516,20 +1434,14 @@ __global__ __launch_bounds__(64) void k_ztf(const double* __restrict__ Zm, uint3
 void launch_ztf(hipStream_t st, const double* Zm, uint32_t n_out, const float* F, uint32_t W, uint64_t n_frames,
                 uint64_t rows_per_chunk, uint32_t n_chunks, double* slab, int narrow) {
   if (n_frames == 0 || n_chunks == 0) return;
-  const uint32_t mt = narrow ? 1 : 4;
-  dim3 grid(n_chunks, (n_out + 16 * mt - 1) / (16 * mt));
-  const uint32_t nt = (W + 15) / 16;
-#define ZT_GO(N)                                                                                                           \
-  do {                                                                                                                     \
-    if (narrow) hipLaunchKernelGGL((k_ztf<N, 1>), grid, dim3(64), 0, st, Zm, n_out, F, W, n_frames, rows_per_chunk, slab);  \
-    else hipLaunchKernelGGL((k_ztf<N, 4>), grid, dim3(64), 0, st, Zm, n_out, F, W, n_frames, rows_per_chunk, slab);         \
-  } while (0)
-  if (nt <= 1) ZT_GO(1);
-  else if (nt == 2) ZT_GO(2);
-  else if (nt == 3) ZT_GO(3);
-  else if (nt == 4) ZT_GO(4);
-  else ZT_GO(5);
-#undef ZT_GO
+  const ScrfZtfPlan p = fused_ztf_plan(W, n_out, n_chunks, narrow);
+  dim3 grid(p.gx, p.gy);
+#define ZT_CASE(N, MT) case (N) * 8 + (MT): hipLaunchKernelGGL((k_ztf<N, MT>), grid, dim3(64), 0, st, Zm, n_out, F, W, n_frames, rows_per_chunk, slab); break
+  switch (p.nt * 8 + p.mt) {
+    ZT_CASE(1, 1); ZT_CASE(2, 1); ZT_CASE(3, 1); ZT_CASE(4, 1); ZT_CASE(5, 1);
+    ZT_CASE(1, 4); ZT_CASE(2, 4); ZT_CASE(3, 4); ZT_CASE(4, 4); ZT_CASE(5, 4);
+  }
+#undef ZT_CASE
 }
 
 // ------------------------------------------------------------------------------------------
@@ -1965,41 +1877,18 @@ void launch_post_z(hipStream_t st, const ScrfKnobs& kn, const ScrfLayout& lay, S
                    const double* smax, const ScrfDpLin& o, const double* zx, double* numer_f, int* status, double* Z,
                    double* mass_s, int la, uint32_t t_max, uint64_t n_frames) {
   if (n_utts == 0) return;
-  dim3 grid(n_utts, (lay.L + 63) / 64);
-  // few wavefronts (a small minibatch): several segments per utterance, about four wavefronts per CU in all (half the
-  // kernel's occupancy), no segment shorter than 2 D frames (SCRF_POSTZ_SPLIT=0: never).  Config 3, 256 utterances:
-  // 1.21 -> 0.50 ms; config 2's shape at 64 utterances: 1.90 -> 0.38 ms
-  int seg_len = 0;
-  uint32_t nz = 1;
-  const uint64_t waves = (uint64_t)grid.x * grid.y;
-  if (kn.postz_split && waves <= 2 * 256 && t_max >= 4 * lay.D) {
-    const uint32_t want = (uint32_t)((4 * 256 + waves - 1) / waves);
-    seg_len = (int)((t_max + want - 1) / want);
-    if (seg_len < (int)(2 * lay.D)) seg_len = (int)(2 * lay.D);
-    nz = (uint32_t)((t_max + seg_len - 1) / seg_len);
-  }
-  if (nz > 1) {
-    grid.z = nz;
-    hipMemsetAsync(Z, 0, sizeof(double) * n_frames * (size_t)(la ? 6 : 5) * lay.L, st);
-  }
-#define PZ_GO3(N, A, R)                                                                                                           \
-  do {                                                                                                                            \
-    if (nz > 1) hipLaunchKernelGGL((k_post_z<N, A, R, 1>), grid, dim3(64), 0, st, lay, bv, u0, next_lab, s_true, M, m_per_frame, ES, smax, o, zx, numer_f, status, Z, mass_s, seg_len); \
-    else hipLaunchKernelGGL((k_post_z<N, A, R, 0>), grid, dim3(64), 0, st, lay, bv, u0, next_lab, s_true, M, m_per_frame, ES, smax, o, zx, numer_f, status, Z, mass_s, 0); \
-  } while (0)
-#define PZ_GO(N)                                              \
-  do {                                                        \
-    if (la && lay.L <= 48) PZ_GO3(N, 1, 48);                  \
-    else if (la) PZ_GO3(N, 1, 64);                            \
-    else PZ_GO3(N, 0, 64);                                    \
-  } while (0)
-  if (lay.D <= 8) PZ_GO(8);
-  else if (lay.D <= 16) PZ_GO(16);
-  else if (lay.D <= 25) PZ_GO(25);
-  else if (lay.D <= 32) PZ_GO(32);
-  else PZ_GO(40);
-#undef PZ_GO
-#undef PZ_GO3
+  const ScrfFusedWalkPlan p = fused_post_z_plan(kn, fused_shape(lay), n_utts, la, t_max);
+  dim3 grid(p.gx, p.gy, p.nz);
+  if (p.clear_z) hipMemsetAsync(Z, 0, sizeof(double) * n_frames * (size_t)(la ? 6 : 5) * lay.L, st);
+  // the forms that exist: (LA, RW) = (0, 64), (1, 48), (1, 64), each in one piece and split
+#define PZ_CASE(N, A, R, SP)                \
+  case ((N) * 2 + (A)) * 256 + (R) * 2 + (SP): \
+    hipLaunchKernelGGL((k_post_z<N, A, R, SP>), grid, dim3(64), 0, st, lay, bv, u0, next_lab, s_true, M, m_per_frame, ES, smax, o, zx, numer_f, status, Z, mass_s, p.seg_len); \
+    break
+#define PZ_CASES(N) PZ_CASE(N, 0, 64, 0); PZ_CASE(N, 0, 64, 1); PZ_CASE(N, 1, 48, 0); PZ_CASE(N, 1, 48, 1); PZ_CASE(N, 1, 64, 0); PZ_CASE(N, 1, 64, 1)
+  switch ((p.dmax * 2 + p.la) * 256 + p.rw * 2 + p.split) { PZ_CASES(8); PZ_CASES(16); PZ_CASES(25); PZ_CASES(32); PZ_CASES(40); }
+#undef PZ_CASES
+#undef PZ_CASE
 }
 
 // ------------------------------------------------------------------------------------------
@@ -2013,7 +1902,6 @@ void launch_post_z(hipStream_t st, const ScrfKnobs& kn, const ScrfLayout& lay, S
 // the partial sums stay in registers for the whole launch.  The k-loop is software pipelined by
 // hand: operands of step ks+1 are in flight while the MFMAs of step ks issue.
 // ------------------------------------------------------------------------------------------
-#define FE_NT 256
 #define FE_NRP 15       // R elements per thread in prefetch registers (76*48 / 256, rounded up)
 #define FE_NFP 6        // raw-frame floats per thread held in prefetch registers
 
@@ -2272,7 +2160,6 @@ __global__ __launch_bounds__(FE_NT, 2) void k_expf_fused(ScrfFusedArgs fa, ScrfL
 // (15 LDS reads per tile at config 2) -- an exact re-association, and 26 of the 143 dense columns less for the MFMAs.
 // G0 = first dense group: 0 = [avg | max | min], 1 = [max | min] (SCRF_PREC_FASTLIN: the average goes through Z_avg).
 // Outputs: slab[block][o][(3 - G0) W] and dslab[block][o][D + bias].
-#define FW_NT 512
 #define FW_DSL 5        // duration slots: producer threads 0..239 = (ol = ptid % 48, ds = ptid / 48)
 #ifndef FW_DMA_NT
 #define FW_DMA_NT 1     // cache policy of the R tile's LDS-DMA loads: 1 = nt (R is read once, as on the register path)
@@ -2606,206 +2493,70 @@ __global__ __launch_bounds__(FW_NT) __attribute__((amdgpu_num_vgpr(208))) void k
   expf_fused_ws_body<NT, DMAX, NKS, G0, ROWS, DMA>(fa, lay, R, n_out, n_tiles, n_ct, slab, dslab);
 }
 
-// column tiles needed, and the row stride of the kernel instantiation that serves them (NCT * 16)
-static uint32_t fused_expf_xs(const ScrfLayout& lay, uint32_t W, uint32_t* n_ct) {
-  const uint32_t ncol = 3 * W + lay.D + (lay.use_sb ? 1 : 0);
-  *n_ct = (ncol + 15) / 16;
-  return (*n_ct <= 5 ? 5 : *n_ct <= 9 ? 9 : 13) * 16;
-}
-// the wave-specialised kernel: dense groups only (g0 = 1: without the average); zb: one statistic per workgroup column
-static uint32_t fused_expf_ws_xs(uint32_t W, int g0, int zb, uint32_t* n_ct) {
-  const uint32_t ncol = zb ? W : (3 - g0) * W;
-  *n_ct = (ncol + 15) / 16;
-  return (*n_ct <= 5 ? 5 : *n_ct <= 9 ? 9 : 13) * 16;
-}
 
-// Expected-count tiles are whole frames: as many as give <= 76 rows (what two workgroups per CU can hold at config 2);
-// the depth the kernel runs is the next of 52 / 64 / 76 rows (rows past the tile are staged as zeros).
-// D = 25: 3 frames, 75 rows in 76; D = 10: 7 frames, 70 in 76.
-uint32_t fused_expf_frames(uint32_t D) { return D >= FE_ROWS ? 1u : FE_ROWS / D; }
-static uint32_t fused_expf_nks(uint32_t D) {
-  const uint32_t rows = fused_expf_frames(D) * D;
-  return rows <= 52 ? 13u : rows <= 64 ? 16u : 19u;
-}
-// most raw frames a tile can need (t_last - f0 + 1)
-static uint32_t fused_expf_nfmax(uint32_t D) { return fused_expf_frames(D) + D - 1; }
-static size_t fused_expf_smem(const ScrfLayout& lay, uint32_t W) {
-  uint32_t n_ct;
-  const uint32_t xs = fused_expf_xs(lay, W, &n_ct);
-  return sizeof(float) * (FE_ROWS + 1) * xs + sizeof(double) * FE_ROWS * FE_RS +
-         sizeof(float) * fused_expf_nfmax(lay.D) * W + 64;
-}
-// the single-role count kernel (all dense columns + one-hot + bias in one image; FAST32, SCRF_EXPF_WS=0)
-static bool fused_expf_plain_fits(const ScrfLayout& lay, uint32_t W) {
-  uint32_t n_ct;
-  fused_expf_xs(lay, W, &n_ct);
-  return n_ct <= 13 && fused_expf_smem(lay, W) <= 156 * 1024;   // above 80 KB: one workgroup per CU instead of two
-}
-
-// the wave-specialised kernel (one 512-thread workgroup per CU, two image pairs in LDS) serves the fp64 form whenever
-// its LDS fits; SCRF_EXPF_WS=0 switches it off (A/B measurements).  Rows per tile: 100 when g0 = 1 and the narrower
-// column image lets two pairs of that height into 160 KB (its own tile list, built with the batch), else 76.
-// Wide streams (config 3: W = 144, config 5: W = 123) do not fit (3 - g0) W columns into 13 column tiles / 160 KB: the
-// launch is then z-blocked, one statistic per workgroup column (W <= 208).
-#define FW_ROWS_BIG 100
-static size_t fused_expf_ws_smem_rows(uint32_t W, int g0, int zb, uint32_t rows) {
-  uint32_t n_ct;
-  const uint32_t xs = fused_expf_ws_xs(W, g0, zb, &n_ct);
-  return 2 * (sizeof(float) * (rows + 1) * xs + sizeof(double) * rows * FE_RS);
-}
-static bool fused_expf_ws_fits(uint32_t W, int g0, int zb) {
-  uint32_t n_ct;
-  fused_expf_ws_xs(W, g0, zb, &n_ct);
-  return n_ct <= 13 && fused_expf_ws_smem_rows(W, g0, zb, FE_ROWS) <= SCRF_LDS_BYTES;
-}
-static int fused_expf_ws_zb(uint32_t W, int g0) { return !fused_expf_ws_fits(W, g0, 0) && fused_expf_ws_fits(W, g0, 1) ? 1 : 0; }
-// The R tiles go to LDS by DMA (16-byte pieces) when every output pair of R is 16-byte aligned: an even row length
-// (and an aligned base, checked at the launch); odd L keeps the register path.  SCRF_EXPF_DMA=0 forces the register
-// path (A/B measurements, tests).
-static bool fused_expf_dma(const ScrfKnobs& kn, uint32_t L) { return kn.expf_dma && !(L & 1); }
-static uint32_t fused_expf_ws_rows(const ScrfKnobs& kn, uint32_t W, int g0) {
-  // Tall tiles only when the side stream is off, or on request (SCRF_EXPF_BIG=1).  On the register path 100-row tiles
-  // take 245 registers and cannot share a SIMD with the side stream's narrow k_ztf (29.22 against 29.46 ms for the
-  // 76-row form with that overlap; without the side stream 29.54 against 29.43).  On the DMA path both heights fit
-  // beside k_ztf (178 / 184 registers) and the tall form is the faster kernel (5.8 against 6.3 ms), but a 100-row tile
-  // list deals other rows to each workgroup's slab, so the counts come out in another summation order (2e-15 relative
-  // on the weights after five steps): the default keeps the order the 76-row list gives.
-  uint32_t n_ct;
-  fused_expf_ws_xs(W, g0, 0, &n_ct);
-  return (kn.expf_big && g0 == 1 && n_ct <= 5 && !fused_expf_ws_zb(W, g0) && fused_expf_ws_smem_rows(W, g0, 0, FW_ROWS_BIG) <= SCRF_LDS_BYTES) ? FW_ROWS_BIG : FE_ROWS;
-}
-static bool fused_expf_ws(const ScrfKnobs& kn, const ScrfLayout& lay, uint32_t W, int f32, int g0) {
-  return kn.expf_ws && !f32 && (fused_expf_ws_fits(W, g0, 0) || fused_expf_ws_fits(W, g0, 1));
-}
-
-// f32: FAST32 runs the single-role count kernel only
-int fused_supported(const ScrfKnobs& kn, const ScrfLayout& lay, uint32_t W, int f32) {
-  if (lay.D < 2 || lay.D > 40 || W < 1) return 0;
-  if (!fused_expf_plain_fits(lay, W) && !fused_expf_ws(kn, lay, W, f32, 0)) return 0;
-  // wide streams with many labels (config 5: W = 123, L = 200, D = 40) are served better by the general path: every
-  // 48-output block of the fused kernels repeats the window scans, the D = 40 forms spill, k_post_z walks four label
-  // groups (measured 253.6 ms fused against 206.4 ms materialised per 128 utterances).  The z-blocked count kernel is for
-  // one label group.
-  if (!fused_expf_plain_fits(lay, W) && lay.L > 64) return 0;
-  // several label groups with the D = 40 forms (k_post_z<40> and the count kernel spill): the hybrid path is faster
-  // (L = 200, D = 40, W = 40, 128 x 1000 frames: 66.8 ms fused, 49.6 ms hybrid; at D <= 25 the fused kernels win: 38.5 vs
-  // 46.5 ms at L = 200, W = 39)
-  if (lay.L > 64 && lay.D > 32) return 0;
-  return fused_scores_tb(W, lay.D) >= 1;
-}
-// SCRF_PREC_FASTLIN needs the wave-specialised count kernel (the only one without the avg group); other shapes run the
-// FAST kernels (the reference's float average) under that precision.  (L > 64: k_post_z keeps one Z_avg ring per
-// 64-output group, which its LDS no longer holds two of per SIMD -- left to FAST.)
-int fused_la_supported(const ScrfKnobs& kn, const ScrfLayout& lay, uint32_t W) {
-  return fused_supported(kn, lay, W, 0) && lay.L <= 64 && fused_expf_ws(kn, lay, W, 0, 1);
-}
-// layout of the count slabs: {dense columns, first dense group, separate duration slab?}, the tile list and its height
-ScrfFusedExpfPlan fused_expf_plan(const ScrfKnobs& kn, const ScrfLayout& lay, uint32_t W, int f32, int la) {
-  ScrfFusedExpfPlan p;
-  p.ws = fused_expf_ws(kn, lay, W, f32, la ? 1 : 0) ? 1 : 0;
-  p.g0 = (p.ws && la) ? 1 : 0;
-  p.ncol = p.ws ? (3 - p.g0) * W : 3 * W + lay.D + (lay.use_sb ? 1 : 0);
-  p.ndur = p.ws ? lay.D + (lay.use_sb ? 1 : 0) : 0;
-  p.rows = p.ws ? fused_expf_ws_rows(kn, W, p.g0) : FE_ROWS;
-  p.tile_list = p.rows == FE_ROWS ? 1 : 2;
-  p.frames = lay.D >= p.rows ? 1u : p.rows / lay.D;
-  p.nz = (p.ws && fused_expf_ws_zb(W, p.g0)) ? (uint32_t)(3 - p.g0) : 1u;
-  return p;
-}
-uint32_t fused_expf_blocks(const ScrfKnobs& kn, const ScrfLayout& lay, uint32_t W, int f32, uint64_t n_tiles, int la) {
-  const uint32_t cap = fused_expf_ws(kn, lay, W, f32, la ? 1 : 0) ? std::min(kn.expf_blocks, 256u) : kn.expf_blocks;   // one workgroup per CU there
-  return (uint32_t)(n_tiles < cap ? n_tiles : cap);
-}
-
+// ---- the count launch: from the plan (fused_expf_plan, scrf_fused_plan.h) to the instantiation
+#define FE_LAUNCH_ARGS hipStream_t st, const ScrfFusedExpfPlan &p, const ScrfFusedArgs &fa, const ScrfLayout &lay, const double *R, uint64_t n_tiles, double *slab, double *dslab
+#define FE_PASS_ARGS st, p, fa, lay, R, n_tiles, slab, dslab
 template <int NT, int DMAX, int NKS, int G0, int ROWS, int DMA>
-static void launch_expf_ws_d(hipStream_t st, const ScrfKnobs& kn, const ScrfFusedArgs& fa, const ScrfLayout& lay, const double* R, uint64_t n_tiles,
-                             uint32_t n_ct, double* slab, double* dslab) {
-  const int zb = fused_expf_ws_zb(fa.W, G0);
-  dim3 grid(fused_expf_blocks(kn, lay, fa.W, 0, n_tiles, G0), (lay.L + 47) / 48, zb ? 3 - G0 : 1);
-  const size_t smw = fused_expf_ws_smem_rows(fa.W, G0, zb, ROWS);
-  if (NT <= 4) {   // the narrow forms leave room for the side stream's kernels
-    hipFuncSetAttribute((const void*)k_expf_fused_ws_n<NT, DMAX, NKS, G0, ROWS, DMA>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smw);
-    hipLaunchKernelGGL((k_expf_fused_ws_n<NT, DMAX, NKS, G0, ROWS, DMA>), grid, dim3(FW_NT), smw, st, fa, lay, R, lay.L, n_tiles, n_ct, slab, dslab);
+static void launch_expf_ws_d(FE_LAUNCH_ARGS) {
+  dim3 grid(fused_expf_blocks(p, n_tiles), p.gy, p.nz);
+  if (fused_expf_ws_capped(NT)) {   // (= p.kernel == SCRF_FK_WS_N; on the template argument, so that the host keeps one entry point per form)
+    hipFuncSetAttribute((const void*)k_expf_fused_ws_n<NT, DMAX, NKS, G0, ROWS, DMA>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)p.lds);
+    hipLaunchKernelGGL((k_expf_fused_ws_n<NT, DMAX, NKS, G0, ROWS, DMA>), grid, dim3(p.threads), p.lds, st, fa, lay, R, lay.L, n_tiles, p.n_ct, slab, dslab);
     return;
   }
-  hipFuncSetAttribute((const void*)k_expf_fused_ws<NT, DMAX, NKS, G0, ROWS, DMA>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smw);
-  hipLaunchKernelGGL((k_expf_fused_ws<NT, DMAX, NKS, G0, ROWS, DMA>), grid, dim3(FW_NT), smw, st, fa, lay, R, lay.L, n_tiles, n_ct, slab, dslab);
+  hipFuncSetAttribute((const void*)k_expf_fused_ws<NT, DMAX, NKS, G0, ROWS, DMA>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)p.lds);
+  hipLaunchKernelGGL((k_expf_fused_ws<NT, DMAX, NKS, G0, ROWS, DMA>), grid, dim3(p.threads), p.lds, st, fa, lay, R, lay.L, n_tiles, p.n_ct, slab, dslab);
 }
-template <int NT, int DMAX, int NKS, int G0, int ROWS>
-static void launch_expf_ws_t(hipStream_t st, const ScrfKnobs& kn, const ScrfFusedArgs& fa, const ScrfLayout& lay, const double* R, uint64_t n_tiles,
-                             uint32_t n_ct, double* slab, double* dslab) {
-  if (fused_expf_dma(kn, lay.L) && ((uintptr_t)R & 15) == 0) launch_expf_ws_d<NT, DMAX, NKS, G0, ROWS, 1>(st, kn, fa, lay, R, n_tiles, n_ct, slab, dslab);
-  else launch_expf_ws_d<NT, DMAX, NKS, G0, ROWS, 0>(st, kn, fa, lay, R, n_tiles, n_ct, slab, dslab);
+template <int NT, int DMAX, int NKS>
+static void launch_expf_ws_t(FE_LAUNCH_ARGS) {
+  switch (p.g0 * 2 + p.dma) {
+    case 0: launch_expf_ws_d<NT, DMAX, NKS, 0, FE_ROWS, 0>(FE_PASS_ARGS); break;
+    case 1: launch_expf_ws_d<NT, DMAX, NKS, 0, FE_ROWS, 1>(FE_PASS_ARGS); break;
+    case 2: launch_expf_ws_d<NT, DMAX, NKS, 1, FE_ROWS, 0>(FE_PASS_ARGS); break;
+    case 3: launch_expf_ws_d<NT, DMAX, NKS, 1, FE_ROWS, 1>(FE_PASS_ARGS); break;
+  }
 }
-
+// the tall tiles: g0 = 1 and 4 slots only
+template <int NT, int DMAX, int NKS>
+static void launch_expf_big_t(FE_LAUNCH_ARGS) {
+  if (p.dma) launch_expf_ws_d<NT, DMAX, NKS, 1, FW_ROWS_BIG, 1>(FE_PASS_ARGS);
+  else launch_expf_ws_d<NT, DMAX, NKS, 1, FW_ROWS_BIG, 0>(FE_PASS_ARGS);
+}
 template <int NT, int DMAX, int F32, int NKS>
-static void launch_expf_fused_t(hipStream_t st, const ScrfKnobs& kn, const ScrfFusedArgs& fa, const ScrfLayout& lay, const double* R,
-                                uint64_t n_tiles, uint32_t n_ct, size_t sm, double* slab) {
-  dim3 grid(fused_expf_blocks(kn, lay, fa.W, F32, n_tiles, 0), (lay.L + 47) / 48);
-  hipFuncSetAttribute((const void*)k_expf_fused<NT, DMAX, F32, NKS>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sm);
-  hipLaunchKernelGGL((k_expf_fused<NT, DMAX, F32, NKS>), grid, dim3(FE_NT), sm, st, fa, lay, R, lay.L, n_tiles, n_ct,
-                     fused_expf_nfmax(lay.D), slab);
+static void launch_expf_fused_d(FE_LAUNCH_ARGS) {
+  dim3 grid(fused_expf_blocks(p, n_tiles), p.gy);
+  hipFuncSetAttribute((const void*)k_expf_fused<NT, DMAX, F32, NKS>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)p.lds);
+  hipLaunchKernelGGL((k_expf_fused<NT, DMAX, F32, NKS>), grid, dim3(p.threads), p.lds, st, fa, lay, R, lay.L, n_tiles, p.n_ct, p.nfmax, slab);
+}
+template <int NT, int DMAX, int NKS>
+static void launch_expf_fused_t(FE_LAUNCH_ARGS) {
+  if (p.f32) launch_expf_fused_d<NT, DMAX, 1, NKS>(FE_PASS_ARGS);
+  else launch_expf_fused_d<NT, DMAX, 0, NKS>(FE_PASS_ARGS);
 }
 
-// slab: [fused_expf_blocks(n_tiles)][L][plan.ncol]; dslab (plan.ndur > 0): [blocks][L][D + bias]
-void launch_expf_fused(hipStream_t st, const ScrfKnobs& kn, const ScrfFusedArgs& fa, const ScrfLayout& lay, const double* R,
-                       uint64_t n_tiles, double* slab, double* dslab, int f32, int la) {
+// p: fused_expf_plan of the launch (the engine keeps it with the chunk: its slabs are laid out by it).
+// slab: [fused_expf_blocks(p, n_tiles)][L][p.ncol]; dslab (p.ndur > 0): [blocks][L][D + bias]
+void launch_expf_fused(FE_LAUNCH_ARGS) {
   if (n_tiles == 0) return;
-  const uint32_t nks = fused_expf_nks(lay.D);
-  // the depths that occur per duration class: D <= 12 always fills more than 64 rows, 13..25 never stops at 52
-#define FE_GO(N)                                                   \
-  do {                                                             \
-    if (lay.D <= 12) FE_GO3(N, 12, 19);                            \
-    else if (lay.D <= 25) {                                        \
-      if (nks == 16) FE_GO3(N, 25, 16); else FE_GO3(N, 25, 19);    \
-    } else {                                                       \
-      if (nks == 13) FE_GO3(N, 40, 13);                            \
-      else if (nks == 16) FE_GO3(N, 40, 16);                       \
-      else FE_GO3(N, 40, 19);                                      \
-    }                                                              \
-  } while (0)
-  const ScrfFusedExpfPlan plan = fused_expf_plan(kn, lay, fa.W, f32, la);
-  if (plan.ws) {
-    uint32_t n_ct;
-    fused_expf_ws_xs(fa.W, plan.g0, plan.nz > 1 ? 1 : 0, &n_ct);
-    if (plan.rows == FW_ROWS_BIG) {
-      // 100-row tiles (g0 = 1, n_ct <= 5): k-steps = ceil(frames * D / 4) rounded up to 21 or 25
-      const uint32_t used = plan.frames * lay.D;
-#define FB_GO(DM)                                                                                                 \
-  do {                                                                                                            \
-    if (used <= 84) launch_expf_ws_t<4, DM, 21, 1, FW_ROWS_BIG>(st, kn, fa, lay, R, n_tiles, n_ct, slab, dslab);  \
-    else launch_expf_ws_t<4, DM, 25, 1, FW_ROWS_BIG>(st, kn, fa, lay, R, n_tiles, n_ct, slab, dslab);             \
-  } while (0)
-      if (lay.D <= 12) FB_GO(12);
-      else if (lay.D <= 25) FB_GO(25);
-      else FB_GO(40);
-#undef FB_GO
-      return;
+#define FE_KEY(N, DM, KS) (((N) * 64 + (DM)) * 64 + (KS))
+#define FE_CASE(GO, N, DM, KS) case FE_KEY(N, DM, KS): GO<N, DM, KS>(FE_PASS_ARGS); break
+  // the depths that occur per duration class (fused_expf_plan)
+#define FE_DEPTHS(GO, N) FE_CASE(GO, N, 12, 19); FE_CASE(GO, N, 25, 16); FE_CASE(GO, N, 25, 19); FE_CASE(GO, N, 40, 13); FE_CASE(GO, N, 40, 16); FE_CASE(GO, N, 40, 19)
+  const int key = FE_KEY(p.nt, p.dmax, p.nks);
+  if (!p.ws) {
+    switch (key) { FE_DEPTHS(launch_expf_fused_t, 4); FE_DEPTHS(launch_expf_fused_t, 7); FE_DEPTHS(launch_expf_fused_t, 10); }
+  } else if (p.tile_list == 2) {
+    switch (key) {
+      FE_CASE(launch_expf_big_t, 4, 12, 21); FE_CASE(launch_expf_big_t, 4, 12, 25); FE_CASE(launch_expf_big_t, 4, 25, 21);
+      FE_CASE(launch_expf_big_t, 4, 25, 25); FE_CASE(launch_expf_big_t, 4, 40, 21); FE_CASE(launch_expf_big_t, 4, 40, 25);
     }
-#define FE_GO3(N, DM, KS)                                                                                   \
-  do {                                                                                                      \
-    if (plan.g0) launch_expf_ws_t<N, DM, KS, 1, FE_ROWS>(st, kn, fa, lay, R, n_tiles, n_ct, slab, dslab);   \
-    else launch_expf_ws_t<N, DM, KS, 0, FE_ROWS>(st, kn, fa, lay, R, n_tiles, n_ct, slab, dslab);           \
-  } while (0)
-    // slots per consumer wavefront = ceil(3 n_ct / 4)
-    if (n_ct <= 5) FE_GO(4);
-    else if (n_ct <= 8) FE_GO(6);
-    else if (n_ct <= 9) FE_GO(7);
-    else FE_GO(10);
-#undef FE_GO3
-    return;
+  } else {
+    switch (key) { FE_DEPTHS(launch_expf_ws_t, 4); FE_DEPTHS(launch_expf_ws_t, 6); FE_DEPTHS(launch_expf_ws_t, 7); FE_DEPTHS(launch_expf_ws_t, 10); }
   }
-  uint32_t n_ct;
-  fused_expf_xs(lay, fa.W, &n_ct);
-  const size_t sm = fused_expf_smem(lay, fa.W);
-#define FE_GO3(N, DM, KS)                                                                             \
-  do {                                                                                                \
-    if (f32) launch_expf_fused_t<N, DM, 1, KS>(st, kn, fa, lay, R, n_tiles, n_ct, sm, slab);          \
-    else launch_expf_fused_t<N, DM, 0, KS>(st, kn, fa, lay, R, n_tiles, n_ct, sm, slab);              \
-  } while (0)
-  if (n_ct <= 5) FE_GO(4);
-  else if (n_ct <= 9) FE_GO(7);
-  else FE_GO(10);
-#undef FE_GO
-#undef FE_GO3
+#undef FE_DEPTHS
+#undef FE_CASE
+#undef FE_KEY
 }
+#undef FE_PASS_ARGS
+#undef FE_LAUNCH_ARGS

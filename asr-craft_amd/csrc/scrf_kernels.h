@@ -5,6 +5,7 @@
 #include "scrf_arcw.h"
 #include "scrf_common.h"
 #include "scrf_knobs.h"
+#include "scrf_fused_plan.h"
 #include "scrf_mfma_plan.h"
 
 #include <vector>
@@ -133,27 +134,12 @@ void launch_gamma_log(hipStream_t st, const ScrfLayout& lay, uint32_t T, const d
                       double* gamma);
 
 // scrf_fused.hip: state contractions with the window synthesis fused in (X never materialised)
-#define SCRF_FUSED_ROWS_SCORES 256
-uint32_t fused_scores_tb(uint32_t W, uint32_t D);   // whole frames per score tile (0: shape not supported)
-#define SCRF_FUSED_ROWS_EXPF 76
-uint32_t fused_expf_frames(uint32_t D);            // whole frames per expected-count tile (<= 76 rows)
-int fused_supported(const ScrfKnobs& kn, const ScrfLayout& lay, uint32_t W, int f32 = 0);
-// SCRF_PREC_FASTLIN (`la`): the window average leaves both dense contractions (prefix sums of a sixth per-frame
-// projection / a sixth group of Z); shapes this returns 0 for run the FAST kernels under that precision
-int fused_la_supported(const ScrfKnobs& kn, const ScrfLayout& lay, uint32_t W);
-// slabs of the fused expected-count kernel: slab [blocks][L][ncol] (dense groups from g0: 0 avg, 1 max) and, when
-// ndur > 0, a separate duration slab [blocks][L][ndur] (one-hot duration counts + bias; wave-specialised kernel)
-// rows / frames: height of the row tiles the kernel walks (whole frames); tile_list: which of the batch's tile lists
-// describes them (1: <= 76 rows, 2: <= 100 rows, built only for batches of an SCRF_PREC_FASTLIN engine)
-struct ScrfFusedExpfPlan { int ws; int g0; uint32_t ncol; uint32_t ndur; uint32_t rows; uint32_t frames; int tile_list; uint32_t nz; };   // nz: workgroup columns of the launch (one dense statistic each when > 1)
-ScrfFusedExpfPlan fused_expf_plan(const ScrfKnobs& kn, const ScrfLayout& lay, uint32_t W, int f32, int la);
-uint32_t fused_expf_blocks(const ScrfKnobs& kn, const ScrfLayout& lay, uint32_t W, int f32, uint64_t n_tiles, int la);   // workgroups (= slabs) of launch_expf_fused, <= 512
-void launch_scores_fused(hipStream_t st, const ScrfFusedArgs& fa, const ScrfLayout& lay, const double* lambda,
-                         const double* P, uint64_t n_tiles, double* S, int f32, double* smax = nullptr,
-                         double* s_true = nullptr, const uint32_t* labels = nullptr, int la = 0);
-size_t fused_tile_table_bytes(uint32_t D, uint32_t TB);
+// (which instantiations the launchers below start, the tile geometry, fused_supported / fused_la_supported and the
+// table sizes: scrf_fused_plan.h; the launchers that take a plan are handed the one the engine made)
+inline ScrfFusedShape fused_shape(const ScrfLayout& l) { return ScrfFusedShape{l.L, l.D, l.use_sb}; }
+void launch_scores_fused(hipStream_t st, const ScrfFusedScoresPlan& p, const ScrfFusedArgs& fa, const ScrfLayout& lay, const double* lambda,
+                         const double* P, uint64_t n_tiles, double* S, double* smax, double* s_true, const uint32_t* labels);
 void launch_tile_tables(hipStream_t st, uint32_t D, uint32_t TB, int la, void* rtab);
-size_t fused_dur_table_doubles(const ScrfLayout& lay);
 void launch_dur_table(hipStream_t st, const ScrfLayout& lay, uint32_t W, const double* lambda, double* dtab);
 void launch_avg_prefix(hipStream_t st, ScrfBatchView bv, uint32_t u0, uint32_t n_utts, uint32_t L, double* P);
 // k_viterbi on float arc weights with one wavefront per utterance (fast decode; L <= 64, constant M)
@@ -161,8 +147,8 @@ int viterbi_fast_supported(const ScrfLayout& lay);
 void launch_viterbi_fast(hipStream_t st, const ScrfKnobs& kn, const ScrfLayout& lay, ScrfBatchView bv, uint32_t u0, uint32_t n_utts,
                          const ScrfArcSrc& src, uint16_t* bp_b, uint16_t* bp_e, uint32_t* out_labels, uint32_t* out_n, float* out_cost);
 // decode mode: float arc weights + the list of entries to recompute (ScrfDecodeOut)
-void launch_scores_fused_decode(hipStream_t st, const ScrfFusedArgs& fa, const ScrfLayout& lay, const double* lambda,
-                                const double* P, uint64_t n_tiles, const ScrfDecodeOut& dz);
+void launch_scores_fused_decode(hipStream_t st, const ScrfFusedScoresPlan& p, const ScrfFusedArgs& fa, const ScrfLayout& lay,
+                                const double* lambda, const double* P, uint64_t n_tiles, const ScrfDecodeOut& dz);
 // w1[o] = sum of |lambda| over label o's state block (features + bias weight)
 void launch_state_l1(hipStream_t st, const double* lambda, const ScrfLayout& lay, double* w1);
 // reference-order recomputation of the listed (row, output) arc weights from the raw frames
@@ -171,13 +157,11 @@ void launch_decode_fixup(hipStream_t st, const float* frames, uint32_t W, ScrfBa
                          uint32_t cap, float* wneg);
 void launch_lin_z(hipStream_t st, const ScrfLayout& lay, ScrfBatchView bv, uint32_t u0, uint32_t n_utts,
                   const double* R, double* Z);
-int pframe_supported(uint32_t W);
 void launch_pframe(hipStream_t st, const float* F, uint32_t W, uint64_t n_frames, const double* lambda,
                    const ScrfLayout& lay, uint32_t n_out, double* P);
 void launch_ztf(hipStream_t st, const double* Zm, uint32_t n_out, const float* F, uint32_t W, uint64_t n_frames,
                 uint64_t rows_per_chunk, uint32_t n_chunks, double* slab, int narrow = 0);
-uint32_t lin_z5_segments(uint32_t n_utts, uint32_t L, uint32_t D, uint32_t t_max, int* seg_len);
-void launch_lin_z5(hipStream_t st, const ScrfLayout& lay, ScrfBatchView bv, uint32_t u0, uint32_t n_utts, uint32_t t_max, uint64_t n_frames,
+void launch_lin_z5(hipStream_t st, const ScrfFusedWalkPlan& p, const ScrfLayout& lay, ScrfBatchView bv, uint32_t u0, uint64_t n_frames,
                    const double* R, double* Z, double* dslab);
 void launch_add_p_exp(hipStream_t st, const ScrfLayout& lay, ScrfBatchView bv, const uint32_t* frame_u, uint32_t u0, uint64_t n_frames,
                       const double* P, double* S, double* smax, double* s_true);
@@ -185,8 +169,8 @@ void launch_post_z(hipStream_t st, const ScrfKnobs& kn, const ScrfLayout& lay, S
                    const uint32_t* next_lab, const double* s_true, const double* M, int m_per_frame, double* ES,
                    const double* smax, const ScrfDpLin& o, const double* zx, double* numer_f, int* status, double* Z,
                    double* mass_s, int la = 0, uint32_t t_max = 0, uint64_t n_frames = 0);
-void launch_expf_fused(hipStream_t st, const ScrfKnobs& kn, const ScrfFusedArgs& fa, const ScrfLayout& lay, const double* R,
-                       uint64_t n_tiles, double* slab, double* dslab, int f32, int la);
+void launch_expf_fused(hipStream_t st, const ScrfFusedExpfPlan& p, const ScrfFusedArgs& fa, const ScrfLayout& lay, const double* R,
+                       uint64_t n_tiles, double* slab, double* dslab);
 
 // ---- STDSEG (scrf_stdseg.hip): lay is the layout over FULL labels (lay.L = nLabs), La = nActualLabs
 void launch_stdseg_rowinfo(hipStream_t st, ScrfBatchView bv, const uint32_t* frame_u, uint32_t u0, uint64_t n_frames,
