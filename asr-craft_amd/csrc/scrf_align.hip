@@ -53,7 +53,6 @@ __device__ inline uint32_t align_backtrace(const uint16_t* __restrict__ bp, cons
 // through ScrfArcView as k_align_group does: with the view its D <= 40 variant measured 0.8 % slower at 4096 utterances x 300
 // frames (profiles/EXPERIMENTS.md), so its body stays as it was.
 // ------------------------------------------------------------------------------------------
-#define AL_WAVES 4
 template <int DMAX>
 __global__ __launch_bounds__(64 * AL_WAVES) void k_align_wave(ScrfLayout lay, ScrfBatchView bv, uint32_t u0, uint32_t n_utts,
                                                               const double* __restrict__ S, const float* __restrict__ Wn,
@@ -184,20 +183,17 @@ __global__ __launch_bounds__(64 * AL_WAVES) void k_align_wave(ScrfLayout lay, Sc
   }
 }
 
-int align_wave_supported(const ScrfLayout& lay) { return lay.D <= 40; }
-
 void launch_align_wave(hipStream_t st, const ScrfLayout& lay, ScrfBatchView bv, uint32_t u0, uint32_t n_utts, const ScrfArcSrc& src,
                        const ScrfAlignArgs& aa, uint32_t* out_labels, uint32_t* out_n, float* out_cost) {
   if (n_utts == 0) return;
-  const size_t sm = sizeof(float) * AL_WAVES * (64 + (size_t)lay.D * 64);   // D <= 40: at most 41 KiB
-  const dim3 grid((n_utts + AL_WAVES - 1) / AL_WAVES), block(64 * AL_WAVES);
-#define AL_GO(N)                                                                                                               \
-  hipLaunchKernelGGL((k_align_wave<N>), grid, block, sm, st, lay, bv, u0, n_utts, src.S, src.Wn, src.M, src.m_per_frame,       \
-                     src.frame_model, aa, out_labels, out_n, out_cost)
-  if (lay.D <= 4) AL_GO(4);
-  else if (lay.D <= 12) AL_GO(12);
-  else AL_GO(40);
-#undef AL_GO
+  const ScrfAlignWavePlan p = align_wave_plan(dp_shape(lay), n_utts);
+#define AL_CASE(N)                                                                                                          \
+  case N:                                                                                                                   \
+    hipLaunchKernelGGL((k_align_wave<N>), dim3(p.gx), dim3(p.threads), p.lds, st, lay, bv, u0, n_utts, src.S, src.Wn, src.M, \
+                       src.m_per_frame, src.frame_model, aa, out_labels, out_n, out_cost);                                  \
+    break
+  switch (p.dmax) { AL_CASE(4); AL_CASE(12); AL_CASE(40); }
+#undef AL_CASE
 }
 
 // ------------------------------------------------------------------------------------------
@@ -311,14 +307,13 @@ __global__ void k_align_group(ScrfLayout lay, ScrfBatchView bv, uint32_t u0, con
   }
 }
 
-size_t align_group_smem_bytes(const ScrfLayout& lay, uint64_t K) { return sizeof(float) * ((size_t)lay.D + 2) * K; }
 
 void launch_align_group(hipStream_t st, const ScrfLayout& lay, ScrfBatchView bv, uint32_t u0, uint32_t n_utts, uint32_t k_max,
                         const ScrfArcSrc& src, const ScrfAlignArgs& aa, uint32_t* out_labels, uint32_t* out_n, float* out_cost) {
   if (n_utts == 0) return;
   int NT = ((int)(k_max ? k_max : 1) + 63) / 64 * 64;
   if (NT > 1024) NT = 1024;
-  const size_t sm = align_group_smem_bytes(lay, k_max ? k_max : 1);   // the chunk's longest transcript
+  const size_t sm = align_group_smem_bytes(dp_shape(lay), k_max ? k_max : 1);   // the chunk's longest transcript
   hipFuncSetAttribute((const void*)k_align_group, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sm);
   hipLaunchKernelGGL(k_align_group, dim3(n_utts), dim3(NT), sm, st, lay, bv, u0, src.S, src.Wn, src.M, src.m_per_frame, src.frame_model,
                      aa, out_labels, out_n, out_cost);

@@ -88,14 +88,13 @@ __global__ __launch_bounds__(256) void k_exp_m_tile(const double* __restrict__ M
 void launch_exp_m(hipStream_t st, const ScrfKnobs& kn, const double* M, uint32_t L, uint64_t n_mat, double* E, double* ET,
                   double* mshift) {
   if (n_mat == 0) return;
-  const uint32_t ne = (L * L + 255) / 256;
-  if (L <= 64 && kn.expm_tile) {
-    if (ne <= 4) hipLaunchKernelGGL(k_exp_m_tile<4>, dim3((uint32_t)n_mat), dim3(256), 0, st, M, L, E, ET, mshift);
-    else if (ne <= 9) hipLaunchKernelGGL(k_exp_m_tile<9>, dim3((uint32_t)n_mat), dim3(256), 0, st, M, L, E, ET, mshift);
-    else hipLaunchKernelGGL(k_exp_m_tile<16>, dim3((uint32_t)n_mat), dim3(256), 0, st, M, L, E, ET, mshift);
-    return;
+  const ScrfExpMPlan p = exp_m_plan(kn, L, n_mat);
+#define EM_CASE(N) case N: hipLaunchKernelGGL(k_exp_m_tile<N>, dim3(p.gx), dim3(p.threads), 0, st, M, L, E, ET, mshift); break
+  switch (p.ne) {
+    case 0: hipLaunchKernelGGL(k_exp_m, dim3(p.gx), dim3(p.threads), 0, st, M, L, E, ET, mshift); break;
+    EM_CASE(4); EM_CASE(9); EM_CASE(16);
   }
-  hipLaunchKernelGGL(k_exp_m, dim3((uint32_t)n_mat), dim3(256), 0, st, M, L, E, ET, mshift);
+#undef EM_CASE
 }
 
 template <int DMAX, int MPF>
@@ -271,34 +270,21 @@ __global__ __launch_bounds__(DP_WPB * 64, 3) void k_dp_wave(
   if (__any(err != 0) && lane == 0) atomicMax(&status[u], SCRF_ERR_NUMERIC);
 }
 
-int dp_wave_supported(const ScrfLayout& lay) { return lay.L <= 64 && lay.D <= 32; }
-
 void launch_dp_wave(hipStream_t st, const ScrfLayout& lay, ScrfBatchView bv, uint32_t u0, uint32_t n_utts,
                     const double* S, const double* E, const double* ET, const double* mshift, int m_per_frame,
                     double* AD, double* alpha_g, double* beta_g, double* sd_g, double* zx, int* status) {
   if (n_utts == 0) return;
-  const uint32_t wpb = dp_waves_per_block(sizeof(double) * (m_per_frame ? 0 : (size_t)lay.L * lay.L), sizeof(double) * (size_t)lay.D * lay.L);
-  const uint32_t nblk = 2 * ((n_utts + wpb - 1) / wpb);
-  const size_t sm = sizeof(double) * ((m_per_frame ? 0 : (size_t)lay.L * lay.L) + (size_t)wpb * lay.D * lay.L);
-#define DP_LAUNCH2(DM, MPF)                                                                                   \
-  do {                                                                                                          \
-    hipFuncSetAttribute((const void*)k_dp_wave<DM, MPF>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sm);  \
-    hipLaunchKernelGGL((k_dp_wave<DM, MPF>), dim3(nblk), dim3(wpb * 64), sm, st, lay, bv, u0, n_utts, S, E, ET, \
-                       mshift, AD, alpha_g, beta_g, sd_g, zx, status);                                          \
-  } while (0)
-#define DP_LAUNCH(DM)                     \
-  do {                                    \
-    if (m_per_frame) DP_LAUNCH2(DM, 1);   \
-    else DP_LAUNCH2(DM, 0);               \
-  } while (0)
-  if (lay.D <= 1) DP_LAUNCH(1);
-  else if (lay.D <= 4) DP_LAUNCH(4);
-  else if (lay.D <= 10) DP_LAUNCH(10);
-  else if (lay.D <= 16) DP_LAUNCH(16);
-  else if (lay.D <= 25) DP_LAUNCH(25);
-  else DP_LAUNCH(32);
-#undef DP_LAUNCH
-#undef DP_LAUNCH2
+  const ScrfDpWavePlan p = dp_wave_plan(dp_shape(lay), n_utts, m_per_frame);
+#define DP_CASE(DM, MPF)                                                                                               \
+  case (DM) * 2 + (MPF):                                                                                               \
+    hipFuncSetAttribute((const void*)k_dp_wave<DM, MPF>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)p.lds);      \
+    hipLaunchKernelGGL((k_dp_wave<DM, MPF>), dim3(p.blocks), dim3(p.threads), p.lds, st, lay, bv, u0, n_utts, S, E, ET, \
+                       mshift, AD, alpha_g, beta_g, sd_g, zx, status);                                                 \
+    break
+#define DP_CASES(DM) DP_CASE(DM, 0); DP_CASE(DM, 1)
+  switch (p.dmax * 2 + p.mpf) { DP_CASES(1); DP_CASES(4); DP_CASES(10); DP_CASES(16); DP_CASES(25); DP_CASES(32); }
+#undef DP_CASES
+#undef DP_CASE
 }
 
 // ------------------------------------------------------------------------------------------
@@ -503,20 +489,14 @@ __global__ __launch_bounds__(64 * RA_G) void k_reduce_atb(const double* __restri
     grad[lay.trans_idx(i / lay.L, i % lay.L) + lay.ntfe] -= lay.tbv * exp(M0[i]) * t;
   }
 }
-int atb_supported(const ScrfLayout& lay) { return lay.L <= 256; }
 void launch_atb(hipStream_t st, const ScrfLayout& lay, const double* A, const double* B, uint64_t n_frames,
                 uint64_t rows_per_chunk, uint32_t n_chunks, double* slab, const double* M0, double* grad,
                 const double* bscale) {
   if (n_frames == 0 || n_chunks == 0 || !lay.use_tb) return;
-  const uint32_t nb = (lay.L + 63) / 64;
-  const dim3 grid((n_chunks + 3) / 4, nb * nb);
-  const uint32_t lt = lay.L > 64 ? 4 : (lay.L + 15) / 16;
-#define ATB_GO(N) hipLaunchKernelGGL(k_atb<N>, grid, dim3(256), 0, st, A, B, lay.L, n_frames, rows_per_chunk, n_chunks, slab, bscale)
-  if (lt <= 1) ATB_GO(1);
-  else if (lt == 2) ATB_GO(2);
-  else if (lt == 3) ATB_GO(3);
-  else ATB_GO(4);
-#undef ATB_GO
+  const ScrfAtbPlan p = atb_plan(dp_shape(lay), n_chunks);
+#define ATB_CASE(N) case N: hipLaunchKernelGGL(k_atb<N>, dim3(p.gx, p.gy), dim3(p.threads), 0, st, A, B, lay.L, n_frames, rows_per_chunk, n_chunks, slab, bscale); break
+  switch (p.lt) { ATB_CASE(1); ATB_CASE(2); ATB_CASE(3); ATB_CASE(4); }
+#undef ATB_CASE
   const uint32_t LL = lay.L * lay.L;
   hipLaunchKernelGGL(k_reduce_atb, dim3((LL + 63) / 64), dim3(64 * RA_G), 0, st, slab, n_chunks, M0, lay, grad);
 }

@@ -368,7 +368,6 @@ __global__ __launch_bounds__(DP_WPB * 64, 3) void k_dp_lin(
 // Round 4: MPF = 1 takes per-frame transition matrices (each wavefront's quarter of the frame's matrix is requested a step
 // ahead into a second register set: 148-182 registers), and the launcher picks that form BY ITSELF when the launch has too
 // few sweeps to fill the chip (launch_dp_lin).
-#define DPV_NW 4
 template <int DMAX, int MPF>
 __global__ __launch_bounds__(64 * DPV_NW, MPF ? 2 : 4) void k_dp_lin_mv(
     ScrfLayout lay, ScrfBatchView bv, uint32_t u0, uint32_t n_utts, const double* __restrict__ ES,
@@ -853,36 +852,6 @@ __global__ __launch_bounds__(256) void k_dp_lin_mw(
   if (__any(err != 0) && lane == 0) atomicMax(&status[u], SCRF_ERR_NUMERIC);
 }
 
-int dplin_mw_supported(const ScrfLayout& lay) { return lay.L > 64 && lay.L <= 256 && lay.D <= 40; }
-// the one-wavefront-per-utterance form (k_dp_lin): L <= 64, D <= 40 (the log-domain k_dp_wave stops at 32)
-int dplin_supported(const ScrfLayout& lay) { return lay.L <= 64 && lay.D <= 40; }
-
-template <int DMAX>
-static void launch_dp_lin_mw_t(hipStream_t st, const ScrfKnobs& kn, const ScrfLayout& lay, ScrfBatchView bv, uint32_t u0, uint32_t n_utts,
-                               const double* ES, const double* smax, const double* E, const double* ET,
-                               const double* mshift, int m_per_frame, const ScrfDpLin& o, double* zx, int* status) {
-  const uint32_t nw = (lay.L + 63) / 64;
-  const size_t sm = sizeof(double) * ((((size_t)lay.D * lay.L + 1) & ~(size_t)1) + 64 * nw + 64 + 64 * nw + 16);
-#define MW_GO(MPF, LR, TAIL)                                                                                                          \
-  do {                                                                                                                                \
-    hipFuncSetAttribute((const void*)k_dp_lin_mw<DMAX, MPF, LR, TAIL>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sm);          \
-    hipLaunchKernelGGL((k_dp_lin_mw<DMAX, MPF, LR, TAIL>), dim3(2 * n_utts), dim3(64 * nw), sm, st, lay, bv, u0, n_utts, ES, smax, E, \
-                       ET, mshift, o.a, o.ga, o.p, o.gp, o.b, o.gb, o.sd, o.gsd, zx, status);                                         \
-  } while (0)
-  // the matrix column in registers (SCRF_DPLIN_EREG=0: from L2 every frame, as before round 4)
-  // Measured (ms per launch, from L2 -> in registers): L = 200, D = 25, 512 x 300 frames 17.6 -> 9.4 (LR = 208: 49 spilled
-  // registers, still a gain); L = 96, D = 25, 1024 utterances 10.2 -> 6.5; L = 128, D = 10: 5.4 -> 4.3.  At DMAX = 40 the
-  // duration step's 80 registers leave room for 128 rows only (L = 200 in full spills 141 registers and LOSES: 13.7 ->
-  // 17.8): there 128 rows live in registers and the rest comes from L2 (TAIL).
-  if (m_per_frame || !kn.dplin_ereg) { if (m_per_frame) MW_GO(1, 0, 0); else MW_GO(0, 0, 0); }
-  else if (lay.L <= 128) MW_GO(0, 128, 0);
-  else if (DMAX <= 25 && lay.L <= 192) MW_GO(0, 192, 0);
-  else if (DMAX <= 25 && lay.L <= 208) MW_GO(0, 208, 0);
-  else if (DMAX > 25 && kn.dplin_tail) MW_GO(0, 128, 1);
-  else MW_GO(0, 0, 0);
-#undef MW_GO
-}
-
 void launch_true_scores(hipStream_t st, const ScrfLayout& lay, ScrfBatchView bv, const uint32_t* frame_u, uint32_t u0,
                         uint64_t n_frames, const double* S, double* s_true) {
   if (n_frames == 0) return;
@@ -908,77 +877,44 @@ void launch_dp_lin(hipStream_t st, const ScrfKnobs& kn, const ScrfLayout& lay, S
                    const double* ES, const double* smax, const double* E, const double* ET, const double* mshift,
                    int m_per_frame, const ScrfDpLin& o, double* zx, int* status) {
   if (n_utts == 0) return;
-  if (lay.L > 64) {
-    if (lay.D <= 10) launch_dp_lin_mw_t<10>(st, kn, lay, bv, u0, n_utts, ES, smax, E, ET, mshift, m_per_frame, o, zx, status);
-    else if (lay.D <= 25) launch_dp_lin_mw_t<25>(st, kn, lay, bv, u0, n_utts, ES, smax, E, ET, mshift, m_per_frame, o, zx, status);
-    else launch_dp_lin_mw_t<40>(st, kn, lay, bv, u0, n_utts, ES, smax, E, ET, mshift, m_per_frame, o, zx, status);
-    return;
+  const ScrfDpLinPlan p = dp_lin_plan(kn, dp_shape(lay), n_utts, m_per_frame, dp_cu_count());
+#define DL_RUN(K)                                                                                                         \
+  hipFuncSetAttribute((const void*)K, hipFuncAttributeMaxDynamicSharedMemorySize, (int)p.lds);                           \
+  hipLaunchKernelGGL(K, dim3(p.blocks), dim3(p.threads), p.lds, st, lay, bv, u0, n_utts, ES, smax, E, ET, mshift, o.a, o.ga, \
+                     o.p, o.gp, o.b, o.gb, o.sd, o.gsd, zx, status);                                                     \
+  break
+#define DL_CASE(DM, MPF, LC) case ((DM) * 2 + (MPF)) * 64 + (LC): DL_RUN((k_dp_lin<DM, MPF, LC>))
+#define DL_CASES(DM) DL_CASE(DM, 0, 0); DL_CASE(DM, 1, 0)
+#define DV_CASE(DM, MPF) case (DM) * 2 + (MPF): DL_RUN((k_dp_lin_mv<DM, MPF>))
+#define DV_CASES(DM) DV_CASE(DM, 0); DV_CASE(DM, 1)
+#define MW_CASE(DM, MPF, LR, TAIL) case (((DM) * 2 + (MPF)) * 256 + (LR)) * 2 + (TAIL): DL_RUN((k_dp_lin_mw<DM, MPF, LR, TAIL>))
+  // every form of the matrix column: per-frame matrices, from L2, 128 rows in registers; all of it (DMAX 10 and 25) or a tail from L2
+#define MW_CASES(DM) MW_CASE(DM, 1, 0, 0); MW_CASE(DM, 0, 0, 0); MW_CASE(DM, 0, 128, 0)
+  switch (p.kernel) {
+    case SCRF_DK_LIN:
+      switch ((p.dmax * 2 + p.mpf) * 64 + p.lc) {
+        DL_CASES(1); DL_CASES(4); DL_CASES(10); DL_CASES(16); DL_CASES(25); DL_CASES(32); DL_CASES(40);
+        DL_CASE(25, 0, 48);
+      }
+      break;
+    case SCRF_DK_LIN_MV:
+      switch (p.dmax * 2 + p.mpf) { DV_CASES(10); DV_CASES(16); DV_CASES(25); DV_CASES(32); DV_CASES(40); }
+      break;
+    case SCRF_DK_LIN_MW:
+      switch (((p.dmax * 2 + p.mpf) * 256 + p.lr) * 2 + p.tail) {
+        MW_CASES(10); MW_CASE(10, 0, 192, 0); MW_CASE(10, 0, 208, 0);
+        MW_CASES(25); MW_CASE(25, 0, 192, 0); MW_CASE(25, 0, 208, 0);
+        MW_CASES(40); MW_CASE(40, 0, 128, 1);
+      }
+      break;
   }
-  // opt-in (SCRF_DPLIN_MV=1): parity-green, but measured no faster than one wavefront per sweep -- see the kernel's header
-  // k_dp_lin_mv (four wavefronts per sweep): SCRF_DPLIN_MV=1 always, =0 never; unset: with per-frame transition matrices
-  // when the launch has at most SCRF_DPLIN_MV_SWEEPS (default 3: the kernel's occupancy) sweeps per CU -- there the
-  // single-wavefront kernel's step is the latency of one wavefront fetching an L x L matrix, and four fetch it in
-  // parallel (config 3, 256 utterances: 1.86 -> 1.03 ms).  With time-invariant transitions it measured no faster at any
-  // batch size (64 .. 4096 utterances), so it stays opt-in there.
-  const bool use_mv = kn.dplin_mv == 1 || (kn.dplin_mv < 0 && m_per_frame && 2 * (uint64_t)n_utts <= (uint64_t)kn.dplin_mv_sweeps * dp_cu_count());
-  if (use_mv && lay.D >= 2) {
-    // several wavefronts per sweep (k_dp_lin_mv): one workgroup of 4 per (utterance, direction)
-    const size_t smv = sizeof(double) * ((((size_t)lay.D * lay.L + 1) & ~(size_t)1) + 4 * DPV_NW * 64);
-#define DV_LAUNCH2(DM, MPF)                                                                                            \
-  do {                                                                                                                 \
-    hipFuncSetAttribute((const void*)k_dp_lin_mv<DM, MPF>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smv);      \
-    hipLaunchKernelGGL((k_dp_lin_mv<DM, MPF>), dim3(2 * n_utts), dim3(64 * DPV_NW), smv, st, lay, bv, u0, n_utts, ES,  \
-                       smax, E, ET, mshift, o.a, o.ga, o.p, o.gp, o.b, o.gb, o.sd, o.gsd, zx, status);                 \
-  } while (0)
-#define DV_LAUNCH(DM) do { if (m_per_frame) DV_LAUNCH2(DM, 1); else DV_LAUNCH2(DM, 0); } while (0)
-    if (lay.D <= 10) DV_LAUNCH(10);
-    else if (lay.D <= 16) DV_LAUNCH(16);
-    else if (lay.D <= 25) DV_LAUNCH(25);
-    else if (lay.D <= 32) DV_LAUNCH(32);
-    else DV_LAUNCH(40);
-#undef DV_LAUNCH
-#undef DV_LAUNCH2
-    return;
-  }
-  uint32_t wpb = dp_waves_per_block(sizeof(double) * (m_per_frame ? 0 : (size_t)lay.L * lay.L), sizeof(double) * ((size_t)lay.D * lay.L + 128));
-  if (wpb > 8) {
-    // Tail-aware workgroup size: one workgroup per CU, so the launch runs in ceil(workgroups / CUs) rounds of T steps,
-    // and a step costs a fixed latency plus a share per resident wavefront (measured on MI355X at config 2:
-    // 3.4 us + 0.31 us per wavefront).  8192 sweeps on 256 CUs: 12 wavefronts per workgroup are
-    // 2.67 -> 3 rounds of 7.1 us steps, 11 are 2.91 -> 3 rounds of 6.8 us steps.
-    const int n_cu = dp_cu_count();
-    uint32_t best = wpb;
-    double best_cost = 1e300;
-    for (uint32_t w = wpb; w >= 8; w--) {
-      const uint64_t blocks = 2 * (((uint64_t)n_utts + w - 1) / w);
-      const double cost = (double)((blocks + n_cu - 1) / n_cu) * (3.4 + 0.31 * w);
-      if (cost < best_cost - 1e-9) { best_cost = cost; best = w; }
-    }
-    wpb = best;
-  }
-  const uint32_t nblk = 2 * ((n_utts + wpb - 1) / wpb);
-  const size_t sm = sizeof(double) * ((m_per_frame ? 0 : (size_t)lay.L * lay.L) + (size_t)wpb * (lay.D * lay.L + 128));
-#define DL_LAUNCH2(DM, MPF, LC)                                                                                    \
-  do {                                                                                                             \
-    hipFuncSetAttribute((const void*)k_dp_lin<DM, MPF, LC>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sm);  \
-    hipLaunchKernelGGL((k_dp_lin<DM, MPF, LC>), dim3(nblk), dim3(wpb * 64), sm, st, lay, bv, u0, n_utts, ES, smax, \
-                       E, ET, mshift, o.a, o.ga, o.p, o.gp, o.b, o.gb, o.sd, o.gsd, zx, status);                   \
-  } while (0)
-#define DL_LAUNCH(DM)                                        \
-  do {                                                       \
-    if (m_per_frame) DL_LAUNCH2(DM, 1, 0);                   \
-    else if (DM == 25 && lay.L == 48) DL_LAUNCH2(DM, 0, 48); \
-    else DL_LAUNCH2(DM, 0, 0);                               \
-  } while (0)
-  if (lay.D <= 1) DL_LAUNCH(1);
-  else if (lay.D <= 4) DL_LAUNCH(4);
-  else if (lay.D <= 10) DL_LAUNCH(10);
-  else if (lay.D <= 16) DL_LAUNCH(16);
-  else if (lay.D <= 25) DL_LAUNCH(25);
-  else if (lay.D <= 32) DL_LAUNCH(32);
-  else DL_LAUNCH(40);
-#undef DL_LAUNCH
-#undef DL_LAUNCH2
+#undef MW_CASES
+#undef MW_CASE
+#undef DV_CASES
+#undef DV_CASE
+#undef DL_CASES
+#undef DL_CASE
+#undef DL_RUN
 }
 
 // ------------------------------------------------------------------------------------------

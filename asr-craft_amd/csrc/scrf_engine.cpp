@@ -1192,7 +1192,7 @@ static bool sparse(scrf_handle h) { return h->cfg.map_type >= SCRF_STDSPARSE; }
 
 static bool wave_path(scrf_handle h, bool post) {
   if (h->force_fb || segtrans(h)) return false;
-  return dp_wave_supported(h->lay) || (post && h->kn.lindp && (dplin_mw_supported(h->lay) || dplin_supported(h->lay)));
+  return dp_wave_supported(dp_shape(h->lay)) || (post && h->kn.lindp && (dplin_mw_supported(dp_shape(h->lay)) || dplin_supported(dp_shape(h->lay))));
 }
 
 // fused path: the five sampled blocks as per-frame projections (outputs (k, label), k < 5), and
@@ -1306,9 +1306,9 @@ static void chunk_layout(scrf_handle h, scrf_batch b, uint32_t u0, uint32_t u1, 
     if (nd.ponly) {
       cb->mass_s = a.take<double>(nfr);
       // [groups][nfr], read as one array; sized one padded row per group, as the planner has always counted it
-      if (post_occ_groups(l) > 1) {
+      if (post_occ_groups(dp_shape(l)) > 1) {
         cb->mass_part = a.take<double>(nfr);
-        for (uint32_t g = 1; g < post_occ_groups(l); g++) a.take<double>(nfr);
+        for (uint32_t g = 1; g < post_occ_groups(dp_shape(l)); g++) a.take<double>(nfr);
       }
     }
     if (nd.post) {
@@ -1697,7 +1697,7 @@ static int queue_status(scrf_handle h, scrf_batch b, hipStream_t st);
 // STDSEG_NO_DUR: one transition matrix per window, its own workgroup recursion
 static int dp_segtrans(scrf_handle h, scrf_batch b, uint32_t u0, uint32_t u1, ChunkBufs& cb, bool post, uint32_t* nl) {
   const ScrfLayout& l = h->lay;
-  if (fb_segtrans_smem_bytes(l, fb_block_threads(l)) > SCRF_LDS_BYTES)
+  if (fb_segtrans_smem_bytes(dp_shape(l), fb_block_threads(dp_shape(l))) > SCRF_LDS_BYTES)
     return fail(h, SCRF_ERR_INVALID, "labels x maximum duration = %u x %u is too large for the stdseg_no_dur recursion "
                 "(its three [D][L] rings must fit 160 KB of LDS)", l.L, l.D);
   KT_RUN("k_fb_segtrans", cb.st, launch_fb_segtrans(cb.st, h->kn, l, b->view(), u0, u1 - u0, b->d_prev_lab, cb.S, cb.M, cb.AD, cb.alpha, cb.beta,
@@ -1710,7 +1710,7 @@ static int dp_segtrans(scrf_handle h, scrf_batch b, uint32_t u0, uint32_t u1, Ch
 static int dp_group(scrf_handle h, scrf_batch b, uint32_t u0, uint32_t u1, ChunkBufs& cb, bool post, uint32_t* nl) {
   const ScrfLayout& l = h->lay;
   const uint32_t nutt = u1 - u0;
-  if (fb_smem_bytes(l, fb_block_threads(l)) > SCRF_LDS_BYTES)
+  if (fb_smem_bytes(dp_shape(l), fb_block_threads(dp_shape(l))) > SCRF_LDS_BYTES)
     return fail(h, SCRF_ERR_INVALID, "labels x maximum duration = %u x %u is too large for the workgroup-per-utterance recursion "
                 "(its two [D][L] rings must fit 160 KB of LDS; the wavefront kernels cover L <= 256 with D <= 40)", l.L, l.D);
   if (post && cb.xi_acc) HIPCHK(h, hipMemsetAsync(cb.xi_acc, 0, sizeof(double) * nutt * l.L * l.L, cb.st));
@@ -1962,7 +1962,7 @@ static const SmallPipe<StdsegBufs> stdseg_pipe = {stdseg_layout, 0, 0};   // no 
 // ---- STDSEG, bias-only transitions, FAST precisions, training path: scrf_stdseg_lin.hip (not during a log-domain redo,
 // force_fb: that one runs k_stdseg_fb, the reference's order)
 static bool stdseg_lin(scrf_handle h) {
-  return h->kn.stdseg_lin && !h->force_fb && h->cfg.train_precision != SCRF_PREC_EXACT && h->lay.use_sf && stdseg_lin_supported(h->lay, stdseg_La(h));
+  return h->kn.stdseg_lin && !h->force_fb && h->cfg.train_precision != SCRF_PREC_EXACT && h->lay.use_sf && stdseg_lin_supported(dp_shape(h->lay), stdseg_La(h));
 }
 static uint64_t sl_rows_per_chunk(uint64_t nfr) {   // K-chunks of the count contractions: <= 256 of them, multiples of 32 frames
   uint64_t rpc = ((nfr + 255) / 256 + 31) & ~31ull;
@@ -2591,7 +2591,7 @@ static int post_chunk(scrf_handle h, scrf_batch b, const PostOut& po, ChunkBufs&
     KT_RUN("k_post_occ", cb.st, nz = launch_post_occ(cb.st, l, bv, u0, nutt, t_max, nfr, cb.S, cb.smax, cb.dl, b->d_zx, b->d_status, occ,
                     cb.mass_part, cb.mass_s, h->kn.postocc_split ? 1 : 0));
     if (nz > 1) h->n_post_split++; else h->n_post_whole++;
-    if (post_occ_groups(l) > 1) *nl += 1;   // k_sum_groups
+    if (post_occ_groups(dp_shape(l)) > 1) *nl += 1;   // k_sum_groups
     KT_RUN("k_mass_check", cb.st, launch_mass_check(cb.st, bv, b->d_frame_u, u0, nfr, l.L, frame_mass_model(h), 1, cb.dl.a, cb.dl.ga, cb.dl.b, cb.dl.gb,
                       b->d_zx, cb.mass_s, b->d_status));
   } else {   // SCRF_PREC_EXACT, or the redo of a pass that raised NUMERIC
@@ -2965,7 +2965,7 @@ extern "C" int scrf_lattice_prune_batch(scrf_handle h, scrf_batch b, double beam
   if (!(beam > 0.0) || !std::isfinite(beam))
     return fail(h, SCRF_ERR_INVALID, "scrf_lattice_prune_batch: the beam must be finite and > 0 (got %g)", beam);
   const ScrfLayout& l = h->lay;
-  if (lat_sweep_smem_bytes(l) > SCRF_LDS_BYTES)
+  if (lat_sweep_smem_bytes(dp_shape(l)) > SCRF_LDS_BYTES)
     return fail(h, SCRF_ERR_INVALID, "scrf_lattice_prune_batch: %u labels x maximum duration %u do not fit the sweep kernel's LDS window", l.L, l.D);
   HIPCHK(h, hipSetDevice(h->device));
   const uint32_t U = b->U;
@@ -3146,7 +3146,7 @@ extern "C" int scrf_viterbi_batch(scrf_handle h, scrf_batch b, uint32_t* seg_lab
   }
   else
     rc = decode_chunks(h, b, Need::viterbi(), [&](const ChunkBufs& cb, uint32_t u0, uint32_t u1, bool fast) {
-      if (fast && viterbi_fast_supported(l))
+      if (fast && viterbi_fast_supported(dp_shape(l)))
         launch_viterbi_fast(h->stream, h->kn, l, b->view(), u0, u1 - u0, arc_src(h, cb, fast), cb.bp_b, cb.bp_e, d_lab, d_n, d_cost);
       else if (segtrans(h)) launch_viterbi_segtrans(h->stream, l, b->view(), u0, u1 - u0, cb.S, cb.M, cb.bp_b, cb.bp_e, d_lab, d_n, d_cost);
       else launch_viterbi(h->stream, l, b->view(), u0, u1 - u0, arc_src(h, cb, fast), cb.bp_b, cb.bp_e, d_lab, d_n, d_cost);
@@ -3219,9 +3219,9 @@ extern "C" int scrf_align_batch(scrf_handle h, scrf_batch b, const uint32_t* pho
     return fail(h, SCRF_ERR_INVALID, "scrf_align_batch: maximum duration %u does not fit the 15 duration bits of a back pointer (at most %u)", l.D, 0x7fffu);
   const uint32_t U = b->U;
   // back-pointer cells before each utterance; the workgroup kernel takes the transcripts the wavefront kernel does not
-  const bool wave_on = h->kn.align_wave && align_wave_supported(l);
+  const bool wave_on = h->kn.align_wave && align_wave_supported(dp_shape(l));
   RCCHK(check_transcripts(h, b, "scrf_align_batch", phones, phone_off, mode, false, 4, 0,
-                          [&](uint64_t K) { return (K > 64 || !wave_on) ? align_group_smem_bytes(l, K) : 0; }, &h->tx.bp_off));
+                          [&](uint64_t K) { return (K > 64 || !wave_on) ? align_group_smem_bytes(dp_shape(l), K) : 0; }, &h->tx.bp_off));
   HIPCHK(h, hipSetDevice(h->device));
   CallTimer call(h);
   HIPCHK(h, h->dec.reserve(b->frame_off[b->U], b->U));
@@ -3259,10 +3259,10 @@ extern "C" int scrf_nbest_batch(scrf_handle h, scrf_batch b, uint32_t n_best, ui
   if (l.D > 0x7fff) return fail(h, SCRF_ERR_INVALID, "%s: maximum duration %u does not fit the 15 duration bits of a back pointer (at most %u)", fn, l.D, 0x7fffu);
   if (l.L > 0xffff) return fail(h, SCRF_ERR_INVALID, "%s: %u labels do not fit the 16 label bits of a back pointer (at most %u)", fn, l.L, 0xffffu);
   if (n_best == 0 || n_best > 0xffff) return fail(h, SCRF_ERR_INVALID, "%s: n_best must be 1 .. 65535 (got %u)", fn, n_best);
-  if (nbest_smem_bytes(l, n_best) > SCRF_LDS_BYTES)
+  if (nbest_smem_bytes(dp_shape(l), n_best) > SCRF_LDS_BYTES)
     return fail(h, SCRF_ERR_INVALID, "%s: n_best %u with %u labels and maximum duration %u needs (%u + 2) x %u x %u x 4 + %zu = %zu bytes of LDS, "
-                "a workgroup has %d", fn, n_best, l.L, l.D, l.D, l.L, n_best, nbest_smem_bytes(l, n_best) - sizeof(float) * ((size_t)l.D + 2) * l.L * n_best,
-                nbest_smem_bytes(l, n_best), SCRF_LDS_BYTES);
+                "a workgroup has %d", fn, n_best, l.L, l.D, l.D, l.L, n_best, nbest_smem_bytes(dp_shape(l), n_best) - sizeof(float) * ((size_t)l.D + 2) * l.L * n_best,
+                nbest_smem_bytes(dp_shape(l), n_best), SCRF_LDS_BYTES);
   HIPCHK(h, hipSetDevice(h->device));
   const bool frame_model = h->cfg.model_type == SCRF_STDFRAME;
   const uint32_t U = b->U;
@@ -3417,7 +3417,7 @@ extern "C" int scrf_transcript_batch(scrf_handle h, scrf_batch b, const uint32_t
   const uint64_t nF = b->frame_off[U];
   // the checks of every transcript and the cells before each utterance; 128 bytes of LDS go to the 16 per-wavefront parts of
   // end[t].  Then the inverted lists (inverted_lists)
-  RCCHK(check_transcripts(h, b, fn, phones, phone_off, mode, true, 8, 128, [&](uint64_t K) { return transcript_smem_bytes(l, K); },
+  RCCHK(check_transcripts(h, b, fn, phones, phone_off, mode, true, 8, 128, [&](uint64_t K) { return transcript_smem_bytes(dp_shape(l), K); },
                           &h->tx.cell_off));
   std::vector<uint32_t> q;   // [3][nq]: utterance, end frame, label value
   uint64_t nq = 0;
@@ -3560,7 +3560,7 @@ extern "C" int scrf_fb_transcript_batch(scrf_handle h, scrf_batch b, const uint3
     return fail(h, SCRF_ERR_INVALID, "%s: unknown mode %d (SCRF_ALIGN_ONE = 0, SCRF_ALIGN_RUNS = 1)", fn, mode);
   const uint32_t U = b->U;
   const uint64_t nF = b->frame_off[U];
-  RCCHK(check_transcripts(h, b, fn, phones, phone_off, mode, true, 8, 128, [&](uint64_t K) { return transcript_smem_bytes(l, K); },
+  RCCHK(check_transcripts(h, b, fn, phones, phone_off, mode, true, 8, 128, [&](uint64_t K) { return transcript_smem_bytes(dp_shape(l), K); },
                           &h->tx.cell_off));
   // a transcript no path realises has no numerator: in training that is an error, not an empty sum
   for (uint32_t u = 0; u < U; u++)

@@ -2500,13 +2500,14 @@ __global__ __launch_bounds__(FW_NT) __attribute__((amdgpu_num_vgpr(208))) void k
 template <int NT, int DMAX, int NKS, int G0, int ROWS, int DMA>
 static void launch_expf_ws_d(FE_LAUNCH_ARGS) {
   dim3 grid(fused_expf_blocks(p, n_tiles), p.gy, p.nz);
-  if (fused_expf_ws_capped(NT)) {   // (= p.kernel == SCRF_FK_WS_N; on the template argument, so that the host keeps one entry point per form)
+  // (= p.kernel == SCRF_FK_WS_N; `if constexpr` on the template argument: each form names, and so builds, one of the two kernels)
+  if constexpr (fused_expf_ws_capped(NT)) {
     hipFuncSetAttribute((const void*)k_expf_fused_ws_n<NT, DMAX, NKS, G0, ROWS, DMA>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)p.lds);
     hipLaunchKernelGGL((k_expf_fused_ws_n<NT, DMAX, NKS, G0, ROWS, DMA>), grid, dim3(p.threads), p.lds, st, fa, lay, R, lay.L, n_tiles, p.n_ct, slab, dslab);
-    return;
+  } else {
+    hipFuncSetAttribute((const void*)k_expf_fused_ws<NT, DMAX, NKS, G0, ROWS, DMA>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)p.lds);
+    hipLaunchKernelGGL((k_expf_fused_ws<NT, DMAX, NKS, G0, ROWS, DMA>), grid, dim3(p.threads), p.lds, st, fa, lay, R, lay.L, n_tiles, p.n_ct, slab, dslab);
   }
-  hipFuncSetAttribute((const void*)k_expf_fused_ws<NT, DMAX, NKS, G0, ROWS, DMA>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)p.lds);
-  hipLaunchKernelGGL((k_expf_fused_ws<NT, DMAX, NKS, G0, ROWS, DMA>), grid, dim3(p.threads), p.lds, st, fa, lay, R, lay.L, n_tiles, p.n_ct, slab, dslab);
 }
 template <int NT, int DMAX, int NKS>
 static void launch_expf_ws_t(FE_LAUNCH_ARGS) {
@@ -2547,12 +2548,12 @@ void launch_expf_fused(FE_LAUNCH_ARGS) {
   if (!p.ws) {
     switch (key) { FE_DEPTHS(launch_expf_fused_t, 4); FE_DEPTHS(launch_expf_fused_t, 7); FE_DEPTHS(launch_expf_fused_t, 10); }
   } else if (p.tile_list == 2) {
-    switch (key) {
-      FE_CASE(launch_expf_big_t, 4, 12, 21); FE_CASE(launch_expf_big_t, 4, 12, 25); FE_CASE(launch_expf_big_t, 4, 25, 21);
-      FE_CASE(launch_expf_big_t, 4, 25, 25); FE_CASE(launch_expf_big_t, 4, 40, 21); FE_CASE(launch_expf_big_t, 4, 40, 25);
+    switch (key) {   // (the shortest duration class always fills more than 84 rows with whole frames: no 21-step form there)
+      FE_CASE(launch_expf_big_t, 4, 12, 25); FE_CASE(launch_expf_big_t, 4, 25, 21); FE_CASE(launch_expf_big_t, 4, 25, 25);
+      FE_CASE(launch_expf_big_t, 4, 40, 21); FE_CASE(launch_expf_big_t, 4, 40, 25);
     }
   } else {
-    switch (key) { FE_DEPTHS(launch_expf_ws_t, 4); FE_DEPTHS(launch_expf_ws_t, 6); FE_DEPTHS(launch_expf_ws_t, 7); FE_DEPTHS(launch_expf_ws_t, 10); }
+    switch (key) { FE_DEPTHS(launch_expf_ws_t, 4); FE_DEPTHS(launch_expf_ws_t, 6); FE_DEPTHS(launch_expf_ws_t, 7); }   // (two images of 13 column tiles pass the LDS: no 10-slot form)
   }
 #undef FE_DEPTHS
 #undef FE_CASE

@@ -11,13 +11,8 @@
 #include <stddef.h>
 #include <stdint.h>
 
+#include "scrf_dp_plan.h"   // SCRF_HD, walk_segments
 #include "scrf_knobs.h"
-
-#ifdef __HIPCC__
-#define SCRF_HD __host__ __device__
-#else
-#define SCRF_HD
-#endif
 
 // the layout fields the choice reads (ScrfLayout's, scrf_common.h; fused_shape() in scrf_kernels.h copies them)
 struct ScrfFusedShape { uint32_t L, D; int32_t use_sb; };
@@ -156,18 +151,9 @@ inline ScrfFusedWalkPlan fused_post_z_plan(const ScrfKnobs& kn, const ScrfFusedS
   ScrfFusedWalkPlan p = fused_lin_z_plan(lay, n_utts);
   p.la = la ? 1 : 0;
   p.rw = (la && lay.L <= 48) ? 48 : 64;
-  // few wavefronts (a small minibatch): several segments per utterance, about four wavefronts per CU in all (half the
-  // kernel's occupancy), no segment shorter than 2 D frames (SCRF_POSTZ_SPLIT=0: never).  Config 3, 256 utterances:
-  // 1.21 -> 0.50 ms; config 2's shape at 64 utterances: 1.90 -> 0.38 ms
+  // few wavefronts (a small minibatch): several segments per utterance (walk_segments; SCRF_POSTZ_SPLIT=0: never)
   int seg_len = 0;
-  uint32_t nz = 1;
-  const uint64_t waves = (uint64_t)p.gx * p.gy;
-  if (kn.postz_split && waves && waves <= 2 * 256 && t_max >= 4 * lay.D) {
-    const uint32_t want = (uint32_t)((4 * 256 + waves - 1) / waves);
-    seg_len = (int)((t_max + want - 1) / want);
-    if (seg_len < (int)(2 * lay.D)) seg_len = (int)(2 * lay.D);
-    nz = (uint32_t)((t_max + seg_len - 1) / seg_len);
-  }
+  const uint32_t nz = kn.postz_split ? walk_segments((uint64_t)p.gx * p.gy, lay.D, t_max, &seg_len) : 1;
   if (nz > 1) { p.nz = nz; p.split = 1; p.seg_len = seg_len; p.clear_z = 1; }
   return p;
 }

@@ -5,10 +5,15 @@
 #include "scrf_arcw.h"
 #include "scrf_common.h"
 #include "scrf_knobs.h"
+#include "scrf_dp_plan.h"
 #include "scrf_fused_plan.h"
 #include "scrf_mfma_plan.h"
 
 #include <vector>
+
+// the recursions, the walks and the searches: which instantiation their launchers start, the predicates that route a chunk
+// to them (dp_wave_supported, dplin_supported, ...) and the LDS sizes the engine checks are in scrf_dp_plan.h
+inline ScrfDpShape dp_shape(const ScrfLayout& l) { return ScrfDpShape{l.L, l.D, l.use_tf, l.use_tb}; }
 
 void launch_windows(hipStream_t st, const float* frames, const uint64_t* sframe_off, ScrfBatchView bv,
                     uint32_t u0, uint32_t u1, uint64_t n_frames, uint32_t W, uint32_t D, uint32_t lctx,
@@ -17,8 +22,6 @@ void launch_frame_rows(hipStream_t st, ScrfBatchView bv, uint32_t u0, uint32_t u
                        uint64_t n_frames, uint64_t* xrow, int next);
 void launch_scores_exact(hipStream_t st, const float* X, uint32_t F, const uint64_t* xrow, uint64_t n_rows,
                          const double* lambda, const ScrfLayout& lay, int is_trans, uint32_t n_out, double* out);
-size_t fb_smem_bytes(const ScrfLayout& lay, int NT);
-int fb_block_threads(const ScrfLayout& lay);
 void launch_fb(hipStream_t st, const ScrfLayout& lay, ScrfBatchView bv, uint32_t u0, uint32_t n_utts,
                const double* S, const double* M, int m_per_frame, double* AD, double* alpha_g, double* beta_g,
                double* XI, double* xi_acc, double* numer, double* zx, int* status, int write_post, int frame_model = 0);
@@ -40,7 +43,6 @@ void launch_scale(hipStream_t st, double* v, uint32_t n, double s, int divide);
 void launch_add(hipStream_t st, double* y, const double* x, uint32_t n);
 
 // scrf_segtrans.hip: STDSEG_NO_DUR (one transition matrix per window): workgroup-per-utterance log-domain recursion
-size_t fb_segtrans_smem_bytes(const ScrfLayout& lay, int NT);
 void launch_zero_initial_rows(hipStream_t st, ScrfBatchView bv, const uint32_t* frame_u, uint32_t u0, uint64_t n_frames,
                               uint32_t D, uint32_t L, double* M2);
 void launch_fb_segtrans(hipStream_t st, const ScrfKnobs& kn, const ScrfLayout& lay, ScrfBatchView bv, uint32_t u0, uint32_t n_utts,
@@ -64,8 +66,6 @@ void launch_expf_mfma(hipStream_t st, const ScrfKnobs& kn, const double* A, uint
 // (which instantiations the two launch, and expf_mfma_wide_tiles for the engine's row chunks: scrf_mfma_plan.h)
 
 // scrf_dp.hip: wavefront-per-utterance DP and the parallel posterior kernels
-int dp_wave_supported(const ScrfLayout& lay);
-int atb_supported(const ScrfLayout& lay);
 void launch_exp_m(hipStream_t st, const ScrfKnobs& kn, const double* M, uint32_t L, uint64_t n_mat, double* E, double* ET,
                   double* mshift);
 void launch_dp_wave(hipStream_t st, const ScrfLayout& lay, ScrfBatchView bv, uint32_t u0, uint32_t n_utts,
@@ -89,8 +89,6 @@ void launch_xi_full(hipStream_t st, const ScrfLayout& lay, ScrfBatchView bv, uin
                     const double* mshift, double* XI);
 
 // scrf_dplin.hip: scaled linear-domain forward/backward + posteriors (training path, L <= 64)
-int dplin_mw_supported(const ScrfLayout& lay);
-int dplin_supported(const ScrfLayout& lay);
 void launch_true_scores(hipStream_t st, const ScrfLayout& lay, ScrfBatchView bv, const uint32_t* frame_u, uint32_t u0,
                         uint64_t n_frames, const double* S, double* s_true);
 void launch_exp_rows(hipStream_t st, double* S, uint64_t n_rows, uint32_t L, double* smax);
@@ -117,7 +115,6 @@ void launch_lin_to_log(hipStream_t st, uint64_t n_frames, uint32_t L, const doub
 // mass_part [post_occ_groups][frames] holds the per-group partial masses when L > 64 (not used with one group).
 // launch_post_occ returns the number of frame segments every utterance's walk was split into (1: one piece); split_ok = 0
 // keeps every walk in one piece
-uint32_t post_occ_groups(const ScrfLayout& lay);
 uint32_t launch_post_occ(hipStream_t st, const ScrfLayout& lay, ScrfBatchView bv, uint32_t u0, uint32_t n_utts, uint32_t t_max,
                          uint64_t n_frames, const double* ES, const double* smax, const ScrfDpLin& o, const double* zx,
                          int* status, double* occ, double* mass_part, double* mass_s, int split_ok);
@@ -143,7 +140,6 @@ void launch_tile_tables(hipStream_t st, uint32_t D, uint32_t TB, int la, void* r
 void launch_dur_table(hipStream_t st, const ScrfLayout& lay, uint32_t W, const double* lambda, double* dtab);
 void launch_avg_prefix(hipStream_t st, ScrfBatchView bv, uint32_t u0, uint32_t n_utts, uint32_t L, double* P);
 // k_viterbi on float arc weights with one wavefront per utterance (fast decode; L <= 64, constant M)
-int viterbi_fast_supported(const ScrfLayout& lay);
 void launch_viterbi_fast(hipStream_t st, const ScrfKnobs& kn, const ScrfLayout& lay, ScrfBatchView bv, uint32_t u0, uint32_t n_utts,
                          const ScrfArcSrc& src, uint16_t* bp_b, uint16_t* bp_e, uint32_t* out_labels, uint32_t* out_n, float* out_cost);
 // decode mode: float arc weights + the list of entries to recompute (ScrfDecodeOut)
@@ -188,7 +184,6 @@ void launch_stdseg_expf(hipStream_t st, const ScrfLayout& lay, uint32_t La, Scrf
                         const float* X, const double* G, const double* XI, double* grad);
 // scrf_stdseg_lin.hip: STDSEG with bias-only transitions on the training path: linear-domain recursion against one
 // exp(M) table, node arrays duration-major [D][frames][La], transition counts as E o (A^T B) on the MFMA
-int stdseg_lin_supported(const ScrfLayout& lay, uint32_t La);
 void launch_sl_tables(hipStream_t st, const ScrfLayout& lay, const double* lambda, double* E, double* ET, double* mmax);
 void launch_sl_rows(hipStream_t st, ScrfBatchView bv, const uint32_t* frame_u, uint32_t u0, uint64_t n_frames, uint32_t D, uint64_t* xrow);
 void launch_sl_fb(hipStream_t st, const ScrfLayout& lay, uint32_t La, ScrfBatchView bv, uint32_t u0, uint32_t n_utts, uint64_t n_frames,
@@ -261,7 +256,6 @@ struct ScrfLatBufs {
   double *fB, *fE, *bB, *bE;
   double* best;   // [U], batch-absolute
 };
-size_t lat_sweep_smem_bytes(const ScrfLayout& lay);
 void launch_lat_sweep(hipStream_t st, const ScrfLayout& lay, ScrfBatchView bv, uint32_t u0, uint32_t n_utts, const ScrfArcSrc& src,
                       const ScrfLatBufs& lb);
 void launch_lat_count(hipStream_t st, const ScrfLayout& lay, ScrfBatchView bv, uint32_t u0, uint32_t n_utts, uint32_t t_max,
@@ -299,10 +293,8 @@ __device__ inline bool align_live_b(int t, int k, int T, int K, int D, int mode)
   return true;
 }
 
-int align_wave_supported(const ScrfLayout& lay);
 void launch_align_wave(hipStream_t st, const ScrfLayout& lay, ScrfBatchView bv, uint32_t u0, uint32_t n_utts, const ScrfArcSrc& src,
                        const ScrfAlignArgs& aa, uint32_t* out_labels, uint32_t* out_n, float* out_cost);
-size_t align_group_smem_bytes(const ScrfLayout& lay, uint64_t K);
 void launch_align_group(hipStream_t st, const ScrfLayout& lay, ScrfBatchView bv, uint32_t u0, uint32_t n_utts, uint32_t k_max,
                         const ScrfArcSrc& src, const ScrfAlignArgs& aa, uint32_t* out_labels, uint32_t* out_n, float* out_cost);
 
@@ -319,8 +311,6 @@ struct ScrfTransArgs {
   int lin;                     // the scores are exp(S - smax) with smax per row (the linear-domain path), not S
   int want_seg;                // segment queries follow: run the backward sweep even without frame / end output
 };
-// dynamic LDS of a workgroup whose longest transcript has K phones: (D + 2) K doubles
-size_t transcript_smem_bytes(const ScrfLayout& lay, uint64_t K);
 // log_num [U], occ [sum T][L] (or NULL), endp [sum T] (or NULL): arrays of the whole batch.  k_max: the longest transcript
 // of the chunk that fits
 void launch_transcript(hipStream_t st, const ScrfLayout& lay, ScrfBatchView bv, uint32_t u0, uint32_t n_utts, uint64_t k_max,
@@ -343,10 +333,6 @@ struct ScrfNbestBufs {
   uint64_t* hyp_pos;    // [utterances * N] index of each hypothesis in the result
   uint64_t* tot;        // {labels, hypotheses} of the chunk
 };
-// head ranks of one wavefront's merge: one 16-bit entry per list, L (boundary, final) or D + 1 (end) of them
-__host__ __device__ inline uint32_t nbest_heads(uint32_t L, uint32_t D) { return ((L > D + 1 ? L : D + 1) + 1) & ~1u; }
-// dynamic LDS of a workgroup: end double-buffered and the boundary ring, (D + 2) L N floats, + the head ranks
-size_t nbest_smem_bytes(const ScrfLayout& lay, uint32_t n_best);
 void launch_nbest(hipStream_t st, const ScrfLayout& lay, ScrfBatchView bv, uint32_t u0, uint32_t n_utts, const ScrfArcSrc& src,
                   const ScrfNbestBufs& nb);
 void launch_nbest_count(hipStream_t st, const ScrfLayout& lay, ScrfBatchView bv, uint32_t u0, uint32_t n_utts, int frame_model,

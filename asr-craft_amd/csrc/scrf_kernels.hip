@@ -396,22 +396,13 @@ __global__ void k_fb(ScrfLayout lay, ScrfBatchView bv, uint32_t u0, const double
   if (err) atomicMax(&status[u], err);
 }
 
-size_t fb_smem_bytes(const ScrfLayout& lay, int NT) {
-  int G = NT / (int)lay.L;
-  if (G < 1) G = 1;
-  return sizeof(double) * ((size_t)2 * lay.D * lay.L + 2 * lay.L + (size_t)2 * G * lay.L);
-}
-
-int fb_block_threads(const ScrfLayout& lay) { return lay.L <= 256 ? 256 : 1024; }
-
 void launch_fb(hipStream_t st, const ScrfLayout& lay, ScrfBatchView bv, uint32_t u0, uint32_t n_utts,
                const double* S, const double* M, int m_per_frame, double* AD, double* alpha_g, double* beta_g,
                double* XI, double* xi_acc, double* numer, double* zx, int* status, int write_post, int frame_model) {
   if (n_utts == 0) return;
-  int NT = fb_block_threads(lay);
-  size_t sm = fb_smem_bytes(lay, NT);
-  hipFuncSetAttribute((const void*)k_fb, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sm);
-  hipLaunchKernelGGL(k_fb, dim3(n_utts), dim3(NT), sm, st, lay, bv, u0, S, M, m_per_frame, AD, alpha_g, beta_g,
+  const ScrfGroupPlan p = fb_plan(dp_shape(lay));
+  hipFuncSetAttribute((const void*)k_fb, hipFuncAttributeMaxDynamicSharedMemorySize, (int)p.lds);
+  hipLaunchKernelGGL(k_fb, dim3(n_utts), dim3(p.threads), p.lds, st, lay, bv, u0, S, M, m_per_frame, AD, alpha_g, beta_g,
                      XI, xi_acc, numer, zx, status, write_post, frame_model);
 }
 
@@ -696,11 +687,9 @@ __global__ void k_viterbi(ScrfLayout lay, ScrfBatchView bv, uint32_t u0, const d
 void launch_viterbi(hipStream_t st, const ScrfLayout& lay, ScrfBatchView bv, uint32_t u0, uint32_t n_utts, const ScrfArcSrc& src,
                     uint16_t* bp_b, uint16_t* bp_e, uint32_t* out_labels, uint32_t* out_n, float* out_cost) {
   if (n_utts == 0) return;
-  int NT = ((int)lay.L + 63) / 64 * 64;
-  if (NT > 1024) NT = 1024;
-  size_t sm = sizeof(float) * ((size_t)2 * lay.L + (size_t)lay.D * lay.L);
-  hipFuncSetAttribute((const void*)k_viterbi, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sm);
-  hipLaunchKernelGGL(k_viterbi, dim3(n_utts), dim3(NT), sm, st, lay, bv, u0, src.S, src.M, src.m_per_frame, src.frame_model,
+  const ScrfGroupPlan p = viterbi_plan(dp_shape(lay));
+  hipFuncSetAttribute((const void*)k_viterbi, hipFuncAttributeMaxDynamicSharedMemorySize, (int)p.lds);
+  hipLaunchKernelGGL(k_viterbi, dim3(n_utts), dim3(p.threads), p.lds, st, lay, bv, u0, src.S, src.M, src.m_per_frame, src.frame_model,
                      src.Wn, bp_b, bp_e, out_labels, out_n, out_cost);
 }
 
@@ -715,7 +704,6 @@ void launch_viterbi(hipStream_t st, const ScrfLayout& lay, ScrfBatchView bv, uin
 // costs are read four at a time (one 16-byte broadcast read instead of eight 4-byte ones per four predecessors); two
 // comparison chains (even / odd predecessors) merged at the end -- the minimum, and among equal costs the smallest
 // predecessor, exactly what the one strict-improvement scan selects.
-#define VF_WAVES 4
 template <int DMAX, int LV>
 __global__ __launch_bounds__(64 * VF_WAVES) void k_viterbi_fast(ScrfLayout lay, ScrfBatchView bv, uint32_t u0, uint32_t n_utts,
                                                                 const float* __restrict__ Wn, const double* __restrict__ M,
@@ -845,34 +833,20 @@ __global__ __launch_bounds__(64 * VF_WAVES) void k_viterbi_fast(ScrfLayout lay, 
   }
 }
 
-int viterbi_fast_supported(const ScrfLayout& lay) {
-  return lay.L <= 64 && lay.D >= 2 && lay.D <= 40 && !lay.use_tf &&
-         sizeof(float) * ((size_t)lay.L * lay.L + VF_WAVES * ((size_t)lay.L + (size_t)lay.D * lay.L)) <= 64 * 1024;
-}
 void launch_viterbi_fast(hipStream_t st, const ScrfKnobs& kn, const ScrfLayout& lay, ScrfBatchView bv, uint32_t u0, uint32_t n_utts,
                          const ScrfArcSrc& src, uint16_t* bp_b, uint16_t* bp_e, uint32_t* out_labels, uint32_t* out_n, float* out_cost) {
   if (n_utts == 0) return;
-  const size_t sm = sizeof(float) * ((size_t)lay.L * lay.L + VF_WAVES * ((size_t)lay.L + (size_t)lay.D * lay.L));
-  const dim3 grid((n_utts + VF_WAVES - 1) / VF_WAVES), block(64 * VF_WAVES);
-#define VF_GO2(N, LV)                                                                                                          \
-  do {                                                                                                                         \
-    hipFuncSetAttribute((const void*)k_viterbi_fast<N, LV>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sm);              \
-    hipLaunchKernelGGL((k_viterbi_fast<N, LV>), grid, block, sm, st, lay, bv, u0, n_utts, src.Wn, src.M, bp_b, bp_e, out_labels, \
-                       out_n, out_cost);                                                                                       \
-  } while (0)
-  // register column + 16-byte reads of the previous node's costs: L a multiple of 4 (the LDS vectors stay 16-byte aligned)
-  const bool vec_ok = kn.viterbi_vec;
-#define VF_GO(N)                                                     \
-  do {                                                               \
-    if (vec_ok && lay.L % 4 == 0 && lay.L <= 48) VF_GO2(N, 48);      \
-    else if (vec_ok && lay.L % 4 == 0) VF_GO2(N, 64);                \
-    else VF_GO2(N, 0);                                               \
-  } while (0)
-  if (lay.D <= 12) VF_GO(12);
-  else if (lay.D <= 25) VF_GO(25);
-  else VF_GO(40);
-#undef VF_GO
-#undef VF_GO2
+  const ScrfViterbiFastPlan p = viterbi_fast_plan(kn, dp_shape(lay), n_utts);
+#define VF_CASE(N, LV)                                                                                                \
+  case (N) * 64 + (LV):                                                                                               \
+    hipFuncSetAttribute((const void*)k_viterbi_fast<N, LV>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)p.lds);  \
+    hipLaunchKernelGGL((k_viterbi_fast<N, LV>), dim3(p.gx), dim3(p.threads), p.lds, st, lay, bv, u0, n_utts, src.Wn, src.M, \
+                       bp_b, bp_e, out_labels, out_n, out_cost);                                                      \
+    break
+#define VF_CASES(N) VF_CASE(N, 0); VF_CASE(N, 48); VF_CASE(N, 64)
+  switch (p.dmax * 64 + p.lv) { VF_CASES(12); VF_CASES(25); VF_CASES(40); }
+#undef VF_CASES
+#undef VF_CASE
 }
 
 // ------------------------------------------------------------------------------------------

@@ -227,14 +227,13 @@ __global__ __launch_bounds__(LAT_NT) void k_lat_emit(ScrfLayout lay, ScrfBatchVi
   }
 }
 
-size_t lat_sweep_smem_bytes(const ScrfLayout& lay) { return sizeof(double) * ((size_t)lay.D + 2) * lay.L; }
 
 void launch_lat_sweep(hipStream_t st, const ScrfLayout& lay, ScrfBatchView bv, uint32_t u0, uint32_t n_utts, const ScrfArcSrc& src,
                       const ScrfLatBufs& lb) {
   if (n_utts == 0) return;
   int NT = ((int)lay.L + 63) / 64 * 64;
   if (NT > 256) NT = 256;
-  const size_t sm = lat_sweep_smem_bytes(lay);
+  const size_t sm = lat_sweep_smem_bytes(dp_shape(lay));
   hipFuncSetAttribute((const void*)k_lat_sweep, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sm);
   hipLaunchKernelGGL(k_lat_sweep, dim3(n_utts, 2), dim3(NT), sm, st, lay, bv, u0, src.S, src.M, src.m_per_frame, src.frame_model, lb);
 }

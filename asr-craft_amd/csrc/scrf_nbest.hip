@@ -21,7 +21,6 @@
 #include "scrf_arcw.h"
 #include "scrf_kernels.h"
 
-#define NB_WAVES 16
 #define NB_NOLIST 0x7fffffff
 
 // the lists a merge draws from, in the order of the tie rule: list(j) = the N sorted costs of predecessor j (nullptr: the
@@ -262,15 +261,11 @@ __global__ void k_nbest_trace(ScrfLayout lay, ScrfBatchView bv, uint32_t u0, uin
   nb_walk(nb, (int)bv.T[u], lay.L, frame_model, bv.frame_off[u] - bv.frame_off[u0], ui, r, res_lab + lp, n);
 }
 
-size_t nbest_smem_bytes(const ScrfLayout& lay, uint32_t n_best) {
-  return sizeof(float) * ((size_t)lay.D + 2) * lay.L * n_best + sizeof(uint16_t) * NB_WAVES * (size_t)nbest_heads(lay.L, lay.D);
-}
-
 void launch_nbest(hipStream_t st, const ScrfLayout& lay, ScrfBatchView bv, uint32_t u0, uint32_t n_utts, const ScrfArcSrc& src,
                   const ScrfNbestBufs& nb) {
   if (n_utts == 0) return;
   const int n_waves = lay.L < NB_WAVES ? (int)lay.L : NB_WAVES;
-  const size_t sm = nbest_smem_bytes(lay, nb.N);
+  const size_t sm = nbest_smem_bytes(dp_shape(lay), nb.N);
   hipFuncSetAttribute((const void*)k_nbest, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sm);
   hipLaunchKernelGGL(k_nbest, dim3(n_utts), dim3(64 * n_waves), sm, st, lay, bv, u0, src.S, src.Wn, src.M, src.m_per_frame,
                      src.frame_model, nb);

@@ -133,40 +133,22 @@ __global__ void k_sum_groups(const double* __restrict__ part, uint32_t n_groups,
   out[f] = s;
 }
 
-uint32_t post_occ_groups(const ScrfLayout& lay) { return (lay.L + 63) / 64; }
-
 uint32_t launch_post_occ(hipStream_t st, const ScrfLayout& lay, ScrfBatchView bv, uint32_t u0, uint32_t n_utts, uint32_t t_max,
                          uint64_t n_frames, const double* ES, const double* smax, const ScrfDpLin& o, const double* zx,
                          int* status, double* occ, double* mass_part, double* mass_s, int split_ok) {
   if (n_utts == 0) return 0;
-  dim3 grid(n_utts, post_occ_groups(lay));
-  // few wavefronts (a small minibatch): several frame segments per utterance, about four wavefronts per CU in all, no
-  // segment shorter than 2 D frames -- launch_post_z's rule.  split_ok = 0: never (the results do not change)
-  int seg_len = 0x7fffffff / 2;
-  const uint64_t waves = (uint64_t)grid.x * grid.y;
-  if (split_ok && waves <= 2 * 256 && t_max >= 4 * lay.D) {
-    const uint32_t want = (uint32_t)((4 * 256 + waves - 1) / waves);
-    seg_len = (int)((t_max + want - 1) / want);
-    if (seg_len < (int)(2 * lay.D)) seg_len = (int)(2 * lay.D);
-    grid.z = (uint32_t)((t_max + seg_len - 1) / seg_len);
-  }
-  double* mp = grid.y == 1 ? mass_s : mass_part;
-#define PO_GO2(N, R) hipLaunchKernelGGL((k_post_occ<N, R>), grid, dim3(64), 0, st, lay, bv, u0, ES, smax, o, zx, status, occ, mp, n_frames, seg_len)
-#define PO_GO(N)                      \
-  do {                                \
-    if (lay.L <= 48) PO_GO2(N, 48);   \
-    else PO_GO2(N, 64);               \
-  } while (0)
-  if (lay.D <= 8) PO_GO(8);
-  else if (lay.D <= 16) PO_GO(16);
-  else if (lay.D <= 25) PO_GO(25);
-  else if (lay.D <= 32) PO_GO(32);
-  else PO_GO(40);
-#undef PO_GO
-#undef PO_GO2
-  if (grid.y > 1)
-    hipLaunchKernelGGL(k_sum_groups, dim3((uint32_t)((n_frames + 255) / 256)), dim3(256), 0, st, mass_part, grid.y, n_frames, mass_s);
-  return grid.z;
+  // (the frame segments: walk_segments, launch_post_z's rule; split_ok = 0: never -- the results do not change)
+  const ScrfPostOccPlan p = post_occ_plan(dp_shape(lay), n_utts, t_max, split_ok);
+  double* mp = p.sum_groups ? mass_part : mass_s;
+#define PO_CASE(N, R) \
+  case (N) * 64 + (R): hipLaunchKernelGGL((k_post_occ<N, R>), dim3(p.gx, p.gy, p.nz), dim3(64), 0, st, lay, bv, u0, ES, smax, o, zx, status, occ, mp, n_frames, p.seg_len); break
+#define PO_CASES(N) PO_CASE(N, 48); PO_CASE(N, 64)
+  switch (p.dmax * 64 + p.rw) { PO_CASES(8); PO_CASES(16); PO_CASES(25); PO_CASES(32); PO_CASES(40); }
+#undef PO_CASES
+#undef PO_CASE
+  if (p.sum_groups)
+    hipLaunchKernelGGL(k_sum_groups, dim3((uint32_t)((n_frames + 255) / 256)), dim3(256), 0, st, mass_part, p.gy, n_frames, mass_s);
+  return p.nz;
 }
 
 // ------------------------------------------------------------------------------------------

@@ -239,7 +239,6 @@ __global__ void k_fb_segtrans(ScrfLayout lay, ScrfBatchView bv, uint32_t u0, con
 // / the reference's logAdd): same value up to the rounding of the shift.  Two workgroup barriers per node and
 // direction instead of two per window.  LDS: 2*D*L doubles.
 // ------------------------------------------------------------------------------------------
-#define FBW_WAVES 16
 __global__ __launch_bounds__(64 * FBW_WAVES) void k_fb_segtrans_w(ScrfLayout lay, ScrfBatchView bv, uint32_t u0, const uint32_t* __restrict__ prev_lab,
                               const double* __restrict__ S, const double* __restrict__ M2, double* __restrict__ AD,
                               double* __restrict__ alpha_g, double* __restrict__ beta_g, double* __restrict__ XI2,
@@ -454,30 +453,19 @@ __global__ __launch_bounds__(64 * FBW_WAVES) void k_fb_segtrans_w(ScrfLayout lay
   if (err) atomicMax(&status[u], err);
 }
 
-size_t fb_segtrans_smem_bytes(const ScrfLayout& lay, int NT) {
-  int G = NT / (int)lay.L;
-  if (G < 1) G = 1;
-  return sizeof(double) * ((size_t)3 * lay.D * lay.L + (size_t)2 * G * lay.L);
-}
-
 void launch_fb_segtrans(hipStream_t st, const ScrfKnobs& kn, const ScrfLayout& lay, ScrfBatchView bv, uint32_t u0, uint32_t n_utts,
                         const uint32_t* prev_lab, const double* S, const double* M2, double* AD, double* alpha_g,
                         double* beta_g, double* XI2, double* numer, double* zx, int* status, int write_post) {
   if (n_utts == 0) return;
-  const size_t smw = sizeof(double) * 2 * (size_t)lay.D * lay.L;
-  if (smw <= 150 * 1024) {   // the wavefront-per-window form; larger D * L keeps the column-wise kernel
-    hipFuncSetAttribute((const void*)k_fb_segtrans_w, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smw);
-    // wavefronts per workgroup: 16 when every CU has at most one utterance, 8 (two workgroups per CU) beyond that
-    int nw = n_utts > 256 ? FBW_WAVES / 2 : FBW_WAVES;
-    if (kn.fbw_waves >= 1 && kn.fbw_waves <= FBW_WAVES) nw = kn.fbw_waves;
-    hipLaunchKernelGGL(k_fb_segtrans_w, dim3(n_utts), dim3(64 * nw), smw, st, lay, bv, u0, prev_lab, S, M2, AD, alpha_g, beta_g,
+  const ScrfFbSegtransPlan p = fb_segtrans_plan(kn, dp_shape(lay), n_utts);
+  if (p.wave) {
+    hipFuncSetAttribute((const void*)k_fb_segtrans_w, hipFuncAttributeMaxDynamicSharedMemorySize, (int)p.lds);
+    hipLaunchKernelGGL(k_fb_segtrans_w, dim3(n_utts), dim3(p.threads), p.lds, st, lay, bv, u0, prev_lab, S, M2, AD, alpha_g, beta_g,
                        XI2, numer, zx, status, write_post);
     return;
   }
-  const int NT = fb_block_threads(lay);
-  const size_t sm = fb_segtrans_smem_bytes(lay, NT);
-  hipFuncSetAttribute((const void*)k_fb_segtrans, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sm);
-  hipLaunchKernelGGL(k_fb_segtrans, dim3(n_utts), dim3(NT), sm, st, lay, bv, u0, prev_lab, S, M2, AD, alpha_g, beta_g, XI2,
+  hipFuncSetAttribute((const void*)k_fb_segtrans, hipFuncAttributeMaxDynamicSharedMemorySize, (int)p.lds);
+  hipLaunchKernelGGL(k_fb_segtrans, dim3(n_utts), dim3(p.threads), p.lds, st, lay, bv, u0, prev_lab, S, M2, AD, alpha_g, beta_g, XI2,
                      numer, zx, status, write_post);
 }
 

@@ -22,7 +22,6 @@
 
 typedef double v4f64 __attribute__((ext_vector_type(4)));
 
-#define SL_NT 512          // threads of the recursion workgroup: one per full label (nLabs <= 512)
 #define SL_LOG0 (-1e300)
 #define SL_DBL_MIN 2.2250738585072014e-308   // the smallest normal double
 
@@ -308,7 +307,6 @@ __global__ void k_sl_numer(ScrfBatchView bv, uint32_t u0, uint32_t n_utts, const
 // One wavefront per (K-chunk, duration, group of SA_MG 16-row tiles of p): SA_MG x NT accumulator tiles
 // (NT = ceil(La / 16) <= 4), operands straight from memory, one k-step = 4 frames.
 // ------------------------------------------------------------------------------------------
-#define SA_MG 3
 template <int NT>
 __global__ __launch_bounds__(64) void k_sl_atb(uint32_t NL, uint32_t La, uint32_t D, uint64_t n_frames, uint64_t rows_per_chunk,
                                                const double* __restrict__ Am, const double* __restrict__ Bp,
@@ -385,10 +383,6 @@ __global__ void k_sl_obs(ScrfLayout lay, uint32_t La, ScrfBatchView bv, const ui
 }
 
 // ---- launchers ---------------------------------------------------------------------------------------------------
-int stdseg_lin_supported(const ScrfLayout& lay, uint32_t La) {
-  const size_t sm = sizeof(double) * ((size_t)lay.D * lay.L + 2 * lay.D + lay.L + SL_NT / 64 + 2);
-  return !lay.use_tf && lay.use_tb && lay.L <= SL_NT && La <= 64 && lay.D >= 1 && sm <= 150 * 1024;
-}
 void launch_sl_tables(hipStream_t st, const ScrfLayout& lay, const double* lambda, double* E, double* ET, double* mmax) {
   hipLaunchKernelGGL(k_sl_tables, dim3(1), dim3(1024), 0, st, lay, lambda, E, ET, mmax);
 }
@@ -400,9 +394,9 @@ void launch_sl_fb(hipStream_t st, const ScrfLayout& lay, uint32_t La, ScrfBatchV
                   const double* Sd, const double* E, const double* ET, const double* mmax, double* Ad, double* Bd, double* Am,
                   double* ga, double* zx, int* status) {
   if (n_utts == 0) return;
-  const size_t sm = sizeof(double) * ((size_t)lay.D * lay.L + 2 * lay.D + lay.L + SL_NT / 64 + 2);
-  hipFuncSetAttribute((const void*)k_sl_fb, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sm);
-  hipLaunchKernelGGL(k_sl_fb, dim3(2 * n_utts), dim3(SL_NT), sm, st, lay, La, bv, u0, n_frames, Sd, E, ET, mmax, Ad, Bd, Am, ga, zx, status);
+  const ScrfSlFbPlan p = sl_fb_plan(dp_shape(lay), n_utts);
+  hipFuncSetAttribute((const void*)k_sl_fb, hipFuncAttributeMaxDynamicSharedMemorySize, (int)p.lds);
+  hipLaunchKernelGGL(k_sl_fb, dim3(p.gx), dim3(p.threads), p.lds, st, lay, La, bv, u0, n_frames, Sd, E, ET, mmax, Ad, Bd, Am, ga, zx, status);
 }
 void launch_sl_post(hipStream_t st, const ScrfLayout& lay, uint32_t La, ScrfBatchView bv, const uint32_t* frame_u, uint32_t u0,
                     uint32_t n_utts, uint64_t n_frames, const uint32_t* prev_lab, const double* lambda, const double* Sd,
@@ -420,15 +414,10 @@ void launch_sl_trans_counts(hipStream_t st, const ScrfLayout& lay, uint32_t La, 
                             double* grad) {
   if (n_frames == 0 || n_chunks == 0) return;
   const uint32_t NL = lay.L;
-  const uint32_t n_mt = (NL + 15) / 16, n_mg = (n_mt + SA_MG - 1) / SA_MG;
-  const dim3 grid((uint32_t)((uint64_t)n_chunks * lay.D * n_mg));
-  const uint32_t nt = (La + 15) / 16;
-#define SA_GO(N) hipLaunchKernelGGL(k_sl_atb<N>, grid, dim3(64), 0, st, NL, La, lay.D, n_frames, rows_per_chunk, Am, Bp, slab)
-  if (nt <= 1) SA_GO(1);
-  else if (nt == 2) SA_GO(2);
-  else if (nt == 3) SA_GO(3);
-  else SA_GO(4);
-#undef SA_GO
+  const ScrfSlAtbPlan p = sl_atb_plan(dp_shape(lay), La, n_chunks);
+#define SA_CASE(N) case N: hipLaunchKernelGGL(k_sl_atb<N>, dim3(p.gx), dim3(p.threads), 0, st, NL, La, lay.D, n_frames, rows_per_chunk, Am, Bp, slab); break
+  switch (p.nt) { SA_CASE(1); SA_CASE(2); SA_CASE(3); SA_CASE(4); }
+#undef SA_CASE
   hipLaunchKernelGGL(k_sl_obs, dim3((uint32_t)((n_frames + 255) / 256)), dim3(256), 0, st, lay, La, bv, frame_u, u0, n_frames, prev_lab, obs);
   hipLaunchKernelGGL(k_sl_trans_grad, dim3((NL * NL + 255) / 256), dim3(256), 0, st, lay, n_chunks, slab, E, mmax, obs, grad);
 }

@@ -237,13 +237,12 @@ __global__ __launch_bounds__(1024) void k_transcript(ScrfLayout lay, ScrfBatchVi
   }
 }
 
-size_t transcript_smem_bytes(const ScrfLayout& lay, uint64_t K) { return sizeof(double) * ((size_t)lay.D + 2) * K; }
 
 void launch_transcript(hipStream_t st, const ScrfLayout& lay, ScrfBatchView bv, uint32_t u0, uint32_t n_utts, uint64_t k_max,
                        const double* S, const double* smax, const double* M, int m_per_frame, const ScrfTransArgs& ta,
                        int* status, double* log_num, double* occ, double* endp) {
   if (n_utts == 0) return;
-  const size_t sm = transcript_smem_bytes(lay, k_max ? k_max : 1);   // the chunk's longest transcript that fits
+  const size_t sm = transcript_smem_bytes(dp_shape(lay), k_max ? k_max : 1);   // the chunk's longest transcript that fits
   hipFuncSetAttribute((const void*)k_transcript, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sm);
   hipLaunchKernelGGL(k_transcript, dim3(n_utts), dim3(tr_threads(k_max)), sm, st, lay, bv, u0, S, smax, M, m_per_frame, ta, status,
                      log_num, occ, endp);

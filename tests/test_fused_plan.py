@@ -68,9 +68,9 @@ def _expected():
 # every instantiation the launchers can reach: 24 score kernels, 5 + 5 k_lin_z / k_lin_z5, 30 k_post_z, 4 k_pframe, 10 k_ztf,
 # 36 single-role count kernels, 24 + 48 wave-specialised ones on 76-row tiles (the 4-slot forms under the register cap) and
 # 10 on 100-row tiles (only with SCRF_EXPF_BIG=1 or SCRF_SIDE=0).  A new or vanished one is an edit of this list.
-# launch_expf_fused's switch also names 26 forms that no shape reaches: the 10-slot wave-specialised kernel (two images of
-# 13 column tiles are 182 KB: the plan z-blocks or leaves the shape to the single-role kernel before it gets there) and
-# the 21-step tall form at D <= 12 (whole frames of D <= 12 always fill more than 84 of 100 rows).
+# launch_expf_fused's switch names these and no others (test_the_count_switch_names_exactly_the_reachable_forms): no 10-slot
+# wave-specialised kernel (two images of 13 column tiles are 182 KB: the plan z-blocks or leaves the shape to the single-role
+# kernel before it gets there), no 21-step tall form at D <= 12 (whole frames of D <= 12 always fill more than 84 of 100 rows).
 INSTANTIATIONS = _expected()
 assert len(INSTANTIATIONS) == 24 + 5 + 5 + 30 + 4 + 10 + 36 + 24 + 48 + 10
 
@@ -392,6 +392,24 @@ def test_the_launchers_hold_no_threshold_of_their_own():
     eng = open(os.path.join(CSRC, "scrf_engine.cpp")).read() + open(os.path.join(CSRC, "scrf_kernels.h")).read()
     for name in ("fused_supported", "fused_scores_tb", "fused_expf_plan", "fused_expf_blocks", "lin_z5_segments", "pframe_supported", "fu_sample_step"):
         assert not re.search(r"^\w[\w \*]*\b%s\(.*\)\s*[;{]" % name, src + eng, re.M), name
+
+
+def test_the_count_switch_names_exactly_the_reachable_forms():
+    """the (NT, DMAX, NKS) keys launch_expf_fused's switch names, per count kernel, are those of INSTANTIATIONS"""
+    src = open(os.path.join(CSRC, "scrf_fused.hip")).read()
+    body = re.search(r"^void launch_expf_fused\(.*?^}", src, re.S | re.M).group(0)
+    depths = [(int(dm), int(ks)) for dm, ks in re.findall(r"FE_CASE\(GO, N, (\d+), (\d+)\)", body)]
+    assert depths
+    named = {(go, int(nt), dm, ks) for go, nt in re.findall(r"FE_DEPTHS\((launch_\w+), (\d+)\)", body) for dm, ks in depths}
+    named |= {(go, int(nt), int(dm), int(ks)) for go, nt, dm, ks in re.findall(r"FE_CASE\((launch_\w+), (\d+), (\d+), (\d+)\)", body)}
+    want = set()
+    for name in INSTANTIATIONS:
+        a = [int(x) for x in name[name.index("<") + 1:-1].split(",")]
+        if name.startswith("k_expf_fused<"):
+            want.add(("launch_expf_fused_t", a[0], a[1], a[3]))
+        elif name.startswith("k_expf_fused_ws"):
+            want.add(("launch_expf_ws_t" if a[4] == 76 else "launch_expf_big_t", a[0], a[1], a[2]))
+    assert named == want, sorted(named ^ want)
 
 
 def test_single_calls_match_the_sweep(probes, parsed):

@@ -127,11 +127,11 @@ def test_expf_big_defaults_to_side_stream_off(probe):
 def test_trans_chunks_and_fbw_waves_keep_the_raw_integer(probe):
     assert changed(probe, SCRF_TRANS_CHUNKS="0") == {}     # not forced
     assert changed(probe, SCRF_TRANS_CHUNKS="12") == {"trans_chunks": 12.0}
-    # the range check [1, FBW_WAVES] stays with the constant, in the launcher: the struct carries what was given
+    # the range check [1, FBW_WAVES] stays with the constant, in the launch plan: the struct carries what was given
     assert changed(probe, SCRF_FBW_WAVES="4") == {"fbw_waves": 4.0}
     assert changed(probe, SCRF_FBW_WAVES="99") == {"fbw_waves": 99.0}
     assert changed(probe, SCRF_FBW_WAVES="0") == {}
-    src = open(os.path.join(CSRC, "scrf_segtrans.hip")).read()
+    src = open(os.path.join(CSRC, "scrf_dp_plan.h")).read()
     assert "kn.fbw_waves >= 1 && kn.fbw_waves <= FBW_WAVES" in src
 
 
